@@ -228,3 +228,64 @@ def test_profile_summariser_fails_loudly_without_the_per_phase_split(tmp_path):
     assert r.returncode == 0 and "NO bench line found" in r.stdout      # (without the flag: a warning in the summary)
     sh = open(os.path.join(root, "tools", "evidence.sh")).read()
     assert "--bench-line $OUT/$W/bench.json --require-phases" in sh and "exit 3" in sh
+
+
+def test_steps_below_one_and_more_than_two_hardware_queues_are_errors():
+    for args in (["--steps", "0"], ["--gpus", "2", "--hw-queues", "3"]):
+        r = _run([*args, "--warmup", "0", "--stub"])
+        assert r.returncode != 0 and r.stdout.strip() == b"", args
+
+
+def test_cpu_baseline_reference_says_why_when_oracle_ref_cannot_run(monkeypatch):
+    """A checkout without the reference's program binaries in oracle/_ref: the reference baseline reports why it is missing (the
+    bench then reports the oracle's baseline), it does not take the bench line down."""
+    from oracle import ref_gl
+    bench = _import_bench()
+    monkeypatch.setattr(ref_gl, "available", lambda: "missing brick_raytracer.b8.rgba8.glbin")
+    assert bench.cpu_baseline_reference(None, None, 0.0, {}) == (None, None, "missing brick_raytracer.b8.rgba8.glbin")
+
+
+def test_dump_outputs_writes_float32_and_samples_a_large_frame_alike(tmp_path):
+    """--dump-outputs: a frame that fits is written whole and exactly; a 4K one is cut to the same seeded sample of its pixels on
+    every call, and the files stay under 64 MB in all."""
+    import numpy as np
+    bench = _import_bench()
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 256, size=(256, 256, 4), dtype=np.uint8)
+    assert bench.dump_outputs(str(tmp_path / "s"), {"frame_rgba8": small}) == {"frame_rgba8": [256, 256, 4]}
+    got = np.load(tmp_path / "s" / "frame_rgba8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = rng.integers(0, 256, size=(2160, 3840, 4), dtype=np.uint8)
+    shapes = [bench.dump_outputs(str(tmp_path / d), {"frame_rgba8": big}) for d in ("a", "b")]
+    assert shapes[0] == shapes[1] and shapes[0]["frame_rgba8"][1] == 4 and shapes[0]["frame_rgba8"][0] < 3840 * 2160
+    a, b = (np.load(tmp_path / d / "frame_rgba8.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert os.path.getsize(tmp_path / "a" / "frame_rgba8.npy") <= 64 << 20
+    # every sampled row is a pixel of the frame
+    assert np.isin(np.ascontiguousarray(a.astype(np.uint8)).view(np.uint32), big.reshape(-1, 4).view(np.uint32)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_times_exactly_the_steps_asked_for_and_dumps_the_last_frame(tmp_path):
+    """`bench.py --gpus 1 --steps 4 --dump-outputs DIR`: the timed region holds 4 steps (the rays it reports are those of views V0, V0,
+    V1, V2) and DIR holds the frame of the last one, equal to the frame one context renders at that view."""
+    import numpy as np
+    from zig_vulkan_amd import workloads as W
+    name = "cfg0_256x256_64c_b4"
+    r = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--workload", name, "--no-cpu-baseline", "--pmc", "off",
+              "--dump-outputs", str(tmp_path)], timeout=540)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    out = _one_json_line(r.stdout)
+    rays = out["config"]["rays_per_frame"]
+    assert out["steps"] == 4 and out["ms_per_step"] > 0
+    assert out["rays_timed_region"] == 2 * rays["V0"] + rays["V1"] + rays["V2"]
+    assert out["dump_outputs"]["view"] == "V2" and out["dump_outputs"]["arrays"] == {"frame_rgba8": [256, 256, 4]}
+    got = np.load(tmp_path / "frame_rgba8.npy")
+    w = W.WORKLOADS[name]
+    rt = W.make_renderer(w, W.build_grid(w), device_id=0)
+    W.set_view(rt, "V2")
+    rt.draw()
+    want = rt.read_rgba8()
+    rt.deinit()
+    assert got.dtype == np.float32 and np.array_equal(got, want)
