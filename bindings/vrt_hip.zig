@@ -248,6 +248,25 @@ pub const DenoiseConfig = extern struct { // GraphicsPipeline.Config, GraphicsPi
 pub const VoxXyzi = extern struct { x: u8, y: u8, z: u8, color_index: u8 };
 pub const VoxRgba = extern struct { r: u8, g: u8, b: u8, a: u8 };
 
+/// vrt_cast_rays / vrt_cast_rays_device (include/vrt_hip.h, "Ray queries"): one query, 32 bytes.
+pub const RayQuery = extern struct {
+    origin: [3]f32,
+    max_t: f32 = std.math.inf(f32), // a first hit with t > max_t is reported as a miss
+    direction: [3]f32,
+    flags: u32 = 0, // 0 or RAY_RAW_DIRECTION
+};
+/// One hit record, 48 bytes; a miss is all zero.  The empty voxel in front of the face hit (where a new voxel goes) is
+/// voxel + (normal[0], -normal[1], normal[2]): vrt_grid_insert flips y.
+pub const RayHit = extern struct {
+    point: [3]f32,
+    t: f32,
+    normal: [3]f32,
+    material: u32,
+    voxel: [3]i32,
+    hit: u32,
+};
+pub const RAY_RAW_DIRECTION: u32 = 1 << 0;
+
 // BEGIN GENERATED extern declarations (tools/gen_zig_binding.py from include/vrt_hip.h) — do not edit by hand
 pub extern fn vrt_create(cfg: [*c]const Config, out: *?*Ctx) c_int;
 pub extern fn vrt_destroy(ctx: ?*Ctx) void;
@@ -308,6 +327,9 @@ pub extern fn vrt_grid_delta(g: ?*const Grid, id: BufferId, from: [*c]u64, to: [
 pub extern fn vrt_grid_reset_delta(g: ?*Grid, id: BufferId) void;
 pub extern fn vrt_upload_grid(ctx: ?*Ctx, g: ?*Grid) c_int;
 pub extern fn vrt_update_grid_delta(ctx: ?*Ctx, g: ?*Grid) c_int;
+pub extern fn vrt_cast_rays(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
+pub extern fn vrt_cast_rays_device(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
+pub extern fn vrt_camera_pixel_ray(cam: [*c]const CameraDevice, px: u32, py: u32, origin: *[3]f32, direction: *[3]f32) c_int;
 pub extern fn vrt_camera_init(vertical_fov_deg: f32, image_width: u32, image_height: u32, cfg: [*c]const CameraConfig, out: [*c]CameraDevice) c_int;
 pub extern fn vrt_camera_set_forward(cam: [*c]CameraDevice, vertical_fov_deg: f32, viewport_height: f32, forward: *const [3]f32) c_int;
 pub extern fn vrt_sun_init(cfg: [*c]const SunConfig, out: [*c]SunDevice) c_int;

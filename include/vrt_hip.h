@@ -451,6 +451,52 @@ int vrt_upload_grid(vrt_ctx *ctx, vrt_grid *g);
  * [from,to) of each of the 5 arrays, then resets the deltas. */
 int vrt_update_grid_delta(vrt_ctx *ctx, vrt_grid *g);
 
+/* ---- Ray queries against the uploaded scene --------------------------------
+ * "What does this ray hit?" — picking, line of sight, placement probes — answered on the GPU by the frames' own
+ * GridHit walk (comp:271-376) over the scene the context holds, with the frames' arithmetic: a query is bit-equal to one
+ * GridHit of the reference shader.
+ *
+ * Default ray: CreateRay(origin, direction) (comp:180-184: the direction normalised, ignore type MAT_NONE, internal
+ * reflection 1.0), then GridHit(t_min = 1e-5, t_max = inf).  VRT_RAY_RAW_DIRECTION: the direction is used as given (t is
+ * then in units of |direction|: origin = a, direction = b - a, max_t = 1 asks whether the segment a -> b is blocked).
+ * max_t filters the first hit (it never lets the walk go on to a farther one).  Rays with a non-finite origin or direction
+ * component, a zero direction, or a NaN or negative max_t are misses and are not walked.
+ *
+ * A hit record is point, normal, t and material as the shader's HitRecord holds them (quirks included: the slab-entry
+ * normal of a hit before any DDA step, the 0.05-voxel back-off), and the voxel hit in the coordinates vrt_grid_insert takes
+ * (y counted as insert counts it, Grid.zig:135).  The empty voxel in front of the face that was hit — where an editor places
+ * a new voxel — is voxel + (normal.x, -normal.y, normal.z): insert flips y.  A miss is an all-zero record. */
+typedef struct vrt_ray_query {      /* 32 bytes */
+    float origin[3];
+    float max_t;                    /* a first hit with t > max_t is reported as a miss; INFINITY = no limit */
+    float direction[3];
+    uint32_t flags;                 /* 0 or VRT_RAY_RAW_DIRECTION */
+} vrt_ray_query;
+
+typedef struct vrt_ray_hit {        /* 48 bytes */
+    float point[3];
+    float t;
+    float normal[3];
+    uint32_t material;              /* HitRecord.index: the material_indices entry of the voxel hit (comp:425) */
+    int32_t voxel[3];               /* the voxel hit, in the coordinates vrt_grid_insert takes (y as insert counts it) */
+    uint32_t hit;                   /* 1 = hit; 0 = miss, and then every other field is 0 */
+} vrt_ray_hit;
+
+#define VRT_RAY_RAW_DIRECTION (1u << 0)
+
+/* rays and hits in host memory; blocks until the hits are written.  VRT_E_INVALID_ARG: a NULL pointer with n > 0 or a
+ * ray with unknown flag bits.  VRT_E_STATE: no grid state uploaded yet, a context of the multi-GPU pipeline, or the
+ * query code object (vrt_query.hsaco next to the library) missing — vrt_last_error names its path.  n == 0: VRT_OK.
+ * A failed query leaves the context usable for frames. */
+int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits);
+/* rays and hits in device memory; ordered on the context's stream after every upload so far; asynchronous (vrt_wait).
+ * The flags are not read on the host here: a ray with unknown flag bits gets a miss record. */
+int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits);
+/* the un-normalised direction and the origin of the one-sample camera ray the frame traces for pixel (px, py), with
+ * (px, py) as in the image vrt_read_rgba8 returns (CameraGetRay, comp:474-477, without jitter).  VRT_E_INVALID_ARG: a NULL
+ * pointer; VRT_E_OUT_OF_RANGE: a pixel outside the camera's image. */
+int vrt_camera_pixel_ray(const vrt_camera_device *cam, uint32_t px, uint32_t py, float origin[3], float direction[3]);
+
 /* ---- Camera (Camera.zig:36-77,162-180) and Sun (Sun.zig:35-63) ----------- */
 typedef struct vrt_camera_config {     /* Camera.zig:5-14 (render-relevant part) */
     float viewport_height;             /* default 2                              */

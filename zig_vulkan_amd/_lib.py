@@ -146,7 +146,19 @@ class SunConfig(C.Structure):  # Sun.zig:4-11
     _fields_ = [("enabled", C.c_uint32), ("color", C.c_float * 3), ("radius", C.c_float), ("sun_distance", C.c_float)]
 
 
+class RayQuery(C.Structure):  # vrt_ray_query (32 bytes)
+    _fields_ = [("origin", C.c_float * 3), ("max_t", C.c_float), ("direction", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+class RayHit(C.Structure):  # vrt_ray_hit (48 bytes)
+    _fields_ = [("point", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("material", C.c_uint32),
+                ("voxel", C.c_int32 * 3), ("hit", C.c_uint32)]
+
+
+RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
+
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
+assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -219,6 +231,9 @@ SIGNATURES = {
     "vrt_grid_reset_delta": (None, [_grid, C.c_int]),
     "vrt_upload_grid": (C.c_int, [_ctx, _grid]),
     "vrt_update_grid_delta": (C.c_int, [_ctx, _grid]),
+    "vrt_cast_rays": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_cast_rays_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),
     "vrt_camera_set_forward": (C.c_int, [_P(CameraDevice), C.c_float, C.c_float, _P(C.c_float * 3)]),
     "vrt_sun_init": (C.c_int, [_P(SunConfig), _P(SunDevice)]),
@@ -281,6 +296,8 @@ lib = load_library(LIB_PATH)
 # test-infrastructure twins of the product library (zig_vulkan_amd/csrc/Makefile); absent unless built
 FUSED_LIB_PATH = os.path.join(_HERE, "libvrt_hip_fused.so")    # fma fused, dot as an fma chain (make fused): how far fusing moves the frames
 DEV_LIB_PATH = os.path.join(_HERE, "libvrt_hip_dev.so")        # + the variants that lost their A/B measurement (make dev)
+# the ray-query kernels (vrt_cast_rays) of the product library: a code object of their own, loaded by the library from its own directory
+QUERY_CODE_OBJECT_PATH = os.path.join(_HERE, "vrt_query.hsaco")
 
 
 def rccl_library_path() -> str:

@@ -35,6 +35,7 @@ void free_ctx(vrt_ctx *c) {
     if (!c) return;
     DeviceGuard dg(c->device); // the caller's current device is restored on return
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    query_release(c);
     dist_destroy(c);      // (its streams are drained and its communicator closed before the memory they use goes)
     c->res.release_all(); // every allocation, event and stream the context made, in reverse order
     delete c;
@@ -791,6 +792,7 @@ int vrt_upload(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, const void 
     if (id == VRT_BUF_GRID_STATE) {
         // the kernel takes the UBO through its argument block; keep the host mirror current
         std::memcpy(reinterpret_cast<uint8_t *>(&ctx->params.grid) + byte_offset, src, (size_t)nbytes);
+        ctx->grid_uploaded = true;
     }
     mark_dirty(ctx, id, byte_offset, nbytes);
     return copy_h2d(ctx, static_cast<uint8_t *>(ctx->dbuf[id]) + byte_offset, src, nbytes);
@@ -804,6 +806,7 @@ int vrt_upload_device(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, cons
         VRT_HIP(ctx, hipMemcpyAsync(reinterpret_cast<uint8_t *>(&ctx->params.grid) + byte_offset, dev_src, nbytes, hipMemcpyDeviceToHost,
                                     ctx->stream));
         VRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->grid_uploaded = true;
     }
     mark_dirty(ctx, id, byte_offset, nbytes);
     const int rcb = begin_scene_write(ctx);

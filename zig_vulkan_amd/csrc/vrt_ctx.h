@@ -3,6 +3,7 @@
 //   vrt_frame.hip  one frame: refresh of the derived structures, kernel choice, tile schedule, launch, timing
 //   vrt_dist.hip   the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip   the present / denoise pass
+//   vrt_query.hip  batched ray queries (its kernels: vrt_query_kernel.hip, in a code object of their own)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
 #pragma once
@@ -203,6 +204,13 @@ struct vrt_ctx {
     bool start_dirty = true;                 // binding 6 changed since it was checked
     vrt::TileOwnership own{};        // weighted tile ownership (period 0: tile t belongs to rank t % shard_count)
     bool status_dirty = true;        // brick_status changed since the derived copy was built
+    bool grid_uploaded = false;      // binding 1 has been uploaded (ray queries need the grid's geometry)
+    // ray queries (vrt_query.hip): the code object, loaded on the first query and unloaded by vrt_destroy; the host path's device buffers
+    hipModule_t query_module = nullptr;
+    hipFunction_t query_fn = nullptr;
+    vrt_ray_query *d_query_rays = nullptr;
+    vrt_ray_hit *d_query_hits = nullptr;
+    uint64_t query_capacity = 0;     // rays the two buffers hold
     size_t lds_bytes = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool split_ok = false;   // small frames may go to half-tile workgroups (vrt_create's conditions other than the number of waves)
@@ -318,8 +326,14 @@ int finish_frame(vrt_ctx *c);                   // wait for the frame in flight 
 int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_device *sun, vrt::PersistentLane *lane, hipStream_t lane_stream, vrt::KernelFn *fn,
                  vrt::KernelFn *product_fn, bool *with_samples, int trial = -1);
 bool lane_samples_ready(vrt_ctx *ctx, vrt::PersistentLane &lane, uint64_t units, hipStream_t lane_stream);
+// the grid-scale reciprocals of TraceParams and every structure derived from the scene buffers, brought up to date with the uploads so far
+// (stream-ordered on the primary stream): the part of pre_dispatch that frames and ray queries share
+int refresh_derived(vrt_ctx *ctx);
 uint64_t sample_units(const vrt_ctx *ctx, int samples_per_pixel); // units of a frame of this context (0: not a frame of units)
 void lane_into_params(const vrt::PersistentLane &lane, bool with_samples, vrt::TraceParams &p);
+
+// ---- vrt_query.hip ----
+void query_release(vrt_ctx *ctx); // unloads the query code object (vrt_destroy; the memory is Resources')
 
 // ---- vrt_dist.hip ----
 int dist_flush(vrt_ctx *ctx);

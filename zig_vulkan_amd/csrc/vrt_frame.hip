@@ -88,20 +88,7 @@ static vrt::KernelFn grid_exit_choice(vrt_ctx *ctx, vrt::KernelFn exit_fn, vrt::
     return exit_path ? exit_path : keep;
 }
 
-// Common front part of a frame: argument checks, push constants, derived-structure refresh.  Leaves the kernel to launch in *fn —
-// for a counting context in *product_fn too: the product kernel that renders the frame read back.  Runs on the primary stream.
-// with_samples: the kernel of the frame (a persistent one) takes samples as its units of work from `lane`'s buffer.
-int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_device *sun, vrt::PersistentLane *lane, hipStream_t lane_stream, vrt::KernelFn *fn,
-                 vrt::KernelFn *product_fn, bool *with_samples, int trial) {
-    if (!ctx || !camera || !sun) return ctx ? fail(ctx, VRT_E_INVALID_ARG, "NULL camera/sun") : VRT_E_INVALID_ARG;
-    if (camera->image_width != ctx->cfg.width || camera->image_height != ctx->cfg.height)
-        return fail(ctx, VRT_E_INVALID_ARG, "camera image size differs from the target image");
-    // The reference blocks here on the previous frame's fence because it re-records its one
-    // command buffer (ComputePipeline.zig:423-436).  Launches are stream-ordered and carry their
-    // arguments by value, so frames may queue; vrt_wait / vrt_read_* are the synchronisation points.
-    ctx->in_flight = false;
-    ctx->params.pcs[0].cam = *camera;
-    ctx->params.pcs[0].sun = *sun;
+int refresh_derived(vrt_ctx *ctx) {
     const vrt_grid_state &g = ctx->params.grid;
     {
         auto pow2_with_normal_reciprocal = [](float v) {
@@ -119,7 +106,6 @@ int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_de
     }
     if (g.dim_x != 0 && (g.dim_x != ctx->cfg.dim_x || g.dim_y != ctx->cfg.dim_y || g.dim_z != ctx->cfg.dim_z))
         return fail(ctx, VRT_E_INVALID_ARG, "uploaded grid state has other brick dimensions than the context was created with");
-    if (ctx->d_counters) VRT_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(vrt::DeviceCounters), ctx->stream));
     if (ctx->status_dirty) {
         // refresh the derived block words / filter from the uploaded status bits (stream-ordered after the uploads)
         int rcw = begin_scene_write(ctx);
@@ -167,6 +153,26 @@ int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_de
     }
     ctx->cell_material_dirty = false;
     ctx->cm_cell_lo = ctx->cm_cell_hi = ctx->cm_slot_lo = ctx->cm_slot_hi = ctx->cm_mat_lo = ctx->cm_mat_hi = 0;
+    return VRT_OK;
+}
+
+// Common front part of a frame: argument checks, push constants, derived-structure refresh.  Leaves the kernel to launch in *fn —
+// for a counting context in *product_fn too: the product kernel that renders the frame read back.  Runs on the primary stream.
+// with_samples: the kernel of the frame (a persistent one) takes samples as its units of work from `lane`'s buffer.
+int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_device *sun, vrt::PersistentLane *lane, hipStream_t lane_stream, vrt::KernelFn *fn,
+                 vrt::KernelFn *product_fn, bool *with_samples, int trial) {
+    if (!ctx || !camera || !sun) return ctx ? fail(ctx, VRT_E_INVALID_ARG, "NULL camera/sun") : VRT_E_INVALID_ARG;
+    if (camera->image_width != ctx->cfg.width || camera->image_height != ctx->cfg.height)
+        return fail(ctx, VRT_E_INVALID_ARG, "camera image size differs from the target image");
+    // The reference blocks here on the previous frame's fence because it re-records its one
+    // command buffer (ComputePipeline.zig:423-436).  Launches are stream-ordered and carry their
+    // arguments by value, so frames may queue; vrt_wait / vrt_read_* are the synchronisation points.
+    ctx->in_flight = false;
+    ctx->params.pcs[0].cam = *camera;
+    ctx->params.pcs[0].sun = *sun;
+    const int rcr = refresh_derived(ctx);
+    if (rcr != VRT_OK) return rcr;
+    if (ctx->d_counters) VRT_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(vrt::DeviceCounters), ctx->stream));
     // max_bounce <= 1 ("only primary ray" + its shadow ray): the bounce loop runs at most once
     *fn = (camera->max_bounce <= 1) ? (camera->samples_per_pixel == 1 ? ctx->kernel_single1 : ctx->kernel_single) : ctx->kernel;
     if (ctx->bounds_pending && hipEventQuery(ctx->ev_bounds) == hipSuccess) {

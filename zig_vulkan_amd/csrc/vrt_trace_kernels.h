@@ -941,13 +941,15 @@ VRT_DI bool brick_walk(const TraceParams &p, const Ray &r, const RaySetup &s, fl
 // The loop returns when some lane has left a solid voxel behind; the material test (comp:422-427) and the hit
 // record are done here, and lanes whose voxel is to be ignored walk on.  `axis_in`: the face through which the
 // brick was entered (the brick-level walk's crossed axis), used when the very first voxel is the hit.
+// VOXEL (ray queries, vrt_query_kernel.hip): the index in its brick of the voxel hit, x + B (z + B y) (comp:412), is also left in
+// *hit_voxel; the frames' kernels compile without it.
 // BY_CELL (round 4, frames with bounces on scenes that stay in the caches): the brick's bits are read from the by-cell copy
 // (TraceParams::cell_occupancy, `cell` = the grid cell) when the context holds one, so that the request for them does not wait for
 // brick_index[cell] (comp:337) — which then only the material look-up of a solid voxel needs.  Such frames last as long as their slowest
 // wave, and that wave's time is its chain of brick entries: one dependent round trip less per entry.
-template <int B, bool EAGER = true, bool BY_CELL = false>
+template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false>
 VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min, Hit &hit,
-                              int axis_in, int &hit_axis, uint32_t cell = 0u) {
+                              int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr) {
     const float brick_voxel_scale = 1.0f / (float)B; // spec const 5, Pipeline.zig:313
     const float voxel_scale = g_scale * brick_voxel_scale;
     const f3 fposition = p.scale_pow2 ? (ray_at(r, hit.t) - brick_min) * p.inv_voxel_scale : (ray_at(r, hit.t) - brick_min) / splat3(voxel_scale);
@@ -1016,6 +1018,7 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup
                 const float t_offset = voxel_scale * 0.05f;
                 hit.t += g.t_in * voxel_scale - t_offset; // t_value of the step into this voxel (comp:442), 0 for the first
                 hit_axis = a;
+                if constexpr (VOXEL) *hit_voxel = voxel_index;
                 found = true;
             }
             VRT_PROF_END(4, tp4);
@@ -1297,8 +1300,12 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 
 // SCALAR_ENTRY: the grid-entry offset 0.0001 * scale (comp:287) formed where it is used (the several-samples kernel; the one-sample
 // kernels measured 0.5 % slower with it and keep the compiler's placement)
-template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false>
-VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c) {
+// VOXEL (ray queries, vrt_query_kernel.hip; the hand-written walks only): on a hit, voxel[0..2] = the voxel's position in the grid's voxel
+// coordinates of the walk (y as the shader counts it, cell * B + position in the brick) — integers from the walk, not derived from hit.point
+template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false>
+VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr) {
+    static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
+                  "voxel coordinates come from the hand-written walk without batching");
     const float t_min = 0.00001f;
     const float t_max = __builtin_inff();
     VRT_COUNT(rays);
@@ -1435,7 +1442,15 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         VRT_COUNT_WAVE(wave_brick_walks);
         bool found;
         if constexpr ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT) {
-            found = brick_walk_gfx950<B, true, BATCH>(p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell);
+            [[maybe_unused]] uint32_t voxel_in_brick = 0u;
+            found = brick_walk_gfx950<B, true, BATCH, VOXEL>(p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick);
+            if constexpr (VOXEL) {
+                if (found) { // voxel index x + B (z + B y) in the brick (comp:412)
+                    voxel[0] = cx * B + (int)(voxel_in_brick % (uint32_t)B);
+                    voxel[1] = cy * B + (int)(voxel_in_brick / (uint32_t)(B * B));
+                    voxel[2] = cz * B + (int)((voxel_in_brick / (uint32_t)B) % (uint32_t)B);
+                }
+            }
         } else {
             found = brick_walk<B, COUNT, MODE == kStatusLinear || MODE == kStatusLinearLds || MODE == kStatusLinearAhead>(
                 p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, c);

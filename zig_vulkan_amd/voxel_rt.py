@@ -150,6 +150,13 @@ class Camera:
     def blob(self) -> bytes:
         return bytes(self.d_camera)
 
+    def pixel_ray(self, px: int, py: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(origin, un-normalised direction) of the one-sample camera ray the frame traces for pixel (px, py) of the image
+        read_rgba8 returns (CameraGetRay, comp:474-477, without jitter) — what cast_rays takes to pick the voxel under a pixel."""
+        o, d = (C.c_float * 3)(), (C.c_float * 3)()
+        check(lib.vrt_camera_pixel_ray(C.byref(self.d_camera), px, py, C.byref(o), C.byref(d)))
+        return np.array(o[:], dtype=np.float32), np.array(d[:], dtype=np.float32)
+
 
 @dataclass
 class SunConfig:  # Sun.zig:4-11
@@ -187,6 +194,23 @@ def default_materials(capacity: int = 256) -> np.ndarray:
 MATERIAL_DTYPE = np.dtype([("type", np.uint32), ("albedo_r", np.float32), ("albedo_g", np.float32),
                            ("albedo_b", np.float32), ("type_data", np.float32)])
 assert MATERIAL_DTYPE.itemsize == 20
+
+# vrt_ray_query / vrt_ray_hit (include/vrt_hip.h) as numpy records
+RAY_QUERY_DTYPE = np.dtype([("origin", np.float32, 3), ("max_t", np.float32), ("direction", np.float32, 3), ("flags", np.uint32)])
+RAY_HIT_DTYPE = np.dtype([("point", np.float32, 3), ("t", np.float32), ("normal", np.float32, 3), ("material", np.uint32),
+                          ("voxel", np.int32, 3), ("hit", np.uint32)])
+assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 48
+
+
+def ray_queries(origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
+    """Host records of vrt_ray_query: origins (n, 3) or one (3,) for all, directions (n, 3), max_t None (no limit), a number or (n,)."""
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    q = np.zeros(d.shape[0], dtype=RAY_QUERY_DTYPE)
+    q["origin"] = np.broadcast_to(np.asarray(origins, dtype=np.float32), d.shape)
+    q["direction"] = d
+    q["max_t"] = np.inf if max_t is None else np.asarray(max_t, dtype=np.float32)
+    q["flags"] = L.RAY_RAW_DIRECTION if raw else 0
+    return q
 
 
 class Benchmark:
@@ -327,6 +351,34 @@ class VoxelRT:
 
     def wait(self) -> None:
         self._check(self._lib.vrt_wait(self._h))
+
+    # -- ray queries ----------------------------------------------------------
+    def cast_rays(self, origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
+        """First hit of each ray against the uploaded scene (vrt_cast_rays): a RAY_HIT_DTYPE record per ray, all zero for a miss.
+        origins (n, 3) or one (3,) for all rays, directions (n, 3); max_t None (no limit), a number or one per ray; raw: the
+        directions are used as given (t in units of |direction|) instead of normalised.  Given torch tensors on the GPU, the queries
+        are formed and answered in device memory (vrt_cast_rays_device, behind torch's current stream) and only the hits are copied back."""
+        if getattr(directions, "is_cuda", False):
+            return self._cast_rays_device(origins, directions, max_t, raw)
+        q = ray_queries(origins, directions, max_t, raw)
+        hits = np.zeros(q.shape[0], dtype=RAY_HIT_DTYPE)
+        self._check(self._lib.vrt_cast_rays(self._h, q.ctypes.data, q.shape[0], hits.ctypes.data))
+        return hits
+
+    def _cast_rays_device(self, origins, directions, max_t, raw: bool) -> np.ndarray:
+        import torch
+        d = directions.reshape(-1, 3)
+        n = d.shape[0]
+        q = torch.empty((n, 8), dtype=torch.float32, device=d.device)
+        q[:, 0:3] = torch.as_tensor(origins, dtype=torch.float32, device=d.device).reshape(-1, 3).expand(n, 3)
+        q[:, 3] = float("inf") if max_t is None else torch.as_tensor(max_t, dtype=torch.float32, device=d.device)
+        q[:, 4:7] = d
+        q.view(torch.int32)[:, 7] = L.RAY_RAW_DIRECTION if raw else 0
+        hits = torch.empty((n, 12), dtype=torch.float32, device=d.device)
+        torch.cuda.current_stream(d.device).synchronize()  # (the queries are written on torch's stream; the library's is another)
+        self._check(self._lib.vrt_cast_rays_device(self._h, q.data_ptr(), n, hits.data_ptr()))
+        self.wait()
+        return hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
 
     def region_begin(self) -> None:
         self._check(self._lib.vrt_region_begin(self._h))
