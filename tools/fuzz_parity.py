@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Randomised parity fuzz (usage: fuzz_parity.py [cases] [seed] [big|pow2|pool]; pow2: grids and frames that take vrt_path_kernel's block-skipping walk;
+"""Randomised parity fuzz (usage: fuzz_parity.py [cases] [seed] [big|pow2|pool|reject]; reject: every case on 8^3 bricks at 1 spp without bounces — the one-sample
+kernel with its brick rejection test (brick_reject, TraceParams::cell_box); pow2: grids and frames that take vrt_path_kernel's block-skipping walk;
 pool: the pow2 draw narrowed to what vrt_pool_kernel takes — both brick sizes (round 5), three power-of-two dimensions, two or three
 bounces; voxels in two opposite corners so that the occupied cells' box is the grid, or (three cases in ten) any box with
 VRT_TUNE_GRID_EXIT_ANY_BOX; half of the cases with ONE material per brick (the byte-per-cell material, TraceParams::cell_material)): random small grids (odd dimensions, both brick sizes, any
@@ -14,7 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from zig_vulkan_amd import BrickGrid, Config, CameraConfig, SunConfig, VoxelRT, default_materials
 from helpers import O, oracle_scene_from_grid
 
-def fuzz(cases: int, seed: int, big: bool = False, verbose: bool = True, pow2: bool = False, library=None, pool: bool = False) -> int:
+def fuzz(cases: int, seed: int, big: bool = False, verbose: bool = True, pow2: bool = False, library=None, pool: bool = False, reject: bool = False) -> int:
     """Returns the number of mismatching cases.  library: path of the development build (make dev) — the variants that lost their
     A/B measurement then take part in the draw; without it only the kernels of the product build are drawn."""
     dev = library is not None
@@ -28,6 +29,8 @@ def fuzz(cases: int, seed: int, big: bool = False, verbose: bool = True, pow2: b
     used = {}
     for case in range(cases):
         b = int(rng.choice([4, 8]))
+        if reject:
+            b = 8
         dims = [int(rng.integers(1, 25 if big else 9)) for _ in range(3)]
         if pow2:  # grids the path kernel's block filter accepts: x, z powers of two >= 4, y a multiple of 4
             dims = [int(rng.choice([4, 8, 16, 32])), int(rng.choice([4, 8, 12, 16, 20])), int(rng.choice([4, 8, 16, 32]))]
@@ -74,12 +77,14 @@ def fuzz(cases: int, seed: int, big: bool = False, verbose: bool = True, pow2: b
         spp, bounce = int(rng.integers(1, 4)), int(rng.integers(0, 3))
         if pow2:
             bounce = int(rng.integers(2 if pool else 1, 4))
+        if reject:
+            spp, bounce = 1, 0
         sun_on, radius = bool(rng.random() < 0.7), float(rng.choice([0.0, 5.0, 40.0]))
         rt = VoxelRT(grid, Config(internal_resolution_width=w, internal_resolution_height=h, camera=CameraConfig(samples_per_pixel=spp, max_bounce=bounce),
                                   sun=SunConfig(enabled=sun_on, radius=radius), want_float_output=True,
                                   library=library, tuning_flags=(1 << 19) if any_box else 0,
                                   kernel_variant=PATH if pool else (int(rng.choice(big_variants)) if big
-                                  else int(rng.choice(pow2_variants) if pow2 else rng.choice([0, 0, PATH])))))
+                                  else int(rng.choice(pow2_variants) if pow2 else (0 if reject else rng.choice([0, 0, PATH]))))))
         rt.push_materials(mats)
         size = np.array(dims) * scale
         centre = np.array(min_point) + 0.5 * size
@@ -130,4 +135,4 @@ def fuzz(cases: int, seed: int, big: bool = False, verbose: bool = True, pow2: b
 if __name__ == "__main__":
     sys.exit(1 if fuzz(int(sys.argv[1]) if len(sys.argv) > 1 else 40, int(sys.argv[2]) if len(sys.argv) > 2 else 7,
                        len(sys.argv) > 3 and sys.argv[3] in ("big", "pow2", "pool"), pow2=len(sys.argv) > 3 and sys.argv[3] == "pow2",
-                       pool=len(sys.argv) > 3 and sys.argv[3] == "pool") else 0)
+                       pool=len(sys.argv) > 3 and sys.argv[3] == "pool", reject=len(sys.argv) > 3 and sys.argv[3] == "reject") else 0)

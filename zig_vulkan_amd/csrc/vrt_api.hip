@@ -603,6 +603,13 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
             VRT_CREATE_HIP(c->res.device(&c->d_cell_material, (size_t)cells + 64u));
             VRT_CREATE_HIP(hipMemsetAsync(c->d_cell_material, 0xFF, (size_t)cells + 64u, c->stream));
         }
+        // the box of a cell's solid voxels, for the brick rejection test of the one-sample kernel on 8^3 bricks (brick_reject): 4 bytes per
+        // cell, 1 MiB at 64^3 cells; at most 16 MiB (not on the 2048^3 scenes, whose frames the persistent kernels trace; without the
+        // array the kernel rejects nothing).  Starts as the whole brick, which never rejects; the first frame builds it for every occupied cell.
+        if (cells <= (1ull << 22) && any_kernel([](const vrt::KernelEntry &e) { return vrt::reads_cell_box(e); })) {
+            VRT_CREATE_HIP(c->res.device(&c->d_cell_box, (size_t)cells * 4u + 64u));
+            VRT_CREATE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_cell_box), (int)vrt::full_cell_box(cfg->brick_dimension), cells + 16u, c->stream));
+        }
         if (!(cfg->tuning_flags & VRT_TUNE_NO_DEFERRED_MATERIAL)) {
             VRT_CREATE_HIP(c->res.device(&c->d_materials_plain, 64u));
             VRT_CREATE_HIP(hipMemsetAsync(c->d_materials_plain, 0, 64u, c->stream));
@@ -707,6 +714,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     p.start_is_slot = c->d_start_is_slot;
     p.materials_plain = c->d_materials_plain;
     p.cell_material = c->d_cell_material;
+    p.cell_box = c->d_cell_box;
     p.status_cells = (uint32_t)cells;
     // (order_auto: frames that alternate between the two streams of a frames_in_flight = 2 context take reverse raster (3)
     // instead, see do_dispatch and DESIGN.md §4)

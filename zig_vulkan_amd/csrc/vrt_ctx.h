@@ -197,6 +197,9 @@ struct vrt_ctx {
     // select vrt_pool_kernel).  Refreshed like the by-cell occupancy, for what was written: cells [occ_cell_lo, hi) (status / index),
     // slots [cm_slot_lo, hi) (occupancy / start index), material entries [cm_mat_lo, hi) (bytes of binding 7); lo >= hi: none
     uint8_t *d_cell_material = nullptr;
+    // derived: the box of the solid voxels of a cell's brick, a word per cell (TraceParams::cell_box; contexts that select the one-sample
+    // kernel on 8^3 bricks).  Built by the same pass and for the same written ranges as d_cell_material
+    uint32_t *d_cell_box = nullptr;
     bool cell_material_dirty = true;
     uint64_t cm_cell_lo = 0, cm_cell_hi = ~0ull, cm_slot_lo = 0, cm_slot_hi = 0, cm_mat_lo = 0, cm_mat_hi = 0;
     uint32_t *d_materials_plain = nullptr;   // derived: 1 = no material record has the type MAT_NONE (TraceParams::materials_plain)

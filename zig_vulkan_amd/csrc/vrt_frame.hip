@@ -143,7 +143,7 @@ int refresh_derived(vrt_ctx *ctx) {
     }
     ctx->occupancy_dirty = ctx->start_dirty = ctx->materials_dirty = false;
     ctx->occ_cell_lo = ctx->occ_cell_hi = ctx->occ_slot_lo = ctx->occ_slot_hi = 0;
-    if (ctx->cell_material_dirty && ctx->d_cell_material) {
+    if (ctx->cell_material_dirty && (ctx->d_cell_material || ctx->d_cell_box)) {
         int rcw = begin_scene_write(ctx);
         if (rcw != VRT_OK) return rcw;
         VRT_HIP(ctx, vrt::launch_build_cell_material(ctx->params, ctx->cfg.brick_dimension, ctx->cfg.brick_alloc, ctx->cm_cell_lo, ctx->cm_cell_hi, ctx->cm_slot_lo, ctx->cm_slot_hi,

@@ -102,6 +102,10 @@ struct TraceParams {
     // a third of the path trace's fabric traffic); where a brick is of one material — every brick of a sphere, most bricks of a
     // terrain's height band — the hit needs this one byte instead, from an array 128 times smaller than material_index.
     const uint8_t *cell_material;
+    // derived from bindings 3-5 (nullptr: not built; contexts that select the one-sample kernel on 8^3 bricks): one word per grid cell — the
+    // box of the solid voxels of the cell's brick, lo x, y, z then hi x, y, z in voxels, log2(B) bits each (the whole brick: unknown or
+    // empty).  Keyed by cell, so that its request does not wait for brick_index[cell].  Read by brick_reject (vrt_trace_kernels.h).
+    const uint32_t *cell_box;
     // derived, device-built copy of brick_status: one 64-bit word per 4x4x4 block of grid cells,
     // block index bx + nbx*(bz + nbz*by), bit (x&3) + 4*(z&3) + 16*(y&3)  (x, z, y order as comp:318)
     const uint2 *status_blocks;

@@ -66,6 +66,12 @@ const KernelEntry *find_trace_kernel(int b, bool count, int mode, int min_waves,
 const KernelEntry *find_path_kernel(int b, int min_waves, bool filter, bool half, bool ahead = false, bool dist = false, int dil = 0);
 const KernelEntry *find_pool_kernel(int b, int min_waves = 0, int slots = 0, int stages = 0); // (0: the first in the table = the library's choice)
 const KernelEntry *kernel_entry_of(KernelFn fn);
+// The kernels that test each brick entry against the box of the brick's solid voxels first (TraceParams::cell_box, brick_reject):
+// the one-sample kernel on 8^3 bricks and the status-byte walk.  vrt_trace_kernel spells the same condition at compile time.
+constexpr bool reads_cell_box(int path, int b, bool count, int mode, int shade) { return path == 0 && b == 8 && !count && mode == kStatusBytes && shade == 2; }
+inline bool reads_cell_box(const KernelEntry &e) { return reads_cell_box(e.path, e.b, e.count != 0, e.mode, e.shade); }
+// TraceParams::cell_box of a brick whose box is unknown or that holds no solid voxel: the whole brick (never rejected)
+constexpr uint32_t full_cell_box(uint32_t b) { return b == 8u ? (0777u << 9) : (077u << 6); }
 // vrt_pool_resolve_kernel (vrt_pool_kernel.h) over the pixels of the owned tiles, behind a vrt_pool_kernel on the same stream
 hipError_t launch_pool_resolve(const TraceParams &p, hipStream_t stream);
 int compiled_kernel_count();

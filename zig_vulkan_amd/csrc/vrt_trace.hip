@@ -140,10 +140,14 @@ __global__ __launch_bounds__(256) void vrt_build_cell_occupancy(const uint32_t *
 // (status bit / brick index in [cell_lo, cell_hi)), its brick's slot (occupancy bytes / start index in [slot_lo, slot_hi)) or its
 // brick's material entries (bytes [mat_lo, mat_hi) of binding 7) — the lanes share the brick's voxels (B^3 / 64 each), find the first
 // solid voxel's material and whether every other solid voxel has it too.  0xFF: mixed, no solid voxel, a malformed brick, or the id 255.
+// The same pass builds TraceParams::cell_box (`box`, when not null; `out` may then be null): the box of the brick's solid voxels, from the
+// coordinates each lane's voxels have — the whole brick where there is none or the brick is malformed.  (Its inputs are a subset of the
+// material byte's, so the material's written ranges cover it; one builder, not two: the product binary keeps its kernel count.)
 template <int B>
 __global__ __launch_bounds__(256) void vrt_build_cell_material(const uint32_t *__restrict__ status, const uint32_t *__restrict__ brick_index,
                                                                const uint8_t *__restrict__ occupancy, const uint32_t *__restrict__ start_index,
-                                                               const uint8_t *__restrict__ material_index, uint8_t *__restrict__ out, uint32_t cells,
+                                                               const uint8_t *__restrict__ material_index, uint8_t *__restrict__ out,
+                                                               uint32_t *__restrict__ box, uint32_t cells,
                                                                uint32_t status_words, uint64_t brick_alloc, uint64_t material_bytes, uint64_t cell_lo,
                                                                uint64_t cell_hi, uint64_t slot_lo, uint64_t slot_hi, uint64_t mat_lo, uint64_t mat_hi) {
     constexpr uint32_t kBits = B * B * B, kPerLane = kBits / 64u;
@@ -158,10 +162,38 @@ __global__ __launch_bounds__(256) void vrt_build_cell_material(const uint32_t *_
         const uint64_t cell = base + b;
         if (cell >= cells) break;
         const uint32_t slot = brick_index[cell];
-        if (slot >= brick_alloc) continue; // (malformed scene: the shader would read outside bindings 5 / 6)
+        if (slot >= brick_alloc) { // (malformed scene: the shader would read outside bindings 5 / 6)
+            if (box && lane == 0u && cell >= cell_lo && cell < cell_hi) box[cell] = full_cell_box(B);
+            continue;
+        }
         const uint64_t start = start_index[slot] & 0x7FFFFFFFu; // comp:422
         const bool written = (cell >= cell_lo && cell < cell_hi) || (slot >= slot_lo && slot < slot_hi) || (start < mat_hi && start + kBits > mat_lo);
         if (!written) continue;
+        if (box) {
+            // per lane: a bit per coordinate value its solid voxels have (voxel v = x + B (z + B y), comp:412); OR-ed over the wave by ballots
+            uint32_t xs, ys, zs;
+            if constexpr (kPerLane == 8u) { // lane = z + 8 y, its byte holds x = 0..7
+                const uint32_t occ = occupancy[(uint64_t)slot * (kBits / 8u) + lane];
+                xs = occ, ys = occ ? 1u << (lane >> 3) : 0u, zs = occ ? 1u << (lane & 7u) : 0u;
+            } else { // lane = v
+                const bool s = ((occupancy[(uint64_t)slot * (kBits / 8u) + (lane >> 3)] >> (lane & 7u)) & 1u) != 0u;
+                xs = s ? 1u << (lane & 3u) : 0u, ys = s ? 1u << (lane >> 4) : 0u, zs = s ? 1u << ((lane >> 2) & 3u) : 0u;
+            }
+            uint32_t mx = 0u, my = 0u, mz = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < (uint32_t)B; k++) {
+                mx |= __builtin_amdgcn_ballot_w64(((xs >> k) & 1u) != 0u) ? 1u << k : 0u;
+                my |= __builtin_amdgcn_ballot_w64(((ys >> k) & 1u) != 0u) ? 1u << k : 0u;
+                mz |= __builtin_amdgcn_ballot_w64(((zs >> k) & 1u) != 0u) ? 1u << k : 0u;
+            }
+            constexpr uint32_t n = B == 8 ? 3u : 2u;
+            auto lo = [](uint32_t m) { return (uint32_t)__builtin_ctz(m); };
+            auto hi = [](uint32_t m) { return 31u - (uint32_t)__builtin_clz(m); };
+            if (lane == 0u)
+                box[cell] = mx == 0u ? full_cell_box(B)
+                                     : (lo(mx) | lo(my) << n | lo(mz) << 2u * n | hi(mx) << 3u * n | hi(my) << 4u * n | hi(mz) << 5u * n);
+        }
+        if (!out) continue;
         uint32_t first = 0xFFu;
         bool solid = false, same = true;
         if (start + kBits <= material_bytes) {
@@ -761,7 +793,7 @@ hipError_t launch_build_cell_occupancy(const TraceParams &p, uint32_t brick_dime
 
 hipError_t launch_build_cell_material(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
                                       uint64_t slot_hi, uint64_t mat_lo, uint64_t mat_hi, hipStream_t stream) {
-    if (!p.cell_material) return hipSuccess;
+    if (!p.cell_material && !p.cell_box) return hipSuccess;
     const uint32_t cells = p.status_cells;
     if (cells == 0u || (cell_lo >= cell_hi && slot_lo >= slot_hi && mat_lo >= mat_hi)) return hipSuccess;
     const uint64_t bits = (uint64_t)brick_dimension * brick_dimension * brick_dimension;
@@ -769,10 +801,10 @@ hipError_t launch_build_cell_material(const TraceParams &p, uint32_t brick_dimen
     uint8_t *out = const_cast<uint8_t *>(p.cell_material);
     if (brick_dimension == 8u)
         VRT_LAUNCH(vrt_build_cell_material<8>, grid, dim3(256), 0, stream, p.brick_status, p.brick_index, p.brick_occupancy, p.brick_start_index, p.material_index, out,
-                           cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
+                           const_cast<uint32_t *>(p.cell_box), cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
     else
         VRT_LAUNCH(vrt_build_cell_material<4>, grid, dim3(256), 0, stream, p.brick_status, p.brick_index, p.brick_occupancy, p.brick_start_index, p.material_index, out,
-                           cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
+                           const_cast<uint32_t *>(p.cell_box), cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
     return hipGetLastError();
 }
 

@@ -937,6 +937,38 @@ VRT_DI bool brick_walk(const TraceParams &p, const Ray &r, const RaySetup &s, fl
     return found;
 }
 
+// Brick rejection (TraceParams::cell_box): true when the voxel walk from `fposition` (comp:395-470, voxel units) can visit no voxel of
+// `box`, the box of the brick's solid voxels — the walk would then find nothing, and the grid-level walk goes on from its own side
+// distances whatever the inner walk did (comp:329-343), so skipping it changes nothing.  A slab test of the ray (t >= 0) against the box
+// DILATED BY ONE VOXEL on every side plus kRejectEps; empty interval: reject.  Why one voxel is enough: the inner walk's path comes
+// from three side-distance sequences, each built by repeated addition of |1/dir| (tests/test_skip_merge.py), so every crossing the
+// walk takes lies within a few ulps of the exact line's crossing of the same plane (at most 3B + 8 additions of a positive number);
+// only crossings of different axes that nearly coincide can be taken in the other order, and each axis's count of crossings is then
+// off by at most one.  A voxel the walk visits is thus at L-infinity distance <= 1 from a voxel the exact line through `fposition`
+// passes through — and if the line misses the dilated box, no visited voxel lies in the box itself.  tests/test_brick_reject.py
+// checks the claim on millions of binary32 walks (faces, edges, corners, axis-parallel, equal-component and grazing rays).
+// (inv_dir is safeInverse: 1e12 for a zero component.  v_min_f32 / v_max_f32 drop a NaN operand — 0 * inf of a denormal component —
+// which leaves the other bound of that axis; the test states it so.)  The transient values die here: the kernel stays at 72 VGPRs.
+constexpr float kRejectEps = 1.0f / 256.0f;
+template <int B>
+VRT_DI bool brick_reject(const f3 &fposition, const f3 &inv_dir, uint32_t box) {
+    constexpr uint32_t n = B == 8 ? 3u : 2u, m = (1u << n) - 1u;
+    auto slab = [&](uint32_t k, float f, float inv, float &near, float &far) {
+        const float lo = (float)((box >> (k * n)) & m) - (1.0f + kRejectEps);
+        const float hi = (float)((box >> ((k + 3u) * n)) & m) + (2.0f + kRejectEps); // (the far face of voxel hi is hi + 1)
+        const float t0 = (lo - f) * inv, t1 = (hi - f) * inv;
+        near = __builtin_fminf(t0, t1);
+        far = __builtin_fmaxf(t0, t1);
+    };
+    float nx, fx, ny, fy, nz, fz;
+    slab(0u, fposition.x, inv_dir.x, nx, fx);
+    slab(1u, fposition.y, inv_dir.y, ny, fy);
+    slab(2u, fposition.z, inv_dir.z, nz, fz);
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), 0.0f);
+    const float tf = __builtin_fminf(__builtin_fminf(fx, fy), fz);
+    return tf < tn;
+}
+
 // comp:378-471 on the hand-written voxel loop (voxel_walk_gfx950): same operations per lane as brick_walk.
 // The loop returns when some lane has left a solid voxel behind; the material test (comp:422-427) and the hit
 // record are done here, and lanes whose voxel is to be ignored walk on.  `axis_in`: the face through which the
@@ -947,9 +979,12 @@ VRT_DI bool brick_walk(const TraceParams &p, const Ray &r, const RaySetup &s, fl
 // (TraceParams::cell_occupancy, `cell` = the grid cell) when the context holds one, so that the request for them does not wait for
 // brick_index[cell] (comp:337) — which then only the material look-up of a solid voxel needs.  Such frames last as long as their slowest
 // wave, and that wave's time is its chain of brick entries: one dependent round trip less per entry.
-template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false>
+// REJECT (the one-sample kernel on 8^3 bricks, vrt::reads_cell_box): `box` is the cell's TraceParams::cell_box, and lanes whose walk
+// brick_reject proves empty leave before the occupancy word is requested; a wave whose lanes all leave skips the walk and the material
+// prefetch.  The walk of every other lane is the shader's.
+template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false>
 VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min, Hit &hit,
-                              int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr) {
+                              int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u) {
     const float brick_voxel_scale = 1.0f / (float)B; // spec const 5, Pipeline.zig:313
     const float voxel_scale = g_scale * brick_voxel_scale;
     const f3 fposition = p.scale_pow2 ? (ray_at(r, hit.t) - brick_min) * p.inv_voxel_scale : (ray_at(r, hit.t) - brick_min) / splat3(voxel_scale);
@@ -969,7 +1004,11 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup
     const uint32_t base = (by_cell ? cell : brick_index) * (uint32_t)(B * B * B);
     uint32_t bit_index = base + ((uint32_t)px + (uint32_t)B * ((uint32_t)pz + (uint32_t)B * (uint32_t)py));
     const uint32_t stride_x = (uint32_t)s.sx, stride_y = (uint32_t)(s.sy * (B * B)), stride_z = (uint32_t)(s.sz * B);
-    const bool more = more_init(px, py, pz, B) && (0.0f <= local_t_max); // comp:409 with t_value = 0
+    bool more = more_init(px, py, pz, B) && (0.0f <= local_t_max); // comp:409 with t_value = 0
+    if constexpr (REJECT) {
+        more = more && !brick_reject<B>(fposition, s.inv_dir, box);
+        if (__builtin_amdgcn_ballot_w64(more) == 0ull) return false;
+    }
 
     const uint8_t *const occupancy = by_cell ? p.cell_occupancy : p.brick_occupancy;
     const unsigned long long occ_addr = (unsigned long long)occupancy;
@@ -1302,7 +1341,8 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 // kernels measured 0.5 % slower with it and keep the compiler's placement)
 // VOXEL (ray queries, vrt_query_kernel.hip; the hand-written walks only): on a hit, voxel[0..2] = the voxel's position in the grid's voxel
 // coordinates of the walk (y as the shader counts it, cell * B + position in the brick) — integers from the walk, not derived from hit.point
-template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false>
+// REJECT: brick entries first tested against the cell's box of solid voxels (brick_walk_gfx950<..., REJECT>; vrt::reads_cell_box)
+template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false>
 VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr) {
     static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
                   "voxel coordinates come from the hand-written walk without batching");
@@ -1438,12 +1478,15 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         global_t_value = t_cross * g_scale + s.grid_t_min + 0.01f * g_scale;                     // comp:347 (deferred) + comp:332
         hit.t = global_t_value;
         const uint32_t brick_index = p.brick_index[cell]; // comp:337
+        // (keyed by cell: requested beside brick_index, not behind it; a context without the array never rejects)
+        [[maybe_unused]] uint32_t box = 0u;
+        if constexpr (REJECT) box = p.cell_box ? p.cell_box[cell] : vrt::full_cell_box(B);
         VRT_COUNT(bricks_entered);
         VRT_COUNT_WAVE(wave_brick_walks);
         bool found;
         if constexpr ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT) {
             [[maybe_unused]] uint32_t voxel_in_brick = 0u;
-            found = brick_walk_gfx950<B, true, BATCH, VOXEL>(p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick);
+            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT>(p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
             if constexpr (VOXEL) {
                 if (found) { // voxel index x + B (z + B y) in the brick (comp:412)
                     voxel[0] = cx * B + (int)(voxel_in_brick % (uint32_t)B);
@@ -1661,14 +1704,14 @@ VRT_DI bool scatter_dielectric(float ir, const Ray &r_in, const Hit &hit, Ray &s
 // comp:203-265 when push_constant.max_bounce <= 1 (Camera.Config.max_bounce = 0: "only primary
 // ray", Camera.zig:74).  The bounce loop then runs at most once, so the scatter functions — whose only
 // products are the next ray and the continue flag — have no observable effect and are not evaluated.
-template <int B, bool COUNT, int MODE, bool SCALAR_ENTRY = false>
+template <int B, bool COUNT, int MODE, bool SCALAR_ENTRY = false, bool REJECT = false>
 VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const uint32_t *lds_filter, const Ray &ray, Cnt<COUNT> &c) {
     const bool sun_enabled = pc.sun.enabled > 0;
     const f3 sun_color = mk3(pc.sun.color[0], pc.sun.color[1], pc.sun.color[2]);
     f3 color = mk3(0, 0, 0);
     int loop_count = 0;
     Hit hit;
-    if (pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY>(p, lds_filter, ray, hit, c)) {
+    if (pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT>(p, lds_filter, ray, hit, c)) {
         // (the material record is read AFTER the shadow ray: only its index stays live across the second walk — three registers
         // fewer at the kernel's point of highest pressure; the record sits in the scalar / L1 cache)
         const uint32_t material = hit.index;
@@ -1679,7 +1722,7 @@ VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const 
                                           pc.sun.radius);
             const Ray shadow_ray = create_ray(hit.point, (sun_position + rv) - hit.point);
             Hit shadow_hit;
-            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY>(p, lds_filter, shadow_ray, shadow_hit, c);
+            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT>(p, lds_filter, shadow_ray, shadow_hit, c);
         }
         const vrt_material *m = p.materials + material;
         const uint32_t mtype = m->type;
@@ -1900,7 +1943,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
             const float u = (x0 + 0.0f) / (float)(pc.cam.image_width - 1u);
             const float v = (y0 + 0.0f) / (float)(pc.cam.image_height - 1u);
             const f3 ray_dir = fma3(horizontal, splat3(u), llc) + fma3(splat3(v), vertical, -origin);
-            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE>(p, pc, lds_filter, create_ray(origin, ray_dir), c);
+            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE, false, vrt::reads_cell_box(0, B, COUNT, MODE, SHADE)>(p, pc, lds_filter, create_ray(origin, ray_dir), c);
         } else {
             const int sample_begin = dual ? (int)(lane >= pixels ? 1u : 0u) : 0, sample_end = dual ? sample_begin + 1 : spp;
             for (int sample_i = sample_begin; sample_i < sample_end; sample_i++) {
