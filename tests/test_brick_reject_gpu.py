@@ -1,7 +1,8 @@
 """The box of a cell's solid voxels (TraceParams::cell_box) follows every kind of upload: the one-sample kernel on 8^3 bricks rejects
 brick entries whose walk cannot reach that box (brick_reject), so a stale box would drop hits.  A small brick of a few voxels is looked
-at, then voxels are added through delta uploads — at the far corner of the same brick (occupancy bytes of its slot), then in a brick of
-a cell that was empty (status bit and brick index) — and every frame must equal the oracle's whole frame."""
+at, then voxels are added through delta uploads — at the far corner of the same brick (occupancy bytes of its slot; insert() rewrites
+the cell's status word too, so the written cell range covers the edit as well), then in a brick of a cell that was empty (status bit
+and brick index) — and every frame must equal the oracle's whole frame.  Uploads of the occupancy bytes alone: tests/test_scene_edits_gpu.py."""
 import numpy as np
 import pytest
 

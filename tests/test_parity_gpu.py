@@ -1032,8 +1032,10 @@ def test_pool_kernel_takes_the_material_of_one_material_bricks_from_a_byte_per_c
     byte of the 2 GiB material_index): a derived byte per cell names the material ALL solid voxels of the cell's brick share, 0xFF where
     they do not (TraceParams::cell_material).  A scene with both kinds — spheres of one material each, plus 6 000 stray voxels of random
     materials that make the bricks they fall into mixed: frames with and without the structure (VRT_TUNE_NO_CELL_MATERIAL) and the
-    oracle's are the same bytes.  Then the host re-inserts 500 solid voxels with ANOTHER material — only material_index entries change,
-    uniform bricks become mixed — and the delta upload must refresh exactly those bytes: the next frame is the oracle's of the edited grid."""
+    oracle's are the same bytes.  Then the host re-inserts 500 solid voxels with ANOTHER material — only material_index entries change
+    in content, uniform bricks become mixed, though insert() uploads the cells' status words and occupancy bytes too, so the written cell
+    range covers them — and the next frame must be the oracle's of the edited grid.  Uploads of material_index alone:
+    tests/test_scene_edits_gpu.py."""
     w = W.Workload("t", 208, 112, 256, 8, 2, 2, True, 5.0, "sparse", 0.08, 30000)
     rng = np.random.default_rng(11)
     stray = rng.integers(0, 256, (6000, 3))
