@@ -485,9 +485,8 @@ typedef struct vrt_ray_hit {        /* 48 bytes */
 #define VRT_RAY_RAW_DIRECTION (1u << 0)
 
 /* rays and hits in host memory; blocks until the hits are written.  VRT_E_INVALID_ARG: a NULL pointer with n > 0 or a
- * ray with unknown flag bits.  VRT_E_STATE: no grid state uploaded yet, a context of the multi-GPU pipeline, or the
- * query code object (vrt_query.hsaco next to the library) missing — vrt_last_error names its path.  n == 0: VRT_OK.
- * A failed query leaves the context usable for frames. */
+ * ray with unknown flag bits.  VRT_E_STATE: no grid state uploaded yet, or a context of the multi-GPU pipeline.
+ * n == 0: VRT_OK.  A failed query leaves the context usable for frames. */
 int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits);
 /* rays and hits in device memory; ordered on the context's stream after every upload so far; asynchronous (vrt_wait).
  * The flags are not read on the host here: a ray with unknown flag bits gets a miss record. */

@@ -16,6 +16,63 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zig_vulkan_amd", "libvrt_hip.so")
 
 
+# Every kernel of the product binary, by symbol: the 28 traversal kernels, 19 others (builders of the derived structures, schedule,
+# present, assembly, self-test) and the two ray-query kernels.  A kernel that appears, goes or returns (a loser of an A/B) fails the test.
+PRODUCT_KERNELS = frozenset([
+    "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb0ELb0ELb0ELi0EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb0ELb0ELb0ELi1EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb0ELb0ELb0ELi2EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi8ELi5ELb0ELb0ELb0ELb0ELi0EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi8ELi5ELb0ELb0ELb0ELb0ELi1EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi8ELi5ELb0ELb0ELb0ELb0ELi2EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_path_kernelILi8ELi5ELb0ELb1ELb0ELb0ELi0EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_pool_kernelILi4ELi6ELi64ELi0EEEvNS_11TraceParamsE",
+    "_ZN3vrt15vrt_pool_kernelILi8ELi6ELi60ELi2EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi4ELi5ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi4ELi7ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi4ELi7ELi2ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi4ELi8ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi7ELi7ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb0ELi7ELi7ELi2ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb1ELi4ELi4ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb1ELi4ELi4ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi4ELb1ELi4ELi4ELi2ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi4ELi5ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi4ELi7ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi4ELi7ELi2ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi4ELi8ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi7ELi7ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb0ELi7ELi7ELi2ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb1ELi4ELi4ELi0ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb1ELi4ELi4ELi1ELi256EEEvNS_11TraceParamsE",
+    "_ZN3vrt16vrt_trace_kernelILi8ELb1ELi4ELi4ELi2ELi256EEEvNS_11TraceParamsE",
+    # builders, schedule, present, assembly, self-test
+    "_Z15vrt_spin_kernely",
+    "_ZN3vrt18vrt_denoise_kernelILb0EEEvPK15HIP_vector_typeIhLj4EEiiNS_13DenoiseParamsEiiPjPS1_IfLj4EE",
+    "_ZN3vrt18vrt_denoise_kernelILb1EEEvPK15HIP_vector_typeIhLj4EEiiNS_13DenoiseParamsEiiPjPS1_IfLj4EE",
+    "_ZN3vrt19vrt_assemble_kernelI15HIP_vector_typeIfLj4EEEEvPKT_PS3_jjjjjNS_13TileOwnershipEj",
+    "_ZN3vrt19vrt_assemble_kernelIjEEvPKT_PS1_jjjjjNS_13TileOwnershipEj",
+    "_ZN3vrt19vrt_schedule_kernelEPKjPjS1_S2_jjjj",
+    "_ZN3vrt21vrt_build_cell_boundsEPKjPijjjj",
+    "_ZN3vrt22vrt_build_status_bytesEPKjPhjj",
+    "_ZN3vrt23vrt_assemble_rgb_kernelEPKhPjjjjjjNS_13TileOwnershipEj",
+    "_ZN3vrt23vrt_build_cell_materialILi4EEEvPKjS2_PKhS2_S4_PhPjjjmmmmmmmm",
+    "_ZN3vrt23vrt_build_cell_materialILi8EEEvPKjS2_PKhS2_S4_PhPjjjmmmmmmmm",
+    "_ZN3vrt23vrt_check_start_is_slotEPKjPjmj",
+    "_ZN3vrt23vrt_denoise_tile_kernelILi0EEEvPK15HIP_vector_typeIhLj4EEiiNS_13DenoiseParamsEiiPjPS1_IfLj4EE",
+    "_ZN3vrt23vrt_denoise_tile_kernelILi20EEEvPK15HIP_vector_typeIhLj4EEiiNS_13DenoiseParamsEiiPjPS1_IfLj4EE",
+    "_ZN3vrt23vrt_pool_resolve_kernelENS_11TraceParamsE",
+    "_ZN3vrt24vrt_assemble_rgb4_kernelEPKhPjjjjjjNS_13TileOwnershipEj",
+    "_ZN3vrt24vrt_build_cell_occupancyEPKjS1_PK15HIP_vector_typeIjLj2EEPS3_mmjmmmmm",
+    "_ZN3vrt25vrt_check_materials_plainEPK12vrt_materialPjj",
+    "_ZN3vrt27vrt_build_status_halfblocksEPKjPjjjj",
+    # ray queries (vrt_query.hip)
+    "vrt_ray_query_b4",
+    "vrt_ray_query_b8",
+])
+
+
 def _kernels():
     if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
         pytest.skip("llvm-objdump / llvm-readelf not found under /opt/rocm/lib/llvm/bin")
@@ -36,15 +93,16 @@ def _kernels():
     return out
 
 
-def test_the_product_binary_holds_only_shipped_kernels():
+def test_the_product_binary_holds_exactly_the_shipped_kernels():
     """about 40 kernels in the product code objects (round 2 shipped 175, most of them losers of an A/B);
     the variants that lost live in the development build (make dev).  Round 4: 27 traversal kernels + 16 small ones (builders of
     the derived structures, schedule, un-swizzle, the two present kernels, vrt_pool_resolve_kernel, vrt_check_materials_plain).  Round 5:
     + vrt_pool_kernel for 4^3 bricks, the two builders of the byte-per-cell material (vrt_build_cell_material<4>, <8>) and the present pass's
     staged kernel as its own (vrt_denoise_tile_kernel<20>, <0>; vrt_denoise_kernel<NEAR> keeps the taps from global memory).  Round 6:
-    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel)."""
+    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel).  The ray queries add vrt_ray_query_b4 / _b8;
+    vrt_build_status_blocks, whose words only development variants read, is in the development build alone."""
     ks = _kernels()
-    assert len(ks) <= 48, sorted(ks)
+    assert set(ks) == PRODUCT_KERNELS, (sorted(set(ks) - PRODUCT_KERNELS), sorted(PRODUCT_KERNELS - set(ks)))
     traversal = [n for n in ks if "vrt_trace_kernel" in n or "vrt_path_kernel" in n or "vrt_pool_kernel" in n]
     assert len(traversal) == 28, sorted(traversal)
 
@@ -136,3 +194,12 @@ def test_path_kernel_holds_5_waves():
     assert len(ks) == 8
     for name, k in ks.items():
         assert k["vgpr"] <= 96 and k["scratch"] <= 128, (name, k)
+
+
+def test_ray_query_kernels_hold_5_waves_without_scratch():
+    """vrt_ray_query_b4 / _b8 (five waves per SIMD): at most 96 VGPRs, no scratch, no static LDS, and no scratch instruction in their code."""
+    ks = {n: k for n, k in _kernels().items() if n.startswith("vrt_ray_query_")}
+    assert sorted(ks) == ["vrt_ray_query_b4", "vrt_ray_query_b8"], ks
+    for name, k in ks.items():
+        assert k["vgpr"] <= 96 and k["scratch"] == 0 and k["lds"] == 0, (name, k)
+        assert _scratch_instructions(name) == 0, name

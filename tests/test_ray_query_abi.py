@@ -1,9 +1,8 @@
 """The ray-query ABI (vrt_cast_rays, vrt_cast_rays_device, vrt_camera_pixel_ray) without a GPU: the two structs in C, ctypes and
-Zig, the flag, the exported and bound functions, the query code object's kernels and their resources, and the camera-ray helper."""
+Zig, the flag, the exported and bound functions, and the camera-ray helper.  (The kernels' resources: tests/test_kernel_resources.py.)"""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 import tempfile
@@ -92,31 +91,6 @@ def test_functions_are_exported_bound_and_in_the_zig_binding():
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert f"pub extern fn {name}(" in zig, name
     assert subprocess.call([sys.executable, os.path.join(ROOT, "tools", "gen_zig_binding.py"), "--check"]) == 0
-
-
-def _code_object_kernels(path):
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("llvm-readelf not found under /opt/rocm/lib/llvm/bin")
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", path], check=True, capture_output=True, text=True).stdout
-    out = {}
-    for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size: (\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-        lds, name, scratch, vgpr = m.groups()
-        out[name] = dict(lds=int(lds), scratch=int(scratch), vgpr=int(vgpr))
-    return out
-
-
-def test_query_code_object_holds_the_two_kernels_within_budget():
-    """Five waves per SIMD: at most 96 VGPRs, no scratch, no static LDS.  (The product library's kernel budget is its own.)"""
-    assert os.path.exists(L.QUERY_CODE_OBJECT_PATH), "vrt_query.hsaco is built by `make -C zig_vulkan_amd/csrc` next to the library"
-    ks = _code_object_kernels(L.QUERY_CODE_OBJECT_PATH)
-    assert sorted(ks) == ["vrt_ray_query_b4", "vrt_ray_query_b8"], ks
-    for name, k in ks.items():
-        assert k["vgpr"] <= 96 and k["scratch"] == 0 and k["lds"] == 0, (name, k)
-    with tempfile.TemporaryDirectory() as d:   # ... and no scratch instruction anywhere in their code
-        shutil.copy(L.QUERY_CODE_OBJECT_PATH, os.path.join(d, "q.hsaco"))
-        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", "q.hsaco"], cwd=d, check=True, capture_output=True,
-                             text=True).stdout
-    assert "vrt_ray_query_b4" in dis and "scratch_" not in dis
 
 
 def test_camera_pixel_ray_checks_its_arguments():

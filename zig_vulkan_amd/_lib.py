@@ -296,8 +296,6 @@ lib = load_library(LIB_PATH)
 # test-infrastructure twins of the product library (zig_vulkan_amd/csrc/Makefile); absent unless built
 FUSED_LIB_PATH = os.path.join(_HERE, "libvrt_hip_fused.so")    # fma fused, dot as an fma chain (make fused): how far fusing moves the frames
 DEV_LIB_PATH = os.path.join(_HERE, "libvrt_hip_dev.so")        # + the variants that lost their A/B measurement (make dev)
-# the ray-query kernels (vrt_cast_rays) of the product library: a code object of their own, loaded by the library from its own directory
-QUERY_CODE_OBJECT_PATH = os.path.join(_HERE, "vrt_query.hsaco")
 
 
 def rccl_library_path() -> str:

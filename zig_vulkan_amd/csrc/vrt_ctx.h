@@ -3,7 +3,7 @@
 //   vrt_frame.hip  one frame: refresh of the derived structures, kernel choice, tile schedule, launch, timing
 //   vrt_dist.hip   the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip   the present / denoise pass
-//   vrt_query.hip  batched ray queries (its kernels: vrt_query_kernel.hip, in a code object of their own)
+//   vrt_query.hip  batched ray queries (their kernels and host side)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
 #pragma once
@@ -208,9 +208,7 @@ struct vrt_ctx {
     vrt::TileOwnership own{};        // weighted tile ownership (period 0: tile t belongs to rank t % shard_count)
     bool status_dirty = true;        // brick_status changed since the derived copy was built
     bool grid_uploaded = false;      // binding 1 has been uploaded (ray queries need the grid's geometry)
-    // ray queries (vrt_query.hip): the code object, loaded on the first query and unloaded by vrt_destroy; the host path's device buffers
-    hipModule_t query_module = nullptr;
-    hipFunction_t query_fn = nullptr;
+    // ray queries (vrt_query.hip): the host path's device buffers
     vrt_ray_query *d_query_rays = nullptr;
     vrt_ray_hit *d_query_hits = nullptr;
     uint64_t query_capacity = 0;     // rays the two buffers hold
@@ -334,9 +332,6 @@ bool lane_samples_ready(vrt_ctx *ctx, vrt::PersistentLane &lane, uint64_t units,
 int refresh_derived(vrt_ctx *ctx);
 uint64_t sample_units(const vrt_ctx *ctx, int samples_per_pixel); // units of a frame of this context (0: not a frame of units)
 void lane_into_params(const vrt::PersistentLane &lane, bool with_samples, vrt::TraceParams &p);
-
-// ---- vrt_query.hip ----
-void query_release(vrt_ctx *ctx); // unloads the query code object (vrt_destroy; the memory is Resources')
 
 // ---- vrt_dist.hip ----
 int dist_flush(vrt_ctx *ctx);

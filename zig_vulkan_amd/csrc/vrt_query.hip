@@ -1,77 +1,106 @@
-// vrt_query.hip — batched ray queries behind the C ABI (vrt_cast_rays, vrt_cast_rays_device) and the camera ray of a pixel
-// (vrt_camera_pixel_ray).  The kernels live in a code object of their own next to the library (vrt_query_kernel.hip ->
-// vrt_query.hsaco; each build flavour its own), loaded on a context's first query with hipModuleLoad on the context's device and
-// unloaded by vrt_destroy.  A query sees the scene as the next frame would: the structures derived from the scene buffers are
-// refreshed through the frames' own path (refresh_derived) on the primary stream, after every upload so far.
+// vrt_query.hip — batched ray queries behind the C ABI (vrt_cast_rays, vrt_cast_rays_device): their kernels vrt_ray_query_b4 / _b8 and
+// their host side; and the camera ray of a pixel (vrt_camera_pixel_ray).  A query sees the scene as the next frame would: the structures
+// derived from the scene buffers are refreshed through the frames' own path (refresh_derived) on the primary stream, after every upload
+// so far.  The kernels are compiled with the product's arithmetic flags, so that a query is bit-equal to the shader's GridHit
+// (vrt_math.h's contract).
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <unistd.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
 #include "vrt_ctx.h"
-#include "vrt_query.h"
+#include "vrt_trace_kernels.h" // (after vrt_ctx.h: behind its <chrono>, the host pass rejects the walk's gfx950 inline assembly)
 
-#ifndef VRT_QUERY_CODE_OBJECT
-#error "VRT_QUERY_CODE_OBJECT (the file name of this flavour's query code object) comes from the Makefile"
-#endif
+namespace vrt {
+
+static_assert(sizeof(vrt_ray_query) == 32, "vrt_ray_query is two dwordx4");
+static_assert(sizeof(vrt_ray_hit) == 48, "vrt_ray_hit is three dwordx4");
+
+// The one kernel argument of vrt_ray_query_b4 / _b8: the scene as the frames see it, and one launch's share of the batch.
+struct QueryArgs {
+    TraceParams p;
+    const vrt_ray_query *rays; // (16-byte aligned)
+    vrt_ray_hit *hits;         // (16-byte aligned)
+    uint64_t n;                // rays of this launch
+};
+
+constexpr uint32_t kQueryBlock = 256u;             // threads per workgroup: four waves, one ray per lane
+constexpr uint64_t kQueryLaunchRays = 1ull << 24;  // rays per launch (65 536 workgroups); larger batches are launched in pieces
+constexpr uint64_t kQueryHostPieceRays = 1ull << 20; // vrt_cast_rays: rays per round trip through the context's device buffers
+
+VRT_DI float as_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
+VRT_DI bool finite3(f3 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
+
+// The frames' choice of status copy: the byte per cell where the context keeps one (grids up to 2^18 cells), the shader's words
+// otherwise.  Both walks give the same hits; the branch is uniform over the launch.
+template <int B>
+VRT_DI bool query_walk(const TraceParams &p, const Ray &r, Hit &hit, int *voxel) {
+    Cnt<false> c;
+    if (p.status_bytes) return grid_hit<B, false, kStatusBytes, false, false, true>(p, nullptr, r, hit, c, voxel);
+    return grid_hit<B, false, kStatusLinearAlways, false, false, true>(p, nullptr, r, hit, c, voxel);
+}
+
+// One GridHit of the frames' own walk per ray, one ray per lane.
+template <int B>
+VRT_DI void ray_query(const QueryArgs &a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= a.n) return;
+    // the query as two dwordx4: a wave reads 2 KiB contiguous
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(a.rays) + 2u * i;
+    const u32x4 q0 = src[0], q1 = src[1];
+    const f3 origin = mk3(as_f32(q0.x), as_f32(q0.y), as_f32(q0.z));
+    const float max_t = as_f32(q0.w);
+    const f3 direction = mk3(as_f32(q1.x), as_f32(q1.y), as_f32(q1.z));
+    const uint32_t flags = q1.w;
+    // screened first: such rays are misses and are never walked (NaN max_t fails `>= 0`)
+    const bool walk = finite3(origin) && finite3(direction) && !(direction.x == 0.0f && direction.y == 0.0f && direction.z == 0.0f) &&
+                      max_t >= 0.0f && (flags & ~VRT_RAY_RAW_DIRECTION) == 0u;
+    Hit hit;
+    int voxel[3] = {0, 0, 0};
+    bool found = false;
+    if (walk) {
+        // CreateRay (comp:180-184), or the ray as given
+        const Ray r = (flags & VRT_RAY_RAW_DIRECTION) ? Ray{origin, direction, 1.0f, MAT_NONE} : create_ray(origin, direction);
+        found = query_walk<B>(a.p, r, hit, voxel) && hit.t <= max_t; // max_t filters the first hit
+    }
+    u32x4 h0 = {0u, 0u, 0u, 0u}, h1 = h0, h2 = h0;
+    if (found) {
+        h0 = u32x4{__builtin_bit_cast(uint32_t, hit.point.x), __builtin_bit_cast(uint32_t, hit.point.y), __builtin_bit_cast(uint32_t, hit.point.z),
+                   __builtin_bit_cast(uint32_t, hit.t)};
+        h1 = u32x4{__builtin_bit_cast(uint32_t, hit.normal.x), __builtin_bit_cast(uint32_t, hit.normal.y), __builtin_bit_cast(uint32_t, hit.normal.z),
+                   hit.index};
+        // y as vrt_grid_insert counts it: insert flips it (Grid.zig:135)
+        h2 = u32x4{(uint32_t)voxel[0], a.p.grid.voxel_dim_y - 1u - (uint32_t)voxel[1], (uint32_t)voxel[2], 1u};
+    }
+    u32x4 *dst = reinterpret_cast<u32x4 *>(a.hits) + 3u * i;
+    dst[0] = h0;
+    dst[1] = h1;
+    dst[2] = h2;
+}
+
+} // namespace vrt
+
+// five waves per SIMD (<= 96 VGPRs)
+extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, 5) void vrt_ray_query_b4(const vrt::QueryArgs a) { vrt::ray_query<4>(a); }
+extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, 5) void vrt_ray_query_b8(const vrt::QueryArgs a) { vrt::ray_query<8>(a); }
 
 using namespace vrt_impl;
 
-namespace vrt_impl {
-void query_release(vrt_ctx *ctx) {
-    if (!ctx->query_module) return;
-    (void)hipModuleUnload(ctx->query_module);
-    ctx->query_module = nullptr;
-    ctx->query_fn = nullptr;
-}
-} // namespace vrt_impl
-
 namespace {
 
-// the query code object of this library's flavour: the file VRT_QUERY_CODE_OBJECT in the library's own directory
-std::string code_object_path() {
-    Dl_info info{};
-    std::string dir = ".";
-    if (dladdr(reinterpret_cast<void *>(&vrt_impl::query_release), &info) && info.dli_fname) {
-        const std::string lib = info.dli_fname;
-        const size_t slash = lib.rfind('/');
-        if (slash != std::string::npos) dir = lib.substr(0, slash);
-    }
-    return dir + "/" VRT_QUERY_CODE_OBJECT;
+// vrt_ray_query_b4 / _b8 over the a.n rays of one launch
+hipError_t launch_ray_query(const vrt::QueryArgs &a, int brick_dimension, hipStream_t stream) {
+    const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
+    if (brick_dimension == 8) VRT_LAUNCH(vrt_ray_query_b8, groups, dim3(vrt::kQueryBlock), 0, stream, a);
+    else VRT_LAUNCH(vrt_ray_query_b4, groups, dim3(vrt::kQueryBlock), 0, stream, a);
+    return hipGetLastError();
 }
 
-int load_query_kernel(vrt_ctx *ctx) {
-    if (ctx->query_fn) return VRT_OK;
-    const std::string path = code_object_path();
-    if (access(path.c_str(), R_OK) != 0) return fail(ctx, VRT_E_STATE, "ray-query code object missing: " + path);
-    hipModule_t m = nullptr;
-    const hipError_t e = hipModuleLoad(&m, path.c_str());
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, VRT_E_STATE, "ray-query code object " + path + " did not load: " + hipGetErrorString(e));
-    }
-    const char *name = ctx->cfg.brick_dimension == 8 ? "vrt_ray_query_b8" : "vrt_ray_query_b4";
-    hipFunction_t f = nullptr;
-    const hipError_t ef = hipModuleGetFunction(&f, m, name);
-    if (ef != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipModuleUnload(m);
-        return fail(ctx, VRT_E_STATE, std::string("ray-query code object ") + path + " lacks " + name + ": " + hipGetErrorString(ef));
-    }
-    ctx->query_module = m;
-    ctx->query_fn = f;
-    return VRT_OK;
-}
-
-// What both entry points check and do before their first launch: the scene is there, the code object is loaded, and the derived
-// structures are current (on the primary stream, behind the uploads).
+// What both entry points check and do before their first launch: the scene is there, and the derived structures are current (on the
+// primary stream, behind the uploads).
 int query_begin(vrt_ctx *ctx) {
     if (ctx->dist) return fail(ctx, VRT_E_STATE, "ray queries are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
-    const int rc = load_query_kernel(ctx);
-    if (rc != VRT_OK) return rc;
     return refresh_derived(ctx);
 }
 
@@ -83,11 +112,7 @@ int launch_queries(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_
         a.rays = rays + first;
         a.hits = hits + first;
         a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchRays);
-        size_t bytes = sizeof a;
-        void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-        const uint32_t groups = (uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock);
-        (void)hipGetLastError(); // (the thread's stale error is not this launch's: VRT_LAUNCH)
-        VRT_HIP(ctx, hipModuleLaunchKernel(ctx->query_fn, groups, 1, 1, vrt::kQueryBlock, 1, 1, 0, ctx->stream, nullptr, config));
+        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream));
     }
     return VRT_OK;
 }

@@ -12,6 +12,7 @@ namespace vrt {
 // out[0 .. nblocks)            one uint2 per 4x4x4 block of cells
 // out[nblocks ..) as u32 words  filter: bit b set iff block b has any occupied cell
 // One thread per block; the filter words are produced by a wave ballot (32 blocks per word).
+#ifdef VRT_DEV_VARIANTS // (only development variants read the words: the Blocked status modes, vrt_path_kernel<FILTER> and DIL 3)
 __global__ __launch_bounds__(256) void vrt_build_status_blocks(const uint32_t *__restrict__ status, uint2 *__restrict__ out, uint32_t dim_x,
                                                                uint32_t dim_y, uint32_t dim_z, uint32_t nbx, uint32_t nby, uint32_t nbz) {
     const uint32_t nblocks = nbx * nby * nbz;
@@ -41,6 +42,7 @@ __global__ __launch_bounds__(256) void vrt_build_status_blocks(const uint32_t *_
     if (lane == 0 && base_word < nwords) filter[base_word] = (uint32_t)(nonempty & 0xFFFFFFFFull);
     if (lane == 32 && base_word + 1u < nwords) filter[base_word + 1u] = (uint32_t)(nonempty >> 32);
 }
+#endif
 
 // The status bits ordered by half-blocks of 4 x 4 x 2 cells (TraceParams::status_halfblocks, grid_walk_park_halfblocks_gfx950):
 // word (x>>2) + (dim_x/4) * ((z>>2) + (dim_z/4) * (y>>1)), bit (x&3) | (z&3) << 2 | (y&1) << 4.  One thread per word.
@@ -846,10 +848,15 @@ hipError_t launch_build_status_bytes(const TraceParams &p, hipStream_t stream) {
 
 hipError_t launch_build_status_blocks(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
     if (!p.status_blocks) return hipSuccess;
+#ifndef VRT_DEV_VARIANTS
+    (void)dim_x, (void)dim_y, (void)dim_z, (void)stream;
+    return hipErrorNotSupported; // (no kernel of the product build reads the words: vrt_create never allocates them there)
+#else
     const uint32_t nblocks = p.nbx * p.nby * p.nbz;
     VRT_LAUNCH(vrt_build_status_blocks, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream, p.brick_status,
                        const_cast<uint2 *>(p.status_blocks), dim_x, dim_y, dim_z, p.nbx, p.nby, p.nbz);
     return hipGetLastError();
+#endif
 }
 
 hipError_t launch_assemble_rgb(const void *gathered, void *frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_count,

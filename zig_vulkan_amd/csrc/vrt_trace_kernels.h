@@ -1,5 +1,6 @@
 // vrt_trace_kernels.h — the traversal kernels (device code, templates).  Included by the instantiation units
-// vrt_inst_*.hip (one per brick dimension / kernel family, so that they compile in parallel) — nothing else includes it.
+// vrt_inst_*.hip (one per brick dimension / kernel family, so that they compile in parallel) and by vrt_query.hip (the ray queries'
+// GridHit) — nothing else includes it.
 #pragma once
 //
 // Brickmap traversal for gfx950 (MI355X), wave64.  Replaces the dispatch of assets/shaders/brick_raytracer.comp
@@ -973,7 +974,7 @@ VRT_DI bool brick_reject(const f3 &fposition, const f3 &inv_dir, uint32_t box) {
 // The loop returns when some lane has left a solid voxel behind; the material test (comp:422-427) and the hit
 // record are done here, and lanes whose voxel is to be ignored walk on.  `axis_in`: the face through which the
 // brick was entered (the brick-level walk's crossed axis), used when the very first voxel is the hit.
-// VOXEL (ray queries, vrt_query_kernel.hip): the index in its brick of the voxel hit, x + B (z + B y) (comp:412), is also left in
+// VOXEL (ray queries, vrt_query.hip): the index in its brick of the voxel hit, x + B (z + B y) (comp:412), is also left in
 // *hit_voxel; the frames' kernels compile without it.
 // BY_CELL (round 4, frames with bounces on scenes that stay in the caches): the brick's bits are read from the by-cell copy
 // (TraceParams::cell_occupancy, `cell` = the grid cell) when the context holds one, so that the request for them does not wait for
@@ -1339,7 +1340,7 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 
 // SCALAR_ENTRY: the grid-entry offset 0.0001 * scale (comp:287) formed where it is used (the several-samples kernel; the one-sample
 // kernels measured 0.5 % slower with it and keep the compiler's placement)
-// VOXEL (ray queries, vrt_query_kernel.hip; the hand-written walks only): on a hit, voxel[0..2] = the voxel's position in the grid's voxel
+// VOXEL (ray queries, vrt_query.hip; the hand-written walks only): on a hit, voxel[0..2] = the voxel's position in the grid's voxel
 // coordinates of the walk (y as the shader counts it, cell * B + position in the brick) — integers from the walk, not derived from hit.point
 // REJECT: brick entries first tested against the cell's box of solid voxels (brick_walk_gfx950<..., REJECT>; vrt::reads_cell_box)
 template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false>
