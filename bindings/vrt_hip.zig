@@ -329,6 +329,10 @@ pub extern fn vrt_upload_grid(ctx: ?*Ctx, g: ?*Grid) c_int;
 pub extern fn vrt_update_grid_delta(ctx: ?*Ctx, g: ?*Grid) c_int;
 pub extern fn vrt_cast_rays(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
 pub extern fn vrt_cast_rays_device(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
+pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
+pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
+pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
+pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_camera_pixel_ray(cam: [*c]const CameraDevice, px: u32, py: u32, origin: *[3]f32, direction: *[3]f32) c_int;
 pub extern fn vrt_camera_init(vertical_fov_deg: f32, image_width: u32, image_height: u32, cfg: [*c]const CameraConfig, out: [*c]CameraDevice) c_int;
 pub extern fn vrt_camera_set_forward(cam: [*c]CameraDevice, vertical_fov_deg: f32, viewport_height: f32, forward: *const [3]f32) c_int;

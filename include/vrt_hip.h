@@ -491,6 +491,41 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_h
 /* rays and hits in device memory; ordered on the context's stream after every upload so far; asynchronous (vrt_wait).
  * The flags are not read on the host here: a ray with unknown flag bits gets a miss record. */
 int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits);
+/* ---- Batched voxel inserts into the uploaded scene --------------------------------------------------------------
+ * BrickGrid.insert (Grid.zig:129-194) for n voxels at once, on the GPU, on the scene buffers the context holds: after
+ * vrt_insert_voxels(ctx, xyz, m, n) on a context whose bindings 2-6 equal a vrt_grid's arrays, bindings 2-6 equal that grid's
+ * arrays after vrt_grid_insert_many(g, xyz, m, n), byte for byte.  xyz: x, y, z per voxel, y as vrt_grid_insert takes it
+ * (flipped, Grid.zig:135).  Applied in array order: a cell that is not loaded gets the next brick, in the order of its first
+ * voxel in the batch, with the next material entry as its start; a voxel written twice keeps the last write's material.
+ * Bindings 0 and 1 are never written.  (Here binding k is buffer id k of vrt_buffer_id: binding 5 = VRT_BUF_BRICK_START_INDEX,
+ * binding 6 = VRT_BUF_MATERIAL_INDEX.)
+ *
+ * ALLOCATION STATE comes from binding 5 itself, so it also holds for a host that uploads its own arrays (vrt_upload): binding 5
+ * is allocation-shaped when entries [0, A) are set with type bit 0 and entries [A, brick_alloc) are 0xFFFFFFFF.  Then A bricks
+ * are allocated and the next material entry is max(start over [0, A)) + B^3 (0 when A = 0); new brick r of a batch gets index
+ * A + r and start cursor + r * B^3.  It is computed on the device at the first insert after any write to binding 5 and kept
+ * current by the inserts.
+ *
+ * ERRORS.  A failed call changes no byte of the scene (unlike the host loop, which stops partway).  VRT_E_OUT_OF_RANGE: a
+ * voxel outside the grid, or n >= 2^31.  VRT_E_OOM: the batch needs more bricks than brick_alloc leaves, or material entries
+ * beyond brick_alloc * B^3.  VRT_E_INVALID_ARG: a NULL pointer with n > 0.  VRT_E_STATE: no grid state uploaded, binding 5 not
+ * allocation-shaped (or a loaded cell naming a brick >= A), a context of the multi-GPU pipeline, or the edit code object
+ * vrt_edit.hsaco missing next to the library (the message names its path).  n == 0: VRT_OK, the device is not touched.
+ *
+ * ORDERING.  A scene write on the context's stream, like vrt_upload_device: frames queued before the call see the old scene,
+ * frames and queries after it the new one.  Both calls return once the batch's status is known (one small read-back); the
+ * caller's buffers are then no longer read.  The derived structures are refreshed for the written ranges before the next frame. */
+/* xyz and materials in host memory (staged through the context's pinned slots) */
+int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n);
+/* xyz and materials in device memory, ordered after every earlier write on the context's stream */
+int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n);
+/* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
+ * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
+int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);
+/* out[0] = allocated bricks A, out[1] = next material entry (MaterialAllocator's cursor), as the next insert continues them.
+ * VRT_E_STATE: no grid state uploaded, binding 5 not allocation-shaped, or the edit code object missing. */
+int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]);
+
 /* the un-normalised direction and the origin of the one-sample camera ray the frame traces for pixel (px, py), with
  * (px, py) as in the image vrt_read_rgba8 returns (CameraGetRay, comp:474-477, without jitter).  VRT_E_INVALID_ARG: a NULL
  * pointer; VRT_E_OUT_OF_RANGE: a pixel outside the camera's image. */

@@ -233,6 +233,10 @@ SIGNATURES = {
     "vrt_update_grid_delta": (C.c_int, [_ctx, _grid]),
     "vrt_cast_rays": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_cast_rays_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "vrt_read_buffer": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_scene_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
     "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),
     "vrt_camera_set_forward": (C.c_int, [_P(CameraDevice), C.c_float, C.c_float, _P(C.c_float * 3)]),

@@ -35,6 +35,7 @@ void free_ctx(vrt_ctx *c) {
     if (!c) return;
     DeviceGuard dg(c->device); // the caller's current device is restored on return
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    edit_release(c);
     dist_destroy(c);      // (its streams are drained and its communicator closed before the memory they use goes)
     c->res.release_all(); // every allocation, event and stream the context made, in reverse order
     delete c;
@@ -62,7 +63,7 @@ int end_scene_write(vrt_ctx *c) {
 // which derived structures a write to scene buffer `id` invalidates (rebuilt before the next frame, pre_dispatch)
 void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t nbytes) {
     if (id == VRT_BUF_BRICK_STATUS) ctx->status_dirty = true;
-    if (id == VRT_BUF_BRICK_START_INDEX) ctx->start_dirty = true;
+    if (id == VRT_BUF_BRICK_START_INDEX) ctx->start_dirty = true, ctx->edit_state_valid = false; // (the inserts' allocation state comes from brick_start_indices)
     if (id == VRT_BUF_MATERIALS) ctx->materials_dirty = true;
     if (id == VRT_BUF_GRID_STATE || id == VRT_BUF_MATERIALS) return;
     auto widen = [](uint64_t &lo, uint64_t &hi, uint64_t a, uint64_t b) {
@@ -149,6 +150,8 @@ int copy_h2d(vrt_ctx *c, void *dst, const void *src, uint64_t nbytes) {
 }
 
 } // namespace
+
+int vrt_impl::staged_copy_h2d(vrt_ctx *c, void *dst, const void *src, uint64_t nbytes) { return copy_h2d(c, dst, src, nbytes); }
 
 extern "C" {
 

@@ -4,6 +4,7 @@
 //   vrt_dist.hip   the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip   the present / denoise pass
 //   vrt_query.hip  batched ray queries (their kernels and host side)
+//   vrt_edit.hip   batched voxel inserts (host side; their kernels: vrt_edit_kernel.hip, in a code object of their own)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
 #pragma once
@@ -132,6 +133,10 @@ constexpr size_t kStagingSlotBytes = 32u << 20; // pinned staging slot
 constexpr int kStagingSlots = 2;
 
 struct Dist; // vrt_dist.hip
+namespace vrt {
+struct EditState;  // vrt_edit.h
+struct EditStatus;
+} // namespace vrt
 
 struct vrt_ctx {
     vrt_config cfg{};
@@ -212,6 +217,22 @@ struct vrt_ctx {
     vrt_ray_query *d_query_rays = nullptr;
     vrt_ray_hit *d_query_hits = nullptr;
     uint64_t query_capacity = 0;     // rays the two buffers hold
+    // batched voxel inserts (vrt_edit.hip): the code object, the allocation state binding 5 defines (on the device, and the host's
+    // copy of what the last read-back said), and the scratch (kept, grown on demand)
+    hipModule_t edit_module = nullptr;
+    hipFunction_t edit_fn[11] = {};
+    bool edit_state_valid = false;   // false: binding 5 was written since the state was computed (every write goes through mark_dirty)
+    bool edit_ok = false;            // binding 5 is allocation-shaped
+    uint32_t edit_bricks = 0;
+    uint64_t edit_cursor = 0;
+    vrt::EditState *d_edit_state = nullptr;
+    vrt::EditStatus *d_edit_status = nullptr, *h_edit_status = nullptr;
+    uint32_t *d_edit_cell_first = nullptr;                   // [cells], 0xFFFFFFFF between batches
+    uint32_t *d_edit_voxels = nullptr;                       // [4][edit_capacity] per-voxel scratch
+    uint32_t *d_edit_groups = nullptr;                       // [edit_capacity / 256]
+    void *d_edit_table = nullptr;                            // [edit_table_entries] {key, value} pairs
+    uint8_t *d_edit_input = nullptr;                         // vrt_insert_voxels: the batch staged into device memory
+    uint64_t edit_capacity = 0, edit_table_entries = 0, edit_input_bytes = 0;
     size_t lds_bytes = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool split_ok = false;   // small frames may go to half-tile workgroups (vrt_create's conditions other than the number of waves)
@@ -314,6 +335,11 @@ int end_scene_write(vrt_ctx *c);
 void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t nbytes);
 // the unit counters and (contexts that select vrt_pool_kernel) the path records of one stream of persistent-kernel frames
 int lane_init(vrt_ctx *c, vrt::PersistentLane &lane);
+// host memory -> device memory through the pinned staging slots, on the primary stream, as a scene write (vrt_upload's copy)
+int staged_copy_h2d(vrt_ctx *c, void *dst, const void *src, uint64_t nbytes);
+
+// ---- vrt_edit.hip ----
+void edit_release(vrt_ctx *ctx); // unloads the edit code object (vrt_destroy)
 
 // ---- vrt_frame.hip ----
 void note_kernel(vrt_ctx *c, vrt::KernelFn fn); // remember which kernel rendered the most recent frame (vrt_kernel_name reports what ran)

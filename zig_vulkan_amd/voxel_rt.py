@@ -335,6 +335,41 @@ class VoxelRT:
     def buffer_size(self, buf_id: int) -> int:
         return self._lib.vrt_buffer_size(self._h, buf_id)
 
+    # -- voxel inserts on the device --------------------------------------------
+    def insert_voxels(self, xyz, materials) -> None:
+        """BrickGrid.insert for a batch on the scene the context holds (vrt_insert_voxels): xyz (n, 3) as BrickGrid.insert_many takes
+        it (y flipped by insert), materials (n,) bytes; applied in array order, all or nothing.  Given torch tensors on the GPU (int32
+        or uint32-compatible xyz, uint8 materials), the batch is read in device memory (vrt_insert_voxels_device, behind torch's current
+        stream)."""
+        if getattr(xyz, "is_cuda", False):
+            import torch
+            x = xyz.reshape(-1, 3).to(torch.int32).contiguous()
+            m = torch.as_tensor(materials, device=x.device).reshape(-1).to(torch.uint8).contiguous()
+            assert x.shape[0] == m.shape[0]
+            torch.cuda.current_stream(x.device).synchronize()  # (the batch is written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_insert_voxels_device(self._h, x.data_ptr(), m.data_ptr(), x.shape[0]))
+            return
+        x = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
+        m = np.ascontiguousarray(materials, dtype=np.uint8).reshape(-1)
+        assert x.shape[0] == m.shape[0]
+        self._check(self._lib.vrt_insert_voxels(self._h, x.ctypes.data, m.ctypes.data, x.shape[0]))
+
+    def read_buffer(self, buf_id: int) -> np.ndarray:
+        """Copy of scene buffer `buf_id` as frames see it now (vrt_read_buffer), typed: uint32 words for bindings 2, 3 and 5, bytes for
+        4, 6 and the grid state, MATERIAL_DTYPE records for the materials."""
+        n = self.buffer_size(buf_id)
+        out = np.empty(n, dtype=np.uint8)
+        self._check(self._lib.vrt_read_buffer(self._h, buf_id, 0, out.ctypes.data, n))
+        if buf_id == L.BUF_MATERIALS:
+            return out[:n - n % MATERIAL_DTYPE.itemsize].view(MATERIAL_DTYPE)
+        return out.view(_GRID_ARRAY_DTYPES.get(buf_id, np.uint8))
+
+    def scene_bricks(self) -> Tuple[int, int]:
+        """(allocated bricks, next material entry) as the next insert continues them (vrt_scene_bricks)."""
+        out = (C.c_uint32 * 2)()
+        self._check(self._lib.vrt_scene_bricks(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     # -- frame --------------------------------------------------------------
     def draw(self, frames: int = 1) -> None:  # VoxelRT.draw -> Pipeline.draw -> compute dispatch (Pipeline.zig:441)
         if frames == 1:
