@@ -509,8 +509,8 @@ int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vr
  * ERRORS.  A failed call changes no byte of the scene (unlike the host loop, which stops partway).  VRT_E_OUT_OF_RANGE: a
  * voxel outside the grid, or n >= 2^31.  VRT_E_OOM: the batch needs more bricks than brick_alloc leaves, or material entries
  * beyond brick_alloc * B^3.  VRT_E_INVALID_ARG: a NULL pointer with n > 0.  VRT_E_STATE: no grid state uploaded, binding 5 not
- * allocation-shaped (or a loaded cell naming a brick >= A), a context of the multi-GPU pipeline, or the edit code object
- * vrt_edit.hsaco missing next to the library (the message names its path).  n == 0: VRT_OK, the device is not touched.
+ * allocation-shaped (or a loaded cell naming a brick >= A), or a context of the multi-GPU pipeline.  n == 0: VRT_OK, the device
+ * is not touched.
  *
  * ORDERING.  A scene write on the context's stream, like vrt_upload_device: frames queued before the call see the old scene,
  * frames and queries after it the new one.  Both calls return once the batch's status is known (one small read-back); the
@@ -523,7 +523,7 @@ int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *m
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);
 /* out[0] = allocated bricks A, out[1] = next material entry (MaterialAllocator's cursor), as the next insert continues them.
- * VRT_E_STATE: no grid state uploaded, binding 5 not allocation-shaped, or the edit code object missing. */
+ * VRT_E_STATE: no grid state uploaded, or binding 5 not allocation-shaped. */
 int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]);
 
 /* the un-normalised direction and the origin of the one-sample camera ray the frame traces for pixel (px, py), with

@@ -17,7 +17,14 @@ LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 
 
 # Every kernel of the product binary, by symbol: the 28 traversal kernels, 19 others (builders of the derived structures, schedule,
-# present, assembly, self-test) and the two ray-query kernels.  A kernel that appears, goes or returns (a loser of an A/B) fails the test.
+# present, assembly, self-test), the two ray-query kernels and the 11 kernels of the batched voxel inserts: 60.  A kernel that appears,
+# goes or returns (a loser of an A/B) fails the test.
+EDIT_KERNELS = frozenset([
+    "vrt_edit_begin", "vrt_edit_scan_start", "vrt_edit_state", "vrt_edit_validate", "vrt_edit_count", "vrt_edit_scan_groups",
+    "vrt_edit_rank", "vrt_edit_resolve", "vrt_edit_table", "vrt_edit_write", "vrt_edit_finish",
+])
+EDIT_MAX_VGPRS = 32
+EDIT_MAX_LDS_BYTES = 64    # the two scans' per-wave counts
 PRODUCT_KERNELS = frozenset([
     "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb0ELb0ELb0ELi0EEEvNS_11TraceParamsE",
     "_ZN3vrt15vrt_path_kernelILi4ELi5ELb0ELb0ELb0ELb0ELi1EEEvNS_11TraceParamsE",
@@ -70,25 +77,32 @@ PRODUCT_KERNELS = frozenset([
     # ray queries (vrt_query.hip)
     "vrt_ray_query_b4",
     "vrt_ray_query_b8",
-])
+]) | EDIT_KERNELS  # batched voxel inserts (vrt_edit.hip)
 
 
-def _kernels():
+def code_object_notes():
+    """The notes (llvm-readelf --notes) of every gfx950 code object inside libvrt_hip.so."""
     if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
         pytest.skip("llvm-objdump / llvm-readelf not found under /opt/rocm/lib/llvm/bin")
     if not os.path.exists(LIB):
         pytest.skip("libvrt_hip.so not built")
-    out = {}
+    out = []
     with tempfile.TemporaryDirectory() as d:
         shutil.copy(LIB, os.path.join(d, "lib.so"))
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True, capture_output=True)
         for name in sorted(os.listdir(d)):
             if "gfx950" not in name:
                 continue
-            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", name], cwd=d, check=True, capture_output=True, text=True).stdout
-            for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size: (\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
-                lds, kname, scratch, vgpr = m.groups()
-                out[kname] = dict(lds=int(lds), scratch=int(scratch), vgpr=int(vgpr))
+            out.append(subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", name], cwd=d, check=True, capture_output=True, text=True).stdout)
+    return out
+
+
+def _kernels():
+    out = {}
+    for notes in code_object_notes():
+        for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size: (\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
+            lds, kname, scratch, vgpr = m.groups()
+            out[kname] = dict(lds=int(lds), scratch=int(scratch), vgpr=int(vgpr))
     assert len(out) >= 20
     return out
 
@@ -99,8 +113,10 @@ def test_the_product_binary_holds_exactly_the_shipped_kernels():
     the derived structures, schedule, un-swizzle, the two present kernels, vrt_pool_resolve_kernel, vrt_check_materials_plain).  Round 5:
     + vrt_pool_kernel for 4^3 bricks, the two builders of the byte-per-cell material (vrt_build_cell_material<4>, <8>) and the present pass's
     staged kernel as its own (vrt_denoise_tile_kernel<20>, <0>; vrt_denoise_kernel<NEAR> keeps the taps from global memory).  Round 6:
-    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel).  The ray queries add vrt_ray_query_b4 / _b8;
-    vrt_build_status_blocks, whose words only development variants read, is in the development build alone."""
+    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel).  The ray queries add vrt_ray_query_b4 / _b8,
+    the batched voxel inserts their 11 vrt_edit_* kernels (60 in all); vrt_build_status_blocks, whose words only development variants
+    read, is in the development build alone."""
+    assert len(PRODUCT_KERNELS) == 60
     ks = _kernels()
     assert set(ks) == PRODUCT_KERNELS, (sorted(set(ks) - PRODUCT_KERNELS), sorted(PRODUCT_KERNELS - set(ks)))
     traversal = [n for n in ks if "vrt_trace_kernel" in n or "vrt_path_kernel" in n or "vrt_pool_kernel" in n]
@@ -110,6 +126,8 @@ def test_the_product_binary_holds_exactly_the_shipped_kernels():
 def test_no_traversal_kernel_owns_static_lds():
     for name, k in _kernels().items():
         if "vrt_schedule_kernel" in name or "vrt_denoise_" in name:   # (the present pass keeps its spiral's per-sample constants — and its box of texels — in LDS)
+            continue
+        if name.startswith("vrt_edit_"):   # (the scans' per-wave counts: bounded by test_edit_kernels_use_no_scratch_little_lds_and_few_registers)
             continue
         assert k["lds"] == 0, f"{name}: {k['lds']} bytes of static LDS (a per-lane struct promoted to LDS?)"
 
@@ -203,3 +221,12 @@ def test_ray_query_kernels_hold_5_waves_without_scratch():
     for name, k in ks.items():
         assert k["vgpr"] <= 96 and k["scratch"] == 0 and k["lds"] == 0, (name, k)
         assert _scratch_instructions(name) == 0, name
+
+
+def test_edit_kernels_use_no_scratch_little_lds_and_few_registers():
+    """The 11 vrt_edit_* kernels of the batched voxel inserts, and no other of that name: no scratch, at most the two scans' per-wave
+    counts in LDS (16 B in vrt_edit_count / _rank, 64 B in vrt_edit_scan_groups) and at most 32 VGPRs."""
+    ks = {n: k for n, k in _kernels().items() if n.startswith("vrt_edit_")}
+    assert set(ks) == EDIT_KERNELS, (sorted(set(ks) - EDIT_KERNELS), sorted(EDIT_KERNELS - set(ks)))
+    for name, k in ks.items():
+        assert k["scratch"] == 0 and k["lds"] <= EDIT_MAX_LDS_BYTES and k["vgpr"] <= EDIT_MAX_VGPRS, (name, k)

@@ -35,7 +35,6 @@ void free_ctx(vrt_ctx *c) {
     if (!c) return;
     DeviceGuard dg(c->device); // the caller's current device is restored on return
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    edit_release(c);
     dist_destroy(c);      // (its streams are drained and its communicator closed before the memory they use goes)
     c->res.release_all(); // every allocation, event and stream the context made, in reverse order
     delete c;

@@ -4,7 +4,7 @@
 //   vrt_dist.hip   the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip   the present / denoise pass
 //   vrt_query.hip  batched ray queries (their kernels and host side)
-//   vrt_edit.hip   batched voxel inserts (host side; their kernels: vrt_edit_kernel.hip, in a code object of their own)
+//   vrt_edit.hip   batched voxel inserts (their kernels and host side)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
 #pragma once
@@ -134,7 +134,7 @@ constexpr int kStagingSlots = 2;
 
 struct Dist; // vrt_dist.hip
 namespace vrt {
-struct EditState;  // vrt_edit.h
+struct EditState;  // vrt_edit.hip
 struct EditStatus;
 } // namespace vrt
 
@@ -217,10 +217,8 @@ struct vrt_ctx {
     vrt_ray_query *d_query_rays = nullptr;
     vrt_ray_hit *d_query_hits = nullptr;
     uint64_t query_capacity = 0;     // rays the two buffers hold
-    // batched voxel inserts (vrt_edit.hip): the code object, the allocation state binding 5 defines (on the device, and the host's
-    // copy of what the last read-back said), and the scratch (kept, grown on demand)
-    hipModule_t edit_module = nullptr;
-    hipFunction_t edit_fn[11] = {};
+    // batched voxel inserts (vrt_edit.hip): the allocation state binding 5 defines (on the device, and the host's copy of what the
+    // last read-back said), and the scratch (kept, grown on demand)
     bool edit_state_valid = false;   // false: binding 5 was written since the state was computed (every write goes through mark_dirty)
     bool edit_ok = false;            // binding 5 is allocation-shaped
     uint32_t edit_bricks = 0;
@@ -337,9 +335,6 @@ void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t n
 int lane_init(vrt_ctx *c, vrt::PersistentLane &lane);
 // host memory -> device memory through the pinned staging slots, on the primary stream, as a scene write (vrt_upload's copy)
 int staged_copy_h2d(vrt_ctx *c, void *dst, const void *src, uint64_t nbytes);
-
-// ---- vrt_edit.hip ----
-void edit_release(vrt_ctx *ctx); // unloads the edit code object (vrt_destroy)
 
 // ---- vrt_frame.hip ----
 void note_kernel(vrt_ctx *c, vrt::KernelFn fn); // remember which kernel rendered the most recent frame (vrt_kernel_name reports what ran)

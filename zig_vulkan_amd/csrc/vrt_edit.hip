@@ -1,71 +1,398 @@
 // vrt_edit.hip — batched voxel inserts behind the C ABI (vrt_insert_voxels, vrt_insert_voxels_device), the allocation state they
-// continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer).  BrickGrid.insert (Grid.zig:129-194) for a whole
-// batch, on the context's scene buffers, with the bytes a vrt_grid gives after vrt_grid_insert_many; a failed batch writes nothing.
-// The kernels live in a code object of their own next to the library (vrt_edit_kernel.hip -> vrt_edit.hsaco), loaded on a context's
-// first insert with hipModuleLoad and unloaded by vrt_destroy.  The library keeps no other dependency on it: without the file, frames
-// and queries work and inserts fail with VRT_E_STATE.  DESIGN.md §11.
+// continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels vrt_edit_* and their host side.
+// BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
+// vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
+// instructions.  "Binding k" below is buffer id k of vrt_buffer_id (binding 5 = VRT_BUF_BRICK_START_INDEX), as in include/vrt_hip.h's
+// insert block.
+//
+// A batch runs as a chain of kernels on the context's stream:
+//   vrt_edit_begin        clears the batch's status (and, after a write to binding 5, the accumulators of its scan)
+//   vrt_edit_scan_start   binding 5 -> first unset entry, last set entry, type bits, largest start   (only after a write to binding 5)
+//   vrt_edit_state        -> allocated bricks A, material cursor, allocation-shaped or not             (idem)
+//   vrt_edit_validate     per voxel: range, cell, voxel within the brick; loaded cells: brick and entry; others: atomicMin of the
+//                         voxel's index into the cell's scratch word (the cell's first voxel in the batch)
+//   vrt_edit_count        first voxels of new cells, counted per workgroup
+//   vrt_edit_scan_groups  exclusive scan of the workgroup counts; new bricks; brick / material exhaustion
+//   vrt_edit_rank         first voxels: brick A + rank (their order in the batch)
+//   vrt_edit_resolve      the other voxels of new cells: the brick of the cell's first voxel; entry of binding 6
+//   vrt_edit_table        clears the cells' scratch words; last writer of every entry of binding 6 (open addressing, atomicMax)
+//   vrt_edit_write        the scene's bytes, and the written ranges
+//   vrt_edit_finish       A and the cursor move on; the status the host reads back
+// Every kernel after vrt_edit_validate reads the error word first and writes no scene byte when it is set.
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <unistd.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include "vrt_ctx.h"
-#include "vrt_edit.h"
+
+namespace vrt {
+
+constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
+constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
+constexpr uint32_t kEditNone = 0xFFFFFFFFu;
+
+// error bits of EditStatus::err (the host reports the highest-ranked one)
+constexpr uint32_t kEditErrShape = 1u << 0;  // binding 5 is not allocation-shaped                       -> VRT_E_STATE
+constexpr uint32_t kEditErrRange = 1u << 1;  // a voxel outside the grid                                  -> VRT_E_OUT_OF_RANGE
+constexpr uint32_t kEditErrCell = 1u << 2;   // a loaded cell names a brick at or beyond the allocated bricks -> VRT_E_STATE
+constexpr uint32_t kEditErrOom = 1u << 3;    // bricks or material entries exhausted                       -> VRT_E_OOM
+
+// The allocation state that binding 5 defines (kept on the device, current across inserts).  While the scan of binding 5 runs,
+// first_unset / last_set_end / type_bits / max_start accumulate; vrt_edit_state turns them into bricks / cursor / ok.
+struct EditState {
+    uint32_t first_unset;  // lowest index holding 0xFFFFFFFF (kEditNone: none)
+    uint32_t last_set_end; // 1 + highest index not holding 0xFFFFFFFF (0: none)
+    uint32_t type_bits;    // 1: some set entry has its type bit (bit 31)
+    uint32_t max_start;    // largest value of a set entry
+    uint32_t bricks;       // A: allocated bricks
+    uint32_t ok;           // 1: binding 5 is allocation-shaped and its cursor lies within binding 6
+    uint64_t cursor;       // next material entry
+};
+
+// What one batch reads back (one small copy).  Ranges are element indices [lo, hi] (lo > hi: nothing written).
+struct EditStatus {
+    uint32_t err;
+    uint32_t new_bricks;
+    uint32_t bricks;        // allocated bricks after the batch (before it if err != 0)
+    uint32_t ok;            // the state's shape flag
+    uint64_t cursor;        // next material entry after the batch
+    uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries)
+    uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit
+    uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
+};
+
+struct EditArgs {
+    // the scene (the context's buffers)
+    uint32_t *status;        // binding 2
+    uint32_t *index;         // binding 3
+    uint32_t *occupancy;     // binding 4 (as 32-bit words: bits are set with atomicOr on the containing word)
+    uint32_t *start;         // binding 5
+    uint8_t *material;       // binding 6
+    // the batch
+    const uint32_t *xyz;     // 3 per voxel, y as vrt_grid_insert takes it
+    const uint8_t *materials;
+    uint32_t n;
+    uint32_t groups;         // ceil(n / kEditBlock)
+    uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
+    // scratch (the context's, grown on demand)
+    uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded; kEditNone between batches
+    uint32_t *vcell;         // [n] the voxel's cell (kEditNone: not written)
+    uint32_t *vinfo;         // [n] bit 31: cell not loaded, bit 30: first voxel of that cell, bits 0-8: voxel within the brick
+    uint32_t *vbrick;        // [n] brick index
+    uint32_t *vslot;         // [n] entry of binding 6
+    uint32_t *group_sums;    // [ceil(n / kEditBlock)] first voxels per workgroup, then their exclusive scan
+    uint2 *table;            // [table_mask + 1] {slot + 1, last batch index writing it} (zeroed before each batch)
+    uint32_t table_mask;
+    EditState *state;
+    EditStatus *out;
+    // the grid
+    uint32_t voxel_dim_x, voxel_dim_y, voxel_dim_z;
+    uint32_t dim_x, dim_z;
+    uint32_t b, bits, brick_bytes;  // B, B^3, B^3 / 8
+    uint32_t brick_alloc;
+    uint32_t start_words;           // entries of binding 5 scanned by vrt_edit_scan_start (= brick_alloc)
+    uint64_t material_entries;      // bytes of binding 6 (brick_alloc * B^3)
+};
+
+} // namespace vrt
+
+using namespace vrt;
+
+namespace {
+
+__device__ inline uint32_t lane_id() { return threadIdx.x & 63u; }
+
+__device__ inline uint32_t wave_min(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ inline uint32_t wave_max(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ inline uint32_t wave_or(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// Guideline 12: one atomic per wave on the shared words (every lane of the wave must call these)
+__device__ inline void wave_atomic_min(uint32_t *p, uint32_t v) {
+    v = wave_min(v);
+    if (lane_id() == 0 && v != kEditNone) atomicMin(p, v);
+}
+__device__ inline void wave_atomic_max(uint32_t *p, uint32_t v) {
+    v = wave_max(v);
+    if (lane_id() == 0 && v != 0u) atomicMax(p, v);
+}
+__device__ inline void wave_atomic_or(uint32_t *p, uint32_t v) {
+    v = wave_or(v);
+    if (lane_id() == 0 && v != 0u) atomicOr(p, v);
+}
+
+__device__ inline uint32_t table_hash(uint32_t key, uint32_t mask) { return ((key * 2654435761u) ^ (key >> 15)) & mask; }
+
+// exclusive prefix of `flag` over the workgroup (kEditBlock threads, four waves); *total: the workgroup's count
+__device__ inline uint32_t group_prefix(bool flag, uint32_t *total) {
+    __shared__ uint32_t wave_counts[kEditBlock / 64];
+    const uint64_t m = __ballot(flag);
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_counts[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, sum = 0;
+    for (uint32_t w = 0; w < kEditBlock / 64; w++) {
+        if (w < wave) before += wave_counts[w];
+        sum += wave_counts[w];
+    }
+    *total = sum;
+    return before + below;
+}
+
+} // namespace
+
+extern "C" {
+
+__global__ void __launch_bounds__(64) vrt_edit_begin(EditArgs a) {
+    if (threadIdx.x != 0) return;
+    EditStatus s;
+    s.err = 0;
+    s.new_bricks = 0;
+    s.bricks = 0;
+    s.ok = 0;
+    s.cursor = 0;
+    s.cell_lo = kEditNone, s.cell_hi = 0;
+    s.occ_lo = kEditNone, s.occ_hi = 0;
+    s.mat_lo = kEditNone, s.mat_hi = 0;
+    *a.out = s;
+    if (a.rescan) {
+        a.state->first_unset = kEditNone;
+        a.state->last_set_end = 0;
+        a.state->type_bits = 0;
+        a.state->max_start = 0;
+    }
+}
+
+// binding 5, grid-stride (every lane runs the same number of trips, so the wave reductions see every lane)
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_scan_start(EditArgs a) {
+    uint32_t first_unset = kEditNone, last_set_end = 0, type_bits = 0, max_start = 0;
+    const uint32_t stride = gridDim.x * kEditBlock;
+    for (uint32_t base = blockIdx.x * kEditBlock; base < a.start_words; base += stride) {
+        const uint32_t j = base + threadIdx.x;
+        if (j < a.start_words) {
+            const uint32_t v = a.start[j];
+            if (v == 0xFFFFFFFFu) {
+                first_unset = min(first_unset, j);
+            } else {
+                last_set_end = max(last_set_end, j + 1u);
+                type_bits |= v >> 31;
+                max_start = max(max_start, v);
+            }
+        }
+    }
+    wave_atomic_min(&a.state->first_unset, first_unset);
+    wave_atomic_max(&a.state->last_set_end, last_set_end);
+    wave_atomic_or(&a.state->type_bits, type_bits);
+    wave_atomic_max(&a.state->max_start, max_start);
+}
+
+__global__ void __launch_bounds__(64) vrt_edit_state(EditArgs a) {
+    if (threadIdx.x != 0) return;
+    EditState s = *a.state;
+    s.bricks = s.first_unset == kEditNone ? a.start_words : s.first_unset;
+    s.cursor = s.bricks ? (uint64_t)s.max_start + a.bits : 0u;
+    s.ok = (s.type_bits == 0 && s.last_set_end <= s.bricks && s.cursor <= a.material_entries) ? 1u : 0u;
+    *a.state = s;
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool ok = a.state->ok != 0;
+    const uint32_t bricks = a.state->bricks;
+    uint32_t cell = kEditNone, info = 0, err = 0;
+    if (i < a.n && ok) {
+        const uint32_t x = a.xyz[3u * i], y = a.xyz[3u * i + 1u], z = a.xyz[3u * i + 2u];
+        if (x >= a.voxel_dim_x || y >= a.voxel_dim_y || z >= a.voxel_dim_z) {
+            err = kEditErrRange; // Grid.zig:130-132
+        } else {
+            const uint32_t fy = a.voxel_dim_y - 1u - y; // Grid.zig:135
+            const uint32_t g = (uint32_t)((uint64_t)(x / a.b) + (uint64_t)a.dim_x * ((uint64_t)(z / a.b) + (uint64_t)a.dim_z * (fy / a.b))); // gridAt
+            const uint32_t nth = x % a.b + a.b * (z % a.b + a.b * (fy % a.b));                                                            // voxelAt
+            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
+                const uint32_t brick = a.index[g];
+                if (brick >= bricks) {
+                    err = kEditErrCell;
+                } else {
+                    a.vbrick[i] = brick;
+                    a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + nth; // (< cursor <= binding 6's size: the state is allocation-shaped)
+                    cell = g;
+                    info = nth;
+                }
+            } else {
+                atomicMin(&a.cell_first[g], i);
+                cell = g;
+                info = 0x80000000u | nth;
+            }
+        }
+    }
+    if (i < a.n) {
+        a.vcell[i] = cell;
+        a.vinfo[i] = info;
+    }
+    if (!ok && i == 0) err = kEditErrShape;
+    wave_atomic_or(&a.out->err, err);
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_count(EditArgs a) {
+    if (a.out->err) return; // (no kernel of this one writes the word: uniform)
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    bool first = false;
+    if (i < a.n) {
+        const uint32_t info = a.vinfo[i];
+        first = (info & 0x80000000u) && a.cell_first[a.vcell[i]] == i;
+        if (first) a.vinfo[i] = info | 0x40000000u;
+    }
+    uint32_t total;
+    (void)group_prefix(first, &total);
+    if (threadIdx.x == 0) a.group_sums[blockIdx.x] = total;
+}
+
+// one workgroup: every thread scans a run of consecutive workgroup counts
+__global__ void __launch_bounds__(kEditScanBlock) vrt_edit_scan_groups(EditArgs a) {
+    if (a.out->err) return;
+    __shared__ uint32_t wave_sums[kEditScanBlock / 64];
+    const uint32_t t = threadIdx.x, lane = lane_id(), wave = t >> 6;
+    const uint32_t groups = a.groups, run = (groups + kEditScanBlock - 1u) / kEditScanBlock;
+    const uint32_t lo = min(groups, t * run), hi = min(groups, lo + run);
+    uint32_t own = 0;
+    for (uint32_t g = lo; g < hi; g++) own += a.group_sums[g];
+    uint32_t v = own; // inclusive scan within the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
+        if ((int)lane >= o) v += u;
+    }
+    if (lane == 63) wave_sums[wave] = v;
+    __syncthreads();
+    uint32_t before = v - own, total = 0;
+    for (uint32_t w = 0; w < kEditScanBlock / 64; w++) {
+        if (w < wave) before += wave_sums[w];
+        total += wave_sums[w];
+    }
+    for (uint32_t g = lo; g < hi; g++) {
+        const uint32_t c = a.group_sums[g];
+        a.group_sums[g] = before;
+        before += c;
+    }
+    if (t == 0) {
+        a.out->new_bricks = total;
+        const EditState s = *a.state;
+        if ((uint64_t)s.bricks + total > a.brick_alloc || s.cursor + (uint64_t)total * a.bits > a.material_entries) atomicOr(&a.out->err, kEditErrOom);
+    }
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_rank(EditArgs a) {
+    if (a.out->err) return;
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool first = i < a.n && (a.vinfo[i] & 0x40000000u);
+    uint32_t total;
+    const uint32_t rank = a.group_sums[blockIdx.x] + group_prefix(first, &total);
+    if (first) a.vbrick[i] = a.state->bricks + rank; // Grid.zig:147, in the order of first occurrence
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_resolve(EditArgs a) {
+    if (a.out->err) return; // (this kernel may set the word: no wave-wide work follows)
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t info = a.vinfo[i];
+    if (!(info & 0x80000000u)) return;
+    const uint32_t f = a.cell_first[a.vcell[i]];
+    if (f >= a.n || !(a.vinfo[f] & 0x40000000u)) { // (cannot happen while the scratch words are clean; never write through a stale one)
+        atomicOr(&a.out->err, kEditErrCell);
+        return;
+    }
+    const uint32_t brick = a.vbrick[f];
+    if (!(info & 0x40000000u)) a.vbrick[i] = brick;
+    // MaterialAllocator.nextSlotIndex (MaterialAllocator.zig:39) for new brick r: cursor + r * B^3; Grid.zig:173
+    a.vslot[i] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits) + (info & 0x1FFu);
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t cell = a.vcell[i];
+    if (a.vinfo[i] & 0x80000000u) a.cell_first[cell] = kEditNone; // (whatever the error word says: the scratch is clean for the next batch)
+    if (a.out->err || cell == kEditNone) return;
+    const uint32_t key = a.vslot[i] + 1u;
+    uint32_t h = table_hash(key, a.table_mask);
+    for (;;) { // (the table has at least twice as many entries as the batch has voxels: an empty one is always found)
+        const uint32_t prev = atomicCAS(&a.table[h].x, 0u, key);
+        if (prev == 0u || prev == key) {
+            atomicMax(&a.table[h].y, i);
+            return;
+        }
+        h = (h + 1u) & a.table_mask;
+    }
+}
+
+__global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
+    if (a.out->err) return;
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    uint32_t cell_lo = kEditNone, cell_hi = 0, occ_lo = kEditNone, occ_hi = 0, mat_lo = kEditNone, mat_hi = 0;
+    const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
+    if (cell != kEditNone) {
+        const uint32_t slot = a.vslot[i], brick = a.vbrick[i], info = a.vinfo[i], nth = info & 0x1FFu;
+        const uint32_t key = slot + 1u;
+        uint32_t h = table_hash(key, a.table_mask);
+        while (a.table[h].x != key) h = (h + 1u) & a.table_mask;
+        if (a.table[h].y == i) { // the last write of this entry in the batch (Grid.zig:174)
+            a.material[slot] = a.materials[i];
+            mat_lo = mat_hi = slot;
+        }
+        // Grid.zig:180-185: the byte's bit, set through the 32-bit word that holds it (records are 8 or 64 bytes: words are aligned)
+        const uint32_t byte = brick * a.brick_bytes + (nth >> 3);
+        atomicOr(&a.occupancy[byte >> 2], 1u << ((byte & 3u) * 8u + (nth & 7u)));
+        occ_lo = occ_hi = byte;
+        if (info & 0x40000000u) { // the first voxel of a cell that was not loaded: Grid.zig:160-168, 188-193
+            atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
+            a.index[cell] = brick;
+            a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
+            cell_lo = cell_hi = cell;
+        }
+    }
+    wave_atomic_min(&a.out->cell_lo, cell_lo);
+    wave_atomic_max(&a.out->cell_hi, cell_hi);
+    wave_atomic_min(&a.out->occ_lo, occ_lo);
+    wave_atomic_max(&a.out->occ_hi, occ_hi);
+    wave_atomic_min(&a.out->mat_lo, mat_lo);
+    wave_atomic_max(&a.out->mat_hi, mat_hi);
+}
+
+__global__ void __launch_bounds__(64) vrt_edit_finish(EditArgs a) {
+    if (threadIdx.x != 0) return;
+    EditState s = *a.state;
+    EditStatus o = *a.out;
+    if (o.err == 0 && o.new_bricks) {
+        s.bricks += o.new_bricks;
+        s.cursor += (uint64_t)o.new_bricks * a.bits;
+        a.state->bricks = s.bricks;
+        a.state->cursor = s.cursor;
+    }
+    a.out->bricks = s.bricks;
+    a.out->cursor = s.cursor;
+    a.out->ok = s.ok;
+}
+
+} // extern "C"
 
 using namespace vrt_impl;
 
 namespace {
 
-enum EditKernel { K_BEGIN, K_SCAN_START, K_STATE, K_VALIDATE, K_COUNT, K_SCAN_GROUPS, K_RANK, K_RESOLVE, K_TABLE, K_WRITE, K_FINISH, K_KERNELS };
-const char *const kEditKernelNames[K_KERNELS] = {"vrt_edit_begin",  "vrt_edit_scan_start", "vrt_edit_state",   "vrt_edit_validate",
-                                                "vrt_edit_count",  "vrt_edit_scan_groups", "vrt_edit_rank",   "vrt_edit_resolve",
-                                                "vrt_edit_table",  "vrt_edit_write",      "vrt_edit_finish"};
-static_assert(K_KERNELS == sizeof(((vrt_ctx *)nullptr)->edit_fn) / sizeof(hipFunction_t), "one function slot per edit kernel");
-
-// the edit code object: vrt_edit.hsaco in the library's own directory
-std::string code_object_path() {
-    Dl_info info{};
-    std::string dir = ".";
-    if (dladdr(reinterpret_cast<void *>(&vrt_impl::edit_release), &info) && info.dli_fname) {
-        const std::string lib = info.dli_fname;
-        const size_t slash = lib.rfind('/');
-        if (slash != std::string::npos) dir = lib.substr(0, slash);
-    }
-    return dir + "/vrt_edit.hsaco";
-}
-
-int load_edit_kernels(vrt_ctx *ctx) {
-    if (ctx->edit_module) return VRT_OK;
-    const std::string path = code_object_path();
-    if (access(path.c_str(), R_OK) != 0) return fail(ctx, VRT_E_STATE, "voxel-edit code object missing: " + path);
-    hipModule_t m = nullptr;
-    const hipError_t e = hipModuleLoad(&m, path.c_str());
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, VRT_E_STATE, "voxel-edit code object " + path + " did not load: " + hipGetErrorString(e));
-    }
-    for (int k = 0; k < K_KERNELS; k++) {
-        const hipError_t ef = hipModuleGetFunction(&ctx->edit_fn[k], m, kEditKernelNames[k]);
-        if (ef != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipModuleUnload(m);
-            std::fill(ctx->edit_fn, ctx->edit_fn + K_KERNELS, nullptr);
-            return fail(ctx, VRT_E_STATE, "voxel-edit code object " + path + " lacks " + kEditKernelNames[k] + ": " + hipGetErrorString(ef));
-        }
-    }
-    ctx->edit_module = m;
-    return VRT_OK;
-}
-
-// what every entry point checks before it touches the device: the scene is there, this context may edit it, the kernels are loaded,
-// and the small buffers of the allocation state exist
+// what every entry point checks before it touches the device: the scene is there, this context may edit it, and the small
+// buffers of the allocation state exist
 int edit_prepare(vrt_ctx *ctx) {
     if (ctx->dist) return fail(ctx, VRT_E_STATE, "voxel inserts are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
-    const int rc = load_edit_kernels(ctx);
-    if (rc != VRT_OK) return rc;
     if (!ctx->d_edit_state) {
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_state, sizeof(vrt::EditState)));
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_status, sizeof(vrt::EditStatus)));
@@ -141,29 +468,27 @@ vrt::EditArgs edit_args(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materi
     return a;
 }
 
-int launch(vrt_ctx *ctx, EditKernel k, vrt::EditArgs &a, uint32_t groups, uint32_t threads) {
+int launch(vrt_ctx *ctx, void (*fn)(vrt::EditArgs), const vrt::EditArgs &a, uint32_t groups, uint32_t threads) {
     if (groups == 0) return VRT_OK;
-    size_t bytes = sizeof a;
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    (void)hipGetLastError(); // (the thread's stale error is not this launch's)
-    VRT_HIP(ctx, hipModuleLaunchKernel(ctx->edit_fn[k], groups, 1, 1, threads, 1, 1, 0, ctx->stream, nullptr, config));
+    VRT_LAUNCH(fn, dim3(groups), dim3(threads), 0, ctx->stream, a);
+    VRT_HIP(ctx, hipGetLastError());
     return VRT_OK;
 }
 
 // the head of every chain: the batch's status cleared and, after a write to binding 5, the allocation state computed from it
 int launch_state(vrt_ctx *ctx, vrt::EditArgs &a) {
-    int rc = launch(ctx, K_BEGIN, a, 1, 64);
+    int rc = launch(ctx, vrt_edit_begin, a, 1, 64);
     if (rc == VRT_OK && a.rescan) {
         const uint32_t groups = std::max<uint32_t>(1u, std::min<uint32_t>((a.start_words + vrt::kEditBlock - 1u) / vrt::kEditBlock, 2048u));
-        rc = launch(ctx, K_SCAN_START, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, K_STATE, a, 1, 64);
+        rc = launch(ctx, vrt_edit_scan_start, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_state, a, 1, 64);
     }
     return rc;
 }
 
 // the tail of every chain: the status back to the host (the one read-back), and the host's copy of the state
 int read_status(vrt_ctx *ctx, vrt::EditArgs &a, vrt::EditStatus *out) {
-    int rc = launch(ctx, K_FINISH, a, 1, 64);
+    int rc = launch(ctx, vrt_edit_finish, a, 1, 64);
     if (rc != VRT_OK) return rc;
     VRT_HIP(ctx, hipMemcpyAsync(ctx->h_edit_status, ctx->d_edit_status, sizeof(vrt::EditStatus), hipMemcpyDeviceToHost, ctx->stream));
     VRT_HIP(ctx, wait_stream(ctx->stream));
@@ -191,13 +516,13 @@ int insert(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t
     const uint32_t groups = a.groups;
     VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
     rc = launch_state(ctx, a);
-    if (rc == VRT_OK) rc = launch(ctx, K_VALIDATE, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_COUNT, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_SCAN_GROUPS, a, 1, vrt::kEditScanBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_RANK, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_RESOLVE, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_TABLE, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, K_WRITE, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
     if (rc != VRT_OK) {
         (void)wait_stream(ctx->stream);
         ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
@@ -237,15 +562,6 @@ int check_batch(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uin
 }
 
 } // namespace
-
-namespace vrt_impl {
-void edit_release(vrt_ctx *ctx) {
-    if (!ctx->edit_module) return;
-    (void)hipModuleUnload(ctx->edit_module);
-    ctx->edit_module = nullptr;
-    std::fill(ctx->edit_fn, ctx->edit_fn + K_KERNELS, nullptr);
-}
-} // namespace vrt_impl
 
 extern "C" {
 
