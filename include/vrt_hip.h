@@ -433,6 +433,18 @@ void vrt_grid_destroy(vrt_grid *g);
 int vrt_grid_insert(vrt_grid *g, uint64_t x, uint64_t y, uint64_t z, uint8_t material_index);
 /* Bulk form: n records of {x,y,z} u32 triples + material byte. */
 int vrt_grid_insert_many(vrt_grid *g, const uint32_t *xyz, const uint8_t *materials, uint64_t n);
+/* Removal (the reference has none: BrickGrid has only insert).  n voxels, x, y, z per voxel as vrt_grid_insert takes them (y
+ * flipped, Grid.zig:135).  All or nothing: a voxel outside the grid gives VRT_E_OUT_OF_RANGE and changes nothing.  A voxel whose
+ * cell is not loaded, or whose occupancy bit is already 0, is a no-op (duplicates are harmless); every other voxel loses its
+ * occupancy bit.  No byte of material_indices is written (the walk never reads the entry of an empty voxel).  After the whole
+ * batch, every loaded cell that holds a voxel of the batch and whose brick has no occupancy bit left loses its status bit — so the
+ * result does not depend on the order of the batch.  THE BRICK IS NOT REUSED: brick_indices[cell], the brick's brick_start_indices
+ * entry, active_bricks and the material cursor stay as they are, and a later insert into that cell takes a fresh brick, as
+ * Grid.zig:141-148 does for any cell that is not loaded (no compaction).  Deltas: the occupancy bytes and the status words that
+ * lost a bit; no other. */
+int vrt_grid_remove_many(vrt_grid *g, const uint32_t *xyz, uint64_t n);
+/* the batch of one */
+int vrt_grid_remove(vrt_grid *g, uint64_t x, uint64_t y, uint64_t z);
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g);
 /* Borrowed pointer + byte size of host array `id` (GRID_STATE..MATERIAL_INDEX;
  * MATERIALS is not part of the grid => NULL). */
@@ -519,6 +531,20 @@ int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vr
 int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n);
 /* xyz and materials in device memory, ordered after every earlier write on the context's stream */
 int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n);
+/* ---- Batched voxel removal from the uploaded scene ---------------------------------------------------------------------
+ * vrt_grid_remove_many for n voxels at once, on the GPU: after vrt_remove_voxels(ctx, xyz, n) on a context whose bindings 2-6 equal
+ * a vrt_grid's arrays, bindings 2-6 equal that grid's arrays after vrt_grid_remove_many(g, xyz, n), byte for byte.  Only
+ * bindings 2 (status bits of cells whose brick was emptied) and 4 (occupancy bits) are written.  A BRICK THAT WAS EMPTIED IS NOT
+ * REUSED: binding 5 stays allocation-shaped, vrt_scene_bricks is unchanged, and vrt_insert_voxels into such a cell takes a fresh
+ * brick.  Errors, ordering and staging as for vrt_insert_voxels: a failed call changes no scene byte; VRT_E_OUT_OF_RANGE (a voxel
+ * outside the grid, or n >= 2^31), VRT_E_INVALID_ARG (a NULL pointer with n > 0), VRT_E_STATE (no grid state uploaded, binding 5
+ * not allocation-shaped, a loaded cell naming a brick >= A, or a context of the multi-GPU pipeline); n == 0: VRT_OK, the device is
+ * not touched.  The derived structures are refreshed for the occupancy bytes that lost a bit and the status words of the cells
+ * that became unloaded; a batch of no-ops refreshes nothing. */
+/* xyz in host memory (staged through the context's pinned slots) */
+int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
+/* xyz in device memory, ordered after every earlier write on the context's stream */
+int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
 /* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Batched voxel inserts on the GPU (vrt_insert_voxels, vrt_insert_voxels_device) against the host path they replace
-(vrt_grid_insert_many + vrt_update_grid_delta), end to end, on the headline scene (512^3 voxels in 8^3 bricks, terrain) and the
-reference app's scene (128 x 64 x 128 bricks of 4^3, terrain).  DESIGN.md §11 gives the table.
+"""Batched voxel inserts and removals on the GPU (vrt_insert_voxels, vrt_remove_voxels and their _device forms) against the host
+paths they replace (vrt_grid_insert_many / vrt_grid_remove_many + vrt_update_grid_delta), end to end, on the headline scene (512^3
+voxels in 8^3 bricks, terrain) and the reference app's scene (128 x 64 x 128 bricks of 4^3, terrain).  DESIGN.md §11 and §12 give
+the tables.
 
 Per scene and batch size (10^3, 10^5, 10^6, 1.6 x 10^7 voxels) two kinds of batch: random voxels over the grid, and a brush — a solid
 sphere around the hit of the camera's centre ray.  Reported, in ms (median of --reps for the device paths, one run of the host path
@@ -13,7 +14,10 @@ from 10^6 voxels up):
 and once per scene the first insert's scan of binding 5 (vrt_scene_bricks after vrt_upload_grid).  Every device run starts from the
 scene as uploaded (vrt_upload_grid between runs, not timed); the host grid takes the batches one after another.
 
-    python tools/edit_bench.py [--reps 5] [--sizes 1000,100000,1000000,16000000] [--out results.json]
+Removal rows (--ops insert,remove; op "remove" in a row): random SOLID voxels of the scene, and the same brush as a dig.  The host grid
+is built anew before each of its runs (not timed), so every run removes solid voxels; otherwise the rows read as the insert rows do.
+
+    python tools/edit_bench.py [--reps 5] [--sizes 1000,100000,1000000,16000000] [--ops insert,remove] [--out results.json]
 Kernel times: a run of its own under `rocprofv3 --kernel-trace --stats` (e.g. with --sizes 1000000 --reps 3)."""
 import argparse
 import json
@@ -49,6 +53,29 @@ def brush_batch(rt, vd, n):
     return p.astype(np.uint32), np.full(len(p), 5, np.uint8)
 
 
+def solid_batch(rng, grid, n, chunk=1 << 16):
+    """n random solid voxels of the grid (a random loaded cell, then a random solid voxel of its brick; with repeats), in the
+    coordinates insert and remove take."""
+    from zig_vulkan_amd import _lib as L
+    b = grid.brick_dimension
+    bits = b ** 3
+    dx, dy, dz = grid.dim
+    status = np.unpackbits(grid.array_view(L.BUF_BRICK_STATUS).view(np.uint8), bitorder="little")[:dx * dy * dz]
+    loaded = np.flatnonzero(status)
+    occupancy = grid.array_view(L.BUF_BRICK_OCCUPANCY).reshape(-1, bits // 8)
+    index = grid.array_view(L.BUF_BRICK_INDEX)
+    out = []
+    for k in range(0, n, chunk):
+        cells = loaded[rng.integers(0, len(loaded), min(chunk, n - k))]
+        solid = np.unpackbits(occupancy[index[cells]], axis=1, bitorder="little")
+        below = np.cumsum(solid, axis=1, dtype=np.uint16)                     # solid voxels up to and including each bit
+        pick = (rng.random(len(cells)) * below[:, -1]).astype(np.uint16)     # the pick-th solid voxel of the brick
+        nth = (below > pick[:, None]).argmax(axis=1)
+        wx, wz, wy = (cells % dx) * b + nth % b, ((cells // dx) % dz) * b + (nth // b) % b, (cells // (dx * dz)) * b + nth // (b * b)
+        out.append(np.stack([wx, dy * b - 1 - wy, wz], axis=1).astype(np.uint32))
+    return np.concatenate(out)
+
+
 def timed(fn):
     t0 = time.perf_counter()
     fn()
@@ -61,7 +88,54 @@ def frame_ms(rt):
     return timed(lambda: (rt.draw(), rt.wait()))
 
 
-def run_scene(name, sizes, reps):
+def removal_rows(name, w, grid, rt, host_rt, sizes, reps, plain_frame):
+    """The removal rows of one scene: as the insert rows, with the host grid built anew (not timed) before each of its runs."""
+    import torch
+    from zig_vulkan_amd import workloads as W
+    lib = rt._lib
+    b = grid.brick_dimension
+    vd = (grid.dim[0] * b, grid.dim[1] * b, grid.dim[2] * b)
+    rng = np.random.default_rng(11)
+    rows = []
+    for n in sizes:
+        for kind in ("random", "brush"):
+            rt._check(lib.vrt_upload_grid(rt._h, grid._h))
+            rt.wait()
+            if kind == "random":
+                xyz = solid_batch(rng, grid, n)
+            else:
+                xyz = brush_batch(rt, vd, n)[0]
+            txyz = torch.from_numpy(xyz.astype(np.int32)).cuda()
+            torch.cuda.synchronize()
+            dev_host, dev_dev, nxt = [], [], []
+            for _ in range(reps):
+                rt._check(lib.vrt_upload_grid(rt._h, grid._h))
+                rt.wait()
+                dev_host.append(timed(lambda: rt.remove_voxels(xyz)))
+                nxt.append(timed(lambda: (rt.draw(), rt.wait())))
+                rt._check(lib.vrt_upload_grid(rt._h, grid._h))
+                rt.wait()
+                dev_dev.append(timed(lambda: rt.remove_voxels(txyz)))
+            host = []
+            for _ in range(1 if n >= 1_000_000 else reps):
+                fresh = W.build_grid(w)
+                host_rt._check(lib.vrt_upload_grid(host_rt._h, fresh._h))
+                host_rt.wait()
+                host_rt.brick_grid = fresh
+                host.append(timed(lambda: (fresh.remove_many(xyz), host_rt.update_grid_delta(), host_rt.wait())))
+            row = dict(scene=name, op="remove", kind=kind, n=int(len(xyz)), device_host_mem=float(np.median(dev_host)),
+                       device_dev_mem=float(np.median(dev_dev)), host_path=float(np.median(host)), next_frame=float(np.median(nxt)),
+                       plain_frame=plain_frame, device_dev_mem_min=float(np.min(dev_dev)), device_dev_mem_max=float(np.max(dev_dev)),
+                       device_host_mem_min=float(np.min(dev_host)), device_host_mem_max=float(np.max(dev_host)))
+            row["speedup_dev_mem"] = row["host_path"] / row["device_dev_mem"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    rt._check(lib.vrt_upload_grid(rt._h, grid._h))
+    rt.wait()
+    return rows
+
+
+def run_scene(name, sizes, reps, ops=("insert",)):
     import torch
     w = W.WORKLOADS[SCENES[name]]
     grid = W.build_grid(w)
@@ -88,7 +162,7 @@ def run_scene(name, sizes, reps):
         scan.append(timed(rt.scene_bricks))
     rows = []
     plain_frame = float(np.median([frame_ms(rt) for _ in range(reps)]))
-    for n in sizes:
+    for n in sizes if "insert" in ops else ():
         for kind in ("random", "brush"):
             xyz, mats = random_batch(rng, vd, n) if kind == "random" else brush_batch(rt, vd, n)
             txyz, tm = torch.from_numpy(xyz.astype(np.int32)).cuda(), torch.from_numpy(mats).cuda()
@@ -105,11 +179,15 @@ def run_scene(name, sizes, reps):
             host = []
             for _ in range(1 if n >= 1_000_000 else reps):
                 host.append(timed(lambda: (host_grid.insert_many(xyz, mats), host_rt.update_grid_delta(), host_rt.wait())))
-            row = dict(scene=name, kind=kind, n=int(len(xyz)), device_host_mem=float(np.median(dev_host)), device_dev_mem=float(np.median(dev_dev)),
-                       host_path=float(np.median(host)), next_frame=float(np.median(nxt)), plain_frame=plain_frame)
+            row = dict(scene=name, op="insert", kind=kind, n=int(len(xyz)), device_host_mem=float(np.median(dev_host)), device_dev_mem=float(np.median(dev_dev)),
+                       host_path=float(np.median(host)), next_frame=float(np.median(nxt)), plain_frame=plain_frame,
+                       device_dev_mem_min=float(np.min(dev_dev)), device_dev_mem_max=float(np.max(dev_dev)),
+                       device_host_mem_min=float(np.min(dev_host)), device_host_mem_max=float(np.max(dev_host)))
             row["speedup_dev_mem"] = row["host_path"] / row["device_dev_mem"]
             rows.append(row)
             print(json.dumps(row), flush=True)
+    if "remove" in ops:
+        rows += removal_rows(name, w, grid, rt, host_rt, sizes, reps, plain_frame)
     for r in (rt, host_rt):
         r.deinit()
     return dict(scene=name, first_insert_scan_ms=float(np.median(scan)), bricks=int(grid.brick_alloc), rows=rows)
@@ -120,19 +198,20 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1000,100000,1000000,16000000")
     ap.add_argument("--scenes", default="headline,refapp")
+    ap.add_argument("--ops", default="insert,remove", help="insert, remove or both")
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",")]
-    res = [run_scene(s, sizes, a.reps) for s in a.scenes.split(",")]
+    res = [run_scene(s, sizes, a.reps, tuple(a.ops.split(","))) for s in a.scenes.split(",")]
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
-    print("| scene | batch | voxels | vrt_insert_voxels ms | _device ms | host path ms | speed-up | next frame ms (plain) |")
-    print("|---|---|---|---|---|---|---|---|")
+    print("| scene | op | batch | voxels | host memory ms | _device ms | host path ms | speed-up | next frame ms (plain) |")
+    print("|---|---|---|---|---|---|---|---|---|")
     for s in res:
         for r in s["rows"]:
-            print(f"| {r['scene']} | {r['kind']} | {r['n']:,} | {r['device_host_mem']:.3f} | {r['device_dev_mem']:.3f} | {r['host_path']:.1f} | "
+            print(f"| {r['scene']} | {r['op']} | {r['kind']} | {r['n']:,} | {r['device_host_mem']:.3f} | {r['device_dev_mem']:.3f} | {r['host_path']:.1f} | "
                   f"{r['speedup_dev_mem']:.0f}x | {r['next_frame']:.3f} ({r['plain_frame']:.3f}) |")
         print(f"first-insert scan of binding 5, {s['scene']} ({s['bricks']:,} entries): {s['first_insert_scan_ms']:.3f} ms")
 

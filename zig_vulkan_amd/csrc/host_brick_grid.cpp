@@ -141,6 +141,54 @@ int BrickGrid::insertImpl(uint64_t x, uint64_t y, uint64_t z, uint8_t material_i
 template int BrickGrid::insertImpl<true>(uint64_t, uint64_t, uint64_t, uint8_t);
 template int BrickGrid::insertImpl<false>(uint64_t, uint64_t, uint64_t, uint8_t);
 
+template <bool Locked>
+int BrickGrid::removeImpl(const uint32_t *xyz, uint64_t n) {
+    const vrt_grid_state &d = device_state_;
+    for (uint64_t i = 0; i < n; i++) // all or nothing: no bit is cleared before every voxel is known to lie inside the grid
+        if (xyz[3 * i] >= d.voxel_dim_x || xyz[3 * i + 1] >= d.voxel_dim_y || xyz[3 * i + 2] >= d.voxel_dim_z) return VRT_E_OUT_OF_RANGE;
+    const uint32_t b = brick_dimension_;
+    auto reg = [](DeviceDataDelta &dd, size_t i) {
+        if (Locked) dd.registerDelta(i);
+        else dd.registerDeltaUnlocked(i);
+    };
+    std::vector<size_t> touched; // the loaded cells that hold a voxel of the batch (runs of one cell once)
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t x = xyz[3 * i], z = xyz[3 * i + 2];
+        const uint32_t flipped_y = d.voxel_dim_y - 1 - xyz[3 * i + 1]; // Grid.zig:135
+        const size_t grid_index = (size_t)(x / b) + (size_t)d.dim_x * ((size_t)(z / b) + (size_t)d.dim_z * (size_t)(flipped_y / b)); // gridAt
+        if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue; // not loaded: a no-op
+        if (touched.empty() || touched.back() != grid_index) touched.push_back(grid_index);
+        const uint32_t nth_bit = (x % b) + b * ((z % b) + b * (flipped_y % b)); // voxelAt
+        const size_t byte = (size_t)brick_indices[grid_index] * brick_bytes_ + nth_bit / 8;
+        const uint8_t mask = (uint8_t)(1u << (nth_bit % 8));
+        if (!(brick_occupancy[byte] & mask)) continue; // already empty: a no-op
+        brick_occupancy[byte] &= (uint8_t)~mask;
+        reg(bricks_occupancy_delta, byte);
+    }
+    // after the whole batch (so the result does not depend on its order, also where two cells name one brick)
+    for (const size_t grid_index : touched) {
+        const uint32_t bit = 1u << (grid_index % 32);
+        if (!(brick_statuses[grid_index / 32] & bit)) continue; // (the cell came up twice)
+        const uint8_t *occ = &brick_occupancy[(size_t)brick_indices[grid_index] * brick_bytes_];
+        bool any = false;
+        for (uint32_t k = 0; k < brick_bytes_ && !any; k++) any = occ[k] != 0;
+        if (any) continue;
+        brick_statuses[grid_index / 32] &= ~bit;
+        reg(brick_statuses_delta, grid_index / 32);
+    }
+    return VRT_OK;
+}
+
+template int BrickGrid::removeImpl<true>(const uint32_t *, uint64_t);
+template int BrickGrid::removeImpl<false>(const uint32_t *, uint64_t);
+
+int BrickGrid::remove(uint64_t x, uint64_t y, uint64_t z) {
+    const vrt_grid_state &d = device_state_;
+    if (x >= d.voxel_dim_x || y >= d.voxel_dim_y || z >= d.voxel_dim_z) return VRT_E_OUT_OF_RANGE;
+    const uint32_t xyz[3] = {(uint32_t)x, (uint32_t)y, (uint32_t)z};
+    return removeImpl<true>(xyz, 1);
+}
+
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {
     switch (id) {
         case VRT_BUF_BRICK_STATUS: return &brick_statuses_delta;

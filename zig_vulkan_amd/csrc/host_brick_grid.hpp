@@ -54,6 +54,16 @@ public:
     // single-threaded bulk path: identical results, no per-delta locking
     int insertUnlocked(uint64_t x, uint64_t y, uint64_t z, uint8_t material_index) { return insertImpl<false>(x, y, z, material_index); }
 
+    // Removal of a batch of voxels (the reference has none: include/vrt_hip.h defines it).  Coordinates as insert takes them.  All or
+    // nothing: a voxel outside the grid is VRT_E_OUT_OF_RANGE and nothing changes.  A voxel of a cell that is not loaded, or whose
+    // occupancy bit is 0, is a no-op; every other voxel loses its occupancy bit (no byte of material_indices is written).  After the
+    // whole batch, every loaded cell that holds a voxel of it and whose brick has no occupancy bit left loses its status bit.
+    // brick_indices, brick_start_indices, active_bricks and the material cursor stay: the brick is NOT reused, a later insert into
+    // the cell takes a fresh one.  Deltas: the occupancy bytes and status words that lost a bit, no other.
+    int remove(uint64_t x, uint64_t y, uint64_t z);
+    // single-threaded bulk path: identical results, no per-delta locking
+    int removeManyUnlocked(const uint32_t *xyz, uint64_t n) { return removeImpl<false>(xyz, n); }
+
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }
     uint32_t brickBits() const { return brick_bits_; }
@@ -79,6 +89,8 @@ private:
     BrickGrid() = default;
     template <bool Locked>
     int insertImpl(uint64_t x, uint64_t y, uint64_t z, uint8_t material_index);
+    template <bool Locked>
+    int removeImpl(const uint32_t *xyz, uint64_t n);
 
     uint32_t brick_dimension_ = 4, brick_bits_ = 64, brick_bytes_ = 8;
     uint64_t brick_alloc_ = 0;

@@ -245,6 +245,16 @@ int vrt_grid_insert_many(vrt_grid *gh, const uint32_t *xyz, const uint8_t *mater
     return VRT_OK;
 }
 
+int vrt_grid_remove(vrt_grid *g, uint64_t x, uint64_t y, uint64_t z) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->remove(x, y, z);
+}
+
+int vrt_grid_remove_many(vrt_grid *g, const uint32_t *xyz, uint64_t n) {
+    if (!g || (n && !xyz)) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->removeManyUnlocked(xyz, n);
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

@@ -229,7 +229,7 @@ struct vrt_ctx {
     uint32_t *d_edit_voxels = nullptr;                       // [4][edit_capacity] per-voxel scratch
     uint32_t *d_edit_groups = nullptr;                       // [edit_capacity / 256]
     void *d_edit_table = nullptr;                            // [edit_table_entries] {key, value} pairs
-    uint8_t *d_edit_input = nullptr;                         // vrt_insert_voxels: the batch staged into device memory
+    uint8_t *d_edit_input = nullptr;                         // vrt_insert_voxels / vrt_remove_voxels: the batch staged into device memory
     uint64_t edit_capacity = 0, edit_table_entries = 0, edit_input_bytes = 0;
     size_t lds_bytes = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;

@@ -1,5 +1,6 @@
-// vrt_edit.hip — batched voxel inserts behind the C ABI (vrt_insert_voxels, vrt_insert_voxels_device), the allocation state they
-// continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels vrt_edit_* and their host side.
+// vrt_edit.hip — batched voxel inserts and removals behind the C ABI (vrt_insert_voxels, vrt_remove_voxels and their _device forms),
+// the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels
+// vrt_edit_* and their host side.
 // BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
 // vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
 // instructions.  "Binding k" below is buffer id k of vrt_buffer_id (binding 5 = VRT_BUF_BRICK_START_INDEX), as in include/vrt_hip.h's
@@ -19,6 +20,16 @@
 //   vrt_edit_write        the scene's bytes, and the written ranges
 //   vrt_edit_finish       A and the cursor move on; the status the host reads back
 // Every kernel after vrt_edit_validate reads the error word first and writes no scene byte when it is set.
+//
+// A removal batch (vrt_grid_remove_many for the batch) is a mode of the same kernels, EditArgs::op = kEditOpRemove:
+//   vrt_edit_begin (+ the scan of binding 5, as above)
+//   vrt_edit_validate     per voxel: range, cell, voxel within the brick; loaded cells: brick, and atomicMin of the voxel's index into
+//                         the cell's scratch word (one voxel elected per touched loaded cell); others: no-ops
+//   vrt_edit_write        phase 0: the occupancy bit cleared (atomicAnd on the word); the range of bytes that lost a bit
+//   vrt_edit_write        phase 1 (a kernel boundary after every clear): the elected voxel of each cell reads its brick's occupancy
+//                         words and, if none is set, clears the cell's status bit; the range of those cells
+//   vrt_edit_table        clears the cells' scratch words
+//   vrt_edit_finish
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -31,6 +42,7 @@ namespace vrt {
 constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
+constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1; // EditArgs::op
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
 constexpr uint32_t kEditErrShape = 1u << 0;  // binding 5 is not allocation-shaped                       -> VRT_E_STATE
@@ -57,8 +69,8 @@ struct EditStatus {
     uint32_t bricks;        // allocated bricks after the batch (before it if err != 0)
     uint32_t ok;            // the state's shape flag
     uint64_t cursor;        // next material entry after the batch
-    uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries)
-    uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit
+    uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries); removal: unloaded
+    uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit; removal: that lost one
     uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
 };
 
@@ -75,8 +87,10 @@ struct EditArgs {
     uint32_t n;
     uint32_t groups;         // ceil(n / kEditBlock)
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
+    uint32_t op;             // kEditOpInsert / kEditOpRemove (uniform: every kernel of a chain sees the same)
+    uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks
     // scratch (the context's, grown on demand)
-    uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded; kEditNone between batches
+    uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded (removal: that is loaded); kEditNone between batches
     uint32_t *vcell;         // [n] the voxel's cell (kEditNone: not written)
     uint32_t *vinfo;         // [n] bit 31: cell not loaded, bit 30: first voxel of that cell, bits 0-8: voxel within the brick
     uint32_t *vbrick;        // [n] brick index
@@ -218,7 +232,20 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
             const uint32_t fy = a.voxel_dim_y - 1u - y; // Grid.zig:135
             const uint32_t g = (uint32_t)((uint64_t)(x / a.b) + (uint64_t)a.dim_x * ((uint64_t)(z / a.b) + (uint64_t)a.dim_z * (fy / a.b))); // gridAt
             const uint32_t nth = x % a.b + a.b * (z % a.b + a.b * (fy % a.b));                                                            // voxelAt
-            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
+            const bool loaded = (a.status[g >> 5] >> (g & 31u)) & 1u;
+            if (a.op == kEditOpRemove) {
+                if (loaded) { // (a cell that is not loaded: a no-op, cell stays kEditNone)
+                    const uint32_t brick = a.index[g];
+                    if (brick >= bricks) {
+                        err = kEditErrCell;
+                    } else {
+                        a.vbrick[i] = brick;
+                        atomicMin(&a.cell_first[g], i); // the cell's elected voxel: it looks at the brick once every bit is cleared
+                        cell = g;
+                        info = nth;
+                    }
+                }
+            } else if (loaded) {
                 const uint32_t brick = a.index[g];
                 if (brick >= bricks) {
                     err = kEditErrCell;
@@ -320,6 +347,10 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     if (i >= a.n) return;
     const uint32_t cell = a.vcell[i];
+    if (a.op == kEditOpRemove) { // (removal used the words of the loaded cells it touched, and needs no last writer)
+        if (cell != kEditNone) a.cell_first[cell] = kEditNone;
+        return;
+    }
     if (a.vinfo[i] & 0x80000000u) a.cell_first[cell] = kEditNone; // (whatever the error word says: the scratch is clean for the next batch)
     if (a.out->err || cell == kEditNone) return;
     const uint32_t key = a.vslot[i] + 1u;
@@ -334,8 +365,42 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
     }
 }
 
+// removal's two passes over the batch (every lane of the wave gets here: the wave reductions see every lane)
+__device__ inline void remove_write(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
+    uint32_t lo = kEditNone, hi = 0;
+    if (a.phase == 0) {
+        if (cell != kEditNone) {
+            const uint32_t nth = a.vinfo[i] & 0x1FFu;
+            const uint32_t byte = a.vbrick[i] * a.brick_bytes + (nth >> 3);
+            const uint32_t bit = 1u << ((byte & 3u) * 8u + (nth & 7u));
+            if (atomicAnd(&a.occupancy[byte >> 2], ~bit) & bit) lo = hi = byte; // (of duplicates, one finds the bit set)
+        }
+        wave_atomic_min(&a.out->occ_lo, lo);
+        wave_atomic_max(&a.out->occ_hi, hi);
+        return;
+    }
+    if (cell != kEditNone && a.cell_first[cell] == i) {
+        const uint32_t words = a.brick_bytes >> 2; // 2 or 16
+        const uint32_t *occ = a.occupancy + (uint64_t)a.vbrick[i] * words;
+        uint32_t any = 0;
+        for (uint32_t w = 0; w < words; w++) any |= occ[w];
+        if (any == 0) { // (the status bit was set when the batch began, and only elected voxels clear bits: the cell becomes unloaded)
+            atomicAnd(&a.status[cell >> 5], ~(1u << (cell & 31u)));
+            lo = hi = cell;
+        }
+    }
+    wave_atomic_min(&a.out->cell_lo, lo);
+    wave_atomic_max(&a.out->cell_hi, hi);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     if (a.out->err) return;
+    if (a.op == kEditOpRemove) {
+        remove_write(a);
+        return;
+    }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     uint32_t cell_lo = kEditNone, cell_hi = 0, occ_lo = kEditNone, occ_hi = 0, mat_lo = kEditNone, mat_hi = 0;
     const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
@@ -390,8 +455,8 @@ namespace {
 
 // what every entry point checks before it touches the device: the scene is there, this context may edit it, and the small
 // buffers of the allocation state exist
-int edit_prepare(vrt_ctx *ctx) {
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, "voxel inserts are not available on a context of the multi-GPU pipeline");
+int edit_prepare(vrt_ctx *ctx, const char *what = "inserts") {
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, std::string("voxel ") + what + " are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
     if (!ctx->d_edit_state) {
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_state, sizeof(vrt::EditState)));
@@ -402,9 +467,9 @@ int edit_prepare(vrt_ctx *ctx) {
 }
 
 // scratch for a batch of n voxels: the per-cell words (once, all 0xFFFFFFFF; every batch leaves them so), the per-voxel words, the
-// per-workgroup counts and the last-writer table (a power of two of at least 2n entries).  No kernel of an earlier batch is in flight:
-// every batch ends with a wait for its status.
-int edit_scratch(vrt_ctx *ctx, uint64_t n) {
+// per-workgroup counts and the last-writer table (a power of two of at least 2n entries; inserts only).  No kernel of an earlier batch
+// is in flight: every batch ends with a wait for its status.
+int edit_scratch(vrt_ctx *ctx, uint64_t n, bool with_table = true) {
     if (!ctx->d_edit_cell_first) {
         const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_cell_first, cells * sizeof(uint32_t)));
@@ -419,6 +484,7 @@ int edit_scratch(vrt_ctx *ctx, uint64_t n) {
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_groups, cap / vrt::kEditBlock * sizeof(uint32_t)));
         ctx->edit_capacity = cap;
     }
+    if (!with_table) return VRT_OK;
     uint64_t entries = 1024;
     while (entries < 2u * n) entries <<= 1;
     if (ctx->edit_table_entries < entries) {
@@ -513,6 +579,7 @@ int insert(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t
     rc = begin_scene_write(ctx);
     if (rc != VRT_OK) return rc;
     vrt::EditArgs a = edit_args(ctx, xyz, materials, (uint32_t)n, !ctx->edit_state_valid);
+    a.op = vrt::kEditOpInsert;
     const uint32_t groups = a.groups;
     VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
     rc = launch_state(ctx, a);
@@ -552,6 +619,43 @@ int insert(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t
         ctx->edit_state_valid = true; // (the device state already counts these bricks: this write is the inserts' own)
     }
     if (s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    return VRT_OK;
+}
+
+// n voxels at xyz (device memory) out of the scene: removal's subset of the chain, as one scene write
+int remove(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
+    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
+    int rc = edit_scratch(ctx, n, false);
+    if (rc != VRT_OK) return rc;
+    rc = begin_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, xyz, nullptr, (uint32_t)n, !ctx->edit_state_valid);
+    a.op = vrt::kEditOpRemove;
+    const uint32_t groups = a.groups;
+    rc = launch_state(ctx, a);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+    a.phase = 1;
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
+    if (rc != VRT_OK) {
+        (void)wait_stream(ctx->stream);
+        ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
+        ctx->edit_state_valid = false;
+        return rc;
+    }
+    rc = end_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditStatus s;
+    rc = read_status(ctx, a, &s);
+    if (rc != VRT_OK) return rc;
+    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
+    if (s.err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, "a voxel lies outside the grid; nothing was removed");
+    if (s.err & vrt::kEditErrCell)
+        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5); nothing was removed");
+    // exactly what lost a bit: the status words of the cells that became unloaded, the occupancy bytes (a batch of no-ops: nothing)
+    if (s.cell_lo <= s.cell_hi) mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
+    if (s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
     return VRT_OK;
 }
 
@@ -596,6 +700,38 @@ int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *material
     if (rc == VRT_OK) rc = staged_copy_h2d(ctx, ctx->d_edit_input + xyz_bytes, materials, n);
     if (rc != VRT_OK) return rc;
     return insert(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), ctx->d_edit_input + xyz_bytes, n);
+}
+
+int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
+    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
+    DeviceGuard dg(ctx->device);
+    const int rc = edit_prepare(ctx, "removals");
+    if (rc != VRT_OK) return rc;
+    return remove(ctx, xyz, n);
+}
+
+int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
+    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
+    DeviceGuard dg(ctx->device);
+    int rc = edit_prepare(ctx, "removals");
+    if (rc != VRT_OK) return rc;
+    // the batch into device memory through the pinned staging slots
+    const uint64_t bytes = 12u * n;
+    if (ctx->edit_input_bytes < bytes) {
+        ctx->res.drop(ctx->d_edit_input);
+        ctx->edit_input_bytes = 0;
+        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_input, bytes));
+        ctx->edit_input_bytes = bytes;
+    }
+    rc = staged_copy_h2d(ctx, ctx->d_edit_input, xyz, bytes);
+    if (rc != VRT_OK) return rc;
+    return remove(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), n);
 }
 
 int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]) {

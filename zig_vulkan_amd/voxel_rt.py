@@ -71,6 +71,15 @@ class BrickGrid:
         assert xyz.shape[0] == materials.shape[0]
         check(lib.vrt_grid_insert_many(self._h, xyz.ctypes.data, materials.ctypes.data, xyz.shape[0]))
 
+    def remove(self, x: int, y: int, z: int) -> None:
+        """vrt_grid_remove: the batch of one of remove_many."""
+        check(lib.vrt_grid_remove(self._h, x, y, z))
+
+    def remove_many(self, xyz: np.ndarray) -> None:
+        """vrt_grid_remove_many: xyz (n, 3) as insert_many takes it; all or nothing.  Emptied bricks are not reused."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
+        check(lib.vrt_grid_remove_many(self._h, xyz.ctypes.data, xyz.shape[0]))
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -353,6 +362,19 @@ class VoxelRT:
         m = np.ascontiguousarray(materials, dtype=np.uint8).reshape(-1)
         assert x.shape[0] == m.shape[0]
         self._check(self._lib.vrt_insert_voxels(self._h, x.ctypes.data, m.ctypes.data, x.shape[0]))
+
+    def remove_voxels(self, xyz) -> None:
+        """BrickGrid.remove_many for a batch on the scene the context holds (vrt_remove_voxels): xyz (n, 3) as BrickGrid.remove_many
+        takes it, all or nothing.  Given a torch tensor on the GPU, the batch is read in device memory (vrt_remove_voxels_device, behind
+        torch's current stream)."""
+        if getattr(xyz, "is_cuda", False):
+            import torch
+            x = xyz.reshape(-1, 3).to(torch.int32).contiguous()
+            torch.cuda.current_stream(x.device).synchronize()  # (the batch is written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_remove_voxels_device(self._h, x.data_ptr(), x.shape[0]))
+            return
+        x = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
+        self._check(self._lib.vrt_remove_voxels(self._h, x.ctypes.data, x.shape[0]))
 
     def read_buffer(self, buf_id: int) -> np.ndarray:
         """Copy of scene buffer `buf_id` as frames see it now (vrt_read_buffer), typed: uint32 words for bindings 2, 3 and 5, bytes for
