@@ -225,7 +225,8 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
     const uint32_t bricks = a.state->bricks;
     uint32_t cell = kEditNone, info = 0, err = 0;
     if (i < a.n && ok) {
-        const uint32_t x = a.xyz[3u * i], y = a.xyz[3u * i + 1u], z = a.xyz[3u * i + 2u];
+        const uint32_t *p = a.xyz + 3ull * i; // (64-bit: 3 i passes 2^32 from i = 1 431 655 766, and a batch holds up to 2^31 - 1 voxels)
+        const uint32_t x = p[0], y = p[1], z = p[2];
         if (x >= a.voxel_dim_x || y >= a.voxel_dim_y || z >= a.voxel_dim_z) {
             err = kEditErrRange; // Grid.zig:130-132
         } else {
