@@ -321,6 +321,7 @@ pub extern fn vrt_grid_insert(g: ?*Grid, x: u64, y: u64, z: u64, material_index:
 pub extern fn vrt_grid_insert_many(g: ?*Grid, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_grid_remove_many(g: ?*Grid, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_grid_remove(g: ?*Grid, x: u64, y: u64, z: u64) c_int;
+pub extern fn vrt_grid_compact(g: ?*Grid, out: *[2]u32) c_int;
 pub extern fn vrt_grid_device_state(g: ?*const Grid) [*c]const GridState;
 pub extern fn vrt_grid_data(g: ?*const Grid, id: BufferId, nbytes: [*c]u64) ?*const anyopaque;
 pub extern fn vrt_grid_active_bricks(g: ?*const Grid) u32;
@@ -335,6 +336,7 @@ pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]c
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_remove_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
+pub extern fn vrt_compact_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_camera_pixel_ray(cam: [*c]const CameraDevice, px: u32, py: u32, origin: *[3]f32, direction: *[3]f32) c_int;

@@ -445,6 +445,18 @@ int vrt_grid_insert_many(vrt_grid *g, const uint32_t *xyz, const uint8_t *materi
 int vrt_grid_remove_many(vrt_grid *g, const uint32_t *xyz, uint64_t n);
 /* the batch of one */
 int vrt_grid_remove(vrt_grid *g, uint64_t x, uint64_t y, uint64_t z);
+/* Compaction: the dead bricks give their slots back (the reference has none).  With A = vrt_grid_active_bricks, B^3 voxels and
+ * bb = B^3 / 8 occupancy bytes per brick: brick b < A is LIVE when a loaded cell (status bit 1) names it, L is the number of live
+ * bricks.  FILL THE HOLES FROM THE TAIL: the live bricks at or beyond L, ascending, move to the dead slots below L, ascending — the
+ * bb occupancy bytes, the B^3 material bytes, and brick_indices of every loaded cell that names the brick; live bricks below L stay
+ * (sources and destinations are disjoint, and no compaction copies fewer bytes).  Afterwards occupancy bytes [L bb, A bb) are 0,
+ * brick_start_indices[L, A) are 0xFFFFFFFF (entries [0, L) keep slot * B^3), active_bricks is L and the next material entry L B^3, so
+ * inserts continue from there.  Never written: material bytes at or beyond L B^3, brick_indices of cells that are not loaded, status
+ * words.  L == A: VRT_OK, nothing written.  VRT_E_STATE, nothing changed: brick_start_indices is not allocation-shaped (see
+ * vrt_insert_voxels), an entry below A is not slot * B^3 (every grid built by vrt_grid_insert* or vrt_insert_voxels has that form),
+ * or a loaded cell names a brick >= A.  out (may be NULL) = {A, L}, on success.  Deltas: per array, the first to the last element
+ * whose value changed; inactive where none did. */
+int vrt_grid_compact(vrt_grid *g, uint32_t out[2]);
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g);
 /* Borrowed pointer + byte size of host array `id` (GRID_STATE..MATERIAL_INDEX;
  * MATERIALS is not part of the grid => NULL). */
@@ -545,6 +557,15 @@ int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *m
 int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
 /* xyz in device memory, ordered after every earlier write on the context's stream */
 int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
+/* ---- Brick compaction on the uploaded scene ------------------------------------------------------------------------------
+ * vrt_grid_compact on the GPU: on a context whose bindings 2-6 equal a vrt_grid's arrays, after vrt_compact_bricks(ctx, out) they
+ * equal that grid's arrays after vrt_grid_compact(g, out), byte for byte; vrt_scene_bricks then reports {L, L B^3} and
+ * vrt_insert_voxels continues from there, so a host that digs and fills without end no longer runs into VRT_E_OOM.  No frame changes
+ * by a bit.  Errors and ordering as for vrt_remove_voxels: one scene write on the context's stream, a refused call changes no scene
+ * byte, one small status read-back ends the call; VRT_E_STATE for vrt_grid_compact's three preconditions, for a context without a
+ * grid state and for one of the multi-GPU pipeline.  out (may be NULL) = {A, L}, on success.  The derived structures are refreshed for
+ * the written ranges (the renamed cells, the filled holes, the cleared tail) before the next frame or query. */
+int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]);
 /* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Batched voxel inserts and removals on the GPU (vrt_insert_voxels, vrt_remove_voxels and their _device forms) against the host
-paths they replace (vrt_grid_insert_many / vrt_grid_remove_many + vrt_update_grid_delta), end to end, on the headline scene (512^3
-voxels in 8^3 bricks, terrain) and the reference app's scene (128 x 64 x 128 bricks of 4^3, terrain).  DESIGN.md §11 and §12 give
-the tables.
+"""Batched voxel inserts and removals and brick compaction on the GPU (vrt_insert_voxels, vrt_remove_voxels and their _device forms,
+vrt_compact_bricks) against the host paths they replace (vrt_grid_insert_many / vrt_grid_remove_many / vrt_grid_compact +
+vrt_update_grid_delta), end to end, on the headline scene (512^3 voxels in 8^3 bricks, terrain) and the reference app's scene
+(128 x 64 x 128 bricks of 4^3, terrain).  DESIGN.md §11, §12 and §13 give the tables.
 
 Per scene and batch size (10^3, 10^5, 10^6, 1.6 x 10^7 voxels) two kinds of batch: random voxels over the grid, and a brush — a solid
 sphere around the hit of the camera's centre ray.  Reported, in ms (median of --reps for the device paths, one run of the host path
@@ -17,7 +17,13 @@ scene as uploaded (vrt_upload_grid between runs, not timed); the host grid takes
 Removal rows (--ops insert,remove; op "remove" in a row): random SOLID voxels of the scene, and the same brush as a dig.  The host grid
 is built anew before each of its runs (not timed), so every run removes solid voxels; otherwise the rows read as the insert rows do.
 
-    python tools/edit_bench.py [--reps 5] [--sizes 1000,100000,1000000,16000000] [--ops insert,remove] [--out results.json]
+Compaction rows (--ops compact; op "compact" in a row): after a dig that empties 1 %, 10 % and 50 % of the scene's
+bricks (random loaded cells; their occupancy records zeroed and status bits cleared in the host grid, as vrt_grid_remove_many of all
+their voxels leaves them, then uploaded), vrt_compact_bricks until it returns (both device columns hold it: there is no batch), against
+vrt_grid_compact on the host grid + vrt_update_grid_delta into a second context until its stream is idle (one run), with the next
+frame's time.  "voxels" is the number of bricks given back.
+
+    python tools/edit_bench.py [--reps 5] [--sizes 1000,100000,1000000,16000000] [--ops insert,remove,compact] [--out results.json]
 Kernel times: a run of its own under `rocprofv3 --kernel-trace --stats` (e.g. with --sizes 1000000 --reps 3)."""
 import argparse
 import json
@@ -135,6 +141,56 @@ def removal_rows(name, w, grid, rt, host_rt, sizes, reps, plain_frame):
     return rows
 
 
+def dig_out(grid, cells):
+    """The cells' bricks emptied as vrt_grid_remove_many of all their voxels leaves them: occupancy records zero, status bits cleared."""
+    from zig_vulkan_amd import _lib as L
+    bits = grid.brick_dimension ** 3
+    grid.array_view(L.BUF_BRICK_OCCUPANCY).reshape(-1, bits // 8)[grid.array_view(L.BUF_BRICK_INDEX)[cells]] = 0
+    np.bitwise_and.at(grid.array_view(L.BUF_BRICK_STATUS), cells >> 5, (0xFFFFFFFF ^ (1 << (cells & 31))).astype(np.uint32))
+
+
+def compaction_rows(name, w, grid, rt, host_rt, reps, plain_frame):
+    """The compaction rows of one scene: a grid built anew per row, dug, compacted `reps` times on the device (uploaded again in
+    between, with a frame so that the derived structures are those of the dug scene; not timed) and once on the host."""
+    from zig_vulkan_amd import _lib as L
+    from zig_vulkan_amd import workloads as W
+    lib = rt._lib
+    rng = np.random.default_rng(13)
+    rt.compact_bricks()   # (warm-up: the scratch for brick_alloc bricks is made; no brick of the scene as built is dead)
+    rows = []
+    for fraction in (0.01, 0.10, 0.50):
+        dug = W.build_grid(w)
+        dx, dy, dz = dug.dim
+        loaded = np.flatnonzero(np.unpackbits(dug.array_view(L.BUF_BRICK_STATUS).view(np.uint8), bitorder="little")[:dx * dy * dz])
+        dig_out(dug, rng.choice(loaded, int(fraction * dug.active_bricks), replace=False))
+        dev, nxt, freed = [], [], 0
+        for _ in range(reps):
+            rt._check(lib.vrt_upload_grid(rt._h, dug._h))
+            rt.draw()
+            rt.wait()
+            t0 = time.perf_counter()
+            before, after = rt.compact_bricks()
+            dev.append((time.perf_counter() - t0) * 1e3)
+            nxt.append(timed(lambda: (rt.draw(), rt.wait())))
+            freed = before - after
+        host_rt._check(lib.vrt_upload_grid(host_rt._h, dug._h))
+        host_rt.brick_grid = dug
+        host_rt.draw()
+        host_rt.wait()
+        host = timed(lambda: (dug.compact(), host_rt.update_grid_delta(), host_rt.wait()))
+        host_frame = timed(lambda: (host_rt.draw(), host_rt.wait()))
+        row = dict(scene=name, op="compact", kind=f"dig {fraction:.0%}", n=int(freed), device_host_mem=float(np.median(dev)),
+                   device_dev_mem=float(np.median(dev)), host_path=float(host), next_frame=float(np.median(nxt)), plain_frame=plain_frame,
+                   device_dev_mem_min=float(np.min(dev)), device_dev_mem_max=float(np.max(dev)), device_host_mem_min=float(np.min(dev)),
+                   device_host_mem_max=float(np.max(dev)), host_next_frame=float(host_frame), bricks_before=int(before))
+        row["speedup_dev_mem"] = row["host_path"] / row["device_dev_mem"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    rt._check(lib.vrt_upload_grid(rt._h, grid._h))
+    rt.wait()
+    return rows
+
+
 def run_scene(name, sizes, reps, ops=("insert",)):
     import torch
     w = W.WORKLOADS[SCENES[name]]
@@ -188,6 +244,8 @@ def run_scene(name, sizes, reps, ops=("insert",)):
             print(json.dumps(row), flush=True)
     if "remove" in ops:
         rows += removal_rows(name, w, grid, rt, host_rt, sizes, reps, plain_frame)
+    if "compact" in ops:
+        rows += compaction_rows(name, w, grid, rt, host_rt, reps, plain_frame)
     for r in (rt, host_rt):
         r.deinit()
     return dict(scene=name, first_insert_scan_ms=float(np.median(scan)), bricks=int(grid.brick_alloc), rows=rows)
@@ -198,7 +256,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1000,100000,1000000,16000000")
     ap.add_argument("--scenes", default="headline,refapp")
-    ap.add_argument("--ops", default="insert,remove", help="insert, remove or both")
+    ap.add_argument("--ops", default="insert,remove", help="any of insert, remove, compact")
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",")]

@@ -225,6 +225,7 @@ SIGNATURES = {
     "vrt_grid_insert_many": (C.c_int, [_grid, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_grid_remove": (C.c_int, [_grid, C.c_uint64, C.c_uint64, C.c_uint64]),
     "vrt_grid_remove_many": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
+    "vrt_grid_compact": (C.c_int, [_grid, _P(C.c_uint32 * 2)]),
     "vrt_grid_device_state": (_P(GridState), [_grid]),
     "vrt_grid_data": (C.c_void_p, [_grid, C.c_int, _P(C.c_uint64)]),
     "vrt_grid_active_bricks": (C.c_uint32, [_grid]),
@@ -241,6 +242,7 @@ SIGNATURES = {
     "vrt_remove_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
     "vrt_read_buffer": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_scene_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
+    "vrt_compact_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
     "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),
     "vrt_camera_set_forward": (C.c_int, [_P(CameraDevice), C.c_float, C.c_float, _P(C.c_float * 3)]),

@@ -189,6 +189,53 @@ int BrickGrid::remove(uint64_t x, uint64_t y, uint64_t z) {
     return removeImpl<true>(xyz, 1);
 }
 
+int BrickGrid::compact(uint32_t out[2]) {
+    const uint32_t a = activeBricks(), bits = brick_bits_, bb = brick_bytes_;
+    const uint64_t cells = brick_indices.size();
+    // the preconditions, before the first write
+    if (a > brick_alloc_) return VRT_E_STATE;
+    for (uint64_t b = 0; b < brick_alloc_; b++)
+        if (brick_start_indices[b] != (b < a ? (uint32_t)(b * bits) : 0xFFFFFFFFu)) return VRT_E_STATE; // (a type bit is a mismatch too)
+    std::vector<uint8_t> live(a, 0);
+    for (uint64_t cell = 0; cell < cells; cell++) {
+        if (!((brick_statuses[cell / 32] >> (cell % 32)) & 1u)) continue;
+        if (brick_indices[cell] >= a) return VRT_E_STATE;
+        live[brick_indices[cell]] = 1;
+    }
+    uint32_t l = 0;
+    for (uint32_t b = 0; b < a; b++) l += live[b];
+    if (out) out[0] = a, out[1] = l;
+    if (l == a) return VRT_OK;
+
+    // a byte that takes another value, and its delta
+    auto put = [](std::vector<uint8_t> &v, DeviceDataDelta &dd, size_t i, uint8_t value) {
+        if (v[i] == value) return;
+        v[i] = value;
+        dd.registerDeltaUnlocked(i);
+    };
+    // fill the holes from the tail: the j-th live brick at or beyond L into the j-th dead slot below L
+    std::vector<uint32_t> remap(a, 0xFFFFFFFFu);
+    uint32_t hole = 0;
+    for (uint32_t t = l; t < a; t++) {
+        if (!live[t]) continue;
+        while (live[hole]) hole++; // (as many dead slots below L as live bricks beyond it)
+        for (uint32_t k = 0; k < bb; k++) put(brick_occupancy, bricks_occupancy_delta, (size_t)hole * bb + k, brick_occupancy[(size_t)t * bb + k]);
+        for (uint32_t k = 0; k < bits; k++) put(material_indices, material_indices_delta, (size_t)hole * bits + k, material_indices[(size_t)t * bits + k]);
+        remap[t] = hole++;
+    }
+    for (uint64_t cell = 0; cell < cells; cell++) {
+        if (!((brick_statuses[cell / 32] >> (cell % 32)) & 1u) || brick_indices[cell] < l) continue;
+        brick_indices[cell] = remap[brick_indices[cell]];
+        brick_indices_delta.registerDeltaUnlocked((size_t)cell);
+    }
+    for (size_t i = (size_t)l * bb; i < (size_t)a * bb; i++) put(brick_occupancy, bricks_occupancy_delta, i, 0);
+    for (uint32_t b = l; b < a; b++) brick_start_indices[b] = 0xFFFFFFFFu;
+    bricks_start_indices_delta.registerDeltaRange(l, a - 1u);
+    active_bricks_.store(l, std::memory_order_relaxed);
+    material_cursor_.store(l * bits, std::memory_order_relaxed);
+    return VRT_OK;
+}
+
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {
     switch (id) {
         case VRT_BUF_BRICK_STATUS: return &brick_statuses_delta;

@@ -64,6 +64,14 @@ public:
     // single-threaded bulk path: identical results, no per-delta locking
     int removeManyUnlocked(const uint32_t *xyz, uint64_t n) { return removeImpl<false>(xyz, n); }
 
+    // Compaction (the reference has none: include/vrt_hip.h defines it).  A brick below active_bricks is live when a loaded cell names
+    // it.  The live bricks at or beyond L (the number of live ones) move, in ascending order, into the dead slots below L, in ascending
+    // order: occupancy record, material entries, and the brick index of every loaded cell that names them.  Afterwards occupancy bytes
+    // [L bb, A bb) are 0, brick_start_indices[L, A) are unset, active_bricks is L and the material cursor L B^3.  VRT_E_STATE, with
+    // nothing changed: brick_start_indices not allocation-shaped, a start that is not slot * B^3, a loaded cell naming a brick >= A.
+    // out (may be null) = {A, L}.  Deltas: per array, the first to the last element whose value changed.  Single-threaded.
+    int compact(uint32_t out[2]);
+
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }
     uint32_t brickBits() const { return brick_bits_; }

@@ -255,6 +255,11 @@ int vrt_grid_remove_many(vrt_grid *g, const uint32_t *xyz, uint64_t n) {
     return reinterpret_cast<vrt::BrickGrid *>(g)->removeManyUnlocked(xyz, n);
 }
 
+int vrt_grid_compact(vrt_grid *g, uint32_t out[2]) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->compact(out);
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

@@ -1,5 +1,6 @@
 // vrt_edit.hip — batched voxel inserts and removals behind the C ABI (vrt_insert_voxels, vrt_remove_voxels and their _device forms),
-// the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels
+// brick compaction (vrt_compact_bricks), the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene
+// buffer (vrt_read_buffer): their kernels
 // vrt_edit_* and their host side.
 // BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
 // vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
@@ -30,6 +31,19 @@
 //                         words and, if none is set, clears the cell's status bit; the range of those cells
 //   vrt_edit_table        clears the cells' scratch words
 //   vrt_edit_finish
+//
+// Compaction (vrt_grid_compact on the scene) is the third mode, EditArgs::op = kEditOpCompact.  It has no batch: its
+// kernels run over the cells of the grid or over the entries of binding 5, and its scratch words are the per-voxel words of a batch of
+// brick_alloc voxels (live flags in vinfo, zeroed before the chain; prefix in vcell; holes in vslot; new names in vbrick):
+//   vrt_edit_begin (+ the scan of binding 5, as above)
+//   vrt_edit_validate     per cell: a loaded cell's brick < A, live[brick] = 1; per allocated brick: start == slot * B^3
+//   vrt_edit_count / _scan_groups / _rank   over bricks, the flag is live: the exclusive prefix P[b], and L = the live bricks
+//   vrt_edit_resolve      dead h < L: holes[h - P[h]] = h
+//   vrt_edit_write        phase 0: live b >= L takes holes[P[b] - P[L]]: new_name[b], and its two records copied in 16-byte pieces
+//   vrt_edit_write        phase 1 (a kernel boundary after every copy): occupancy [L bb, A bb) zeroed, binding 5 [L, A) unset, the
+//                         loaded cells naming a brick >= L renamed; the range of those cells
+//   vrt_edit_finish       A = L, cursor = L B^3; the written ranges of bindings 4 and 6 from the first and the last hole
+// (vrt_edit_table is not launched: no cell's scratch word is touched.)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -42,13 +56,15 @@ namespace vrt {
 constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
-constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1; // EditArgs::op
+constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2; // EditArgs::op
+constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
 constexpr uint32_t kEditErrShape = 1u << 0;  // binding 5 is not allocation-shaped                       -> VRT_E_STATE
 constexpr uint32_t kEditErrRange = 1u << 1;  // a voxel outside the grid                                  -> VRT_E_OUT_OF_RANGE
 constexpr uint32_t kEditErrCell = 1u << 2;   // a loaded cell names a brick at or beyond the allocated bricks -> VRT_E_STATE
 constexpr uint32_t kEditErrOom = 1u << 3;    // bricks or material entries exhausted                       -> VRT_E_OOM
+constexpr uint32_t kEditErrSlot = 1u << 4;   // compaction: an allocated brick's start is not slot * B^3   -> VRT_E_STATE
 
 // The allocation state that binding 5 defines (kept on the device, current across inserts).  While the scan of binding 5 runs,
 // first_unset / last_set_end / type_bits / max_start accumulate; vrt_edit_state turns them into bricks / cursor / ok.
@@ -65,12 +81,13 @@ struct EditState {
 // What one batch reads back (one small copy).  Ranges are element indices [lo, hi] (lo > hi: nothing written).
 struct EditStatus {
     uint32_t err;
-    uint32_t new_bricks;
+    uint32_t new_bricks;    // compaction: the live bricks L while the chain runs; the bricks given back, A - L, once it has finished
     uint32_t bricks;        // allocated bricks after the batch (before it if err != 0)
     uint32_t ok;            // the state's shape flag
     uint64_t cursor;        // next material entry after the batch
-    uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries); removal: unloaded
-    uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit; removal: that lost one
+    uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries); removal: unloaded;
+                                // compaction: renamed (binding 3 only)
+    uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit; removal: that lost one; compaction: first hole to the end of brick A - 1
     uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
 };
 
@@ -88,7 +105,8 @@ struct EditArgs {
     uint32_t groups;         // ceil(n / kEditBlock)
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
     uint32_t op;             // kEditOpInsert / kEditOpRemove (uniform: every kernel of a chain sees the same)
-    uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks
+    uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks;
+                             // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells
     // scratch (the context's, grown on demand)
     uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded (removal: that is loaded); kEditNone between batches
     uint32_t *vcell;         // [n] the voxel's cell (kEditNone: not written)
@@ -107,6 +125,7 @@ struct EditArgs {
     uint32_t brick_alloc;
     uint32_t start_words;           // entries of binding 5 scanned by vrt_edit_scan_start (= brick_alloc)
     uint64_t material_entries;      // bytes of binding 6 (brick_alloc * B^3)
+    uint32_t cells;                 // compaction: cells of the grid (n = max(cells, brick_alloc): the threads of its per-cell kernels)
 };
 
 } // namespace vrt
@@ -161,6 +180,13 @@ __device__ inline uint32_t group_prefix(bool flag, uint32_t *total) {
     }
     *total = sum;
     return before + below;
+}
+
+// one 16-byte (8-byte: the occupancy record of a 4^3 brick) piece of a record from brick `src` to brick `dst`
+template <typename T>
+__device__ inline void copy_piece(void *base, uint64_t record_bytes, uint32_t src, uint32_t dst, uint32_t piece) {
+    uint8_t *p = static_cast<uint8_t *>(base);
+    *reinterpret_cast<T *>(p + dst * record_bytes + piece * sizeof(T)) = *reinterpret_cast<const T *>(p + src * record_bytes + piece * sizeof(T));
 }
 
 } // namespace
@@ -219,7 +245,30 @@ __global__ void __launch_bounds__(64) vrt_edit_state(EditArgs a) {
     *a.state = s;
 }
 
+// compaction's preconditions and the live flags: thread i looks at cell i and at entry i of binding 5 (every lane gets to the reduction)
+__device__ inline void compact_validate(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool ok = a.state->ok != 0;
+    const uint32_t bricks = a.state->bricks;
+    uint32_t err = 0;
+    if (ok) {
+        if (i < a.cells && ((a.status[i >> 5] >> (i & 31u)) & 1u)) {
+            const uint32_t brick = a.index[i];
+            if (brick >= bricks) err = kEditErrCell;
+            else a.vinfo[brick] = 1u; // live (every cell naming the brick stores the same word)
+        }
+        if (i < bricks && a.start[i] != i * a.bits) err |= kEditErrSlot; // (i B^3 < brick_alloc B^3 <= 2^31; a type bit is a mismatch too)
+    } else if (i == 0) {
+        err = kEditErrShape;
+    }
+    wave_atomic_or(&a.out->err, err);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
+    if (a.op == kEditOpCompact) {
+        compact_validate(a);
+        return;
+    }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     const bool ok = a.state->ok != 0;
     const uint32_t bricks = a.state->bricks;
@@ -275,7 +324,9 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_count(EditArgs a) {
     if (a.out->err) return; // (no kernel of this one writes the word: uniform)
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     bool first = false;
-    if (i < a.n) {
+    if (a.op == kEditOpCompact) {
+        first = i < a.state->bricks && a.vinfo[i] != 0u; // a live brick
+    } else if (i < a.n) {
         const uint32_t info = a.vinfo[i];
         first = (info & 0x80000000u) && a.cell_first[a.vcell[i]] == i;
         if (first) a.vinfo[i] = info | 0x40000000u;
@@ -312,7 +363,8 @@ __global__ void __launch_bounds__(kEditScanBlock) vrt_edit_scan_groups(EditArgs 
         before += c;
     }
     if (t == 0) {
-        a.out->new_bricks = total;
+        a.out->new_bricks = total; // (compaction: the live bricks L)
+        if (a.op == kEditOpCompact) return;
         const EditState s = *a.state;
         if ((uint64_t)s.bricks + total > a.brick_alloc || s.cursor + (uint64_t)total * a.bits > a.material_entries) atomicOr(&a.out->err, kEditErrOom);
     }
@@ -321,15 +373,24 @@ __global__ void __launch_bounds__(kEditScanBlock) vrt_edit_scan_groups(EditArgs 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_rank(EditArgs a) {
     if (a.out->err) return;
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
-    const bool first = i < a.n && (a.vinfo[i] & 0x40000000u);
+    const bool compact = a.op == kEditOpCompact;
+    const bool first = compact ? (i < a.state->bricks && a.vinfo[i] != 0u) : (i < a.n && (a.vinfo[i] & 0x40000000u));
     uint32_t total;
     const uint32_t rank = a.group_sums[blockIdx.x] + group_prefix(first, &total);
+    if (compact) {
+        if (i < a.state->bricks) a.vcell[i] = rank; // P[b]: the live bricks below b
+        return;
+    }
     if (first) a.vbrick[i] = a.state->bricks + rank; // Grid.zig:147, in the order of first occurrence
 }
 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_resolve(EditArgs a) {
     if (a.out->err) return; // (this kernel may set the word: no wave-wide work follows)
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    if (a.op == kEditOpCompact) { // the dead bricks below L, in ascending order (L <= A: the words of brick i are written)
+        if (i < a.out->new_bricks && a.vinfo[i] == 0u) a.vslot[i - a.vcell[i]] = i;
+        return;
+    }
     if (i >= a.n) return;
     const uint32_t info = a.vinfo[i];
     if (!(info & 0x80000000u)) return;
@@ -396,10 +457,53 @@ __device__ inline void remove_write(const EditArgs &a) {
     wave_atomic_max(&a.out->cell_hi, hi);
 }
 
+// compaction's two passes (every lane of the wave gets to phase 1's reductions)
+__device__ inline void compact_write(const EditArgs &a) {
+    const uint32_t live = a.out->new_bricks, bricks = a.state->bricks; // L, A
+    const uint32_t stride = gridDim.x * kEditBlock, i = blockIdx.x * kEditBlock + threadIdx.x;
+    if (a.phase == 0) {
+        // lanes over (brick, piece): the B^3 / 16 pieces of the material entries, then the occupancy record (4 pieces; one of 8 bytes for 4^3)
+        const uint32_t mat_pieces = a.bits >> 4, pieces = mat_pieces + (a.b == 8u ? 4u : 1u);
+        const uint32_t work = (bricks - live) * pieces; // (brick_alloc B^3 <= 2^31, so brick_alloc (B^3 / 16 + 4) <= 2^28)
+        for (uint32_t t = i; t < work; t += stride) {
+            const uint32_t src = live + t / pieces, piece = t % pieces;
+            if (a.vinfo[src] == 0u) continue;
+            const uint32_t dst = a.vslot[a.vcell[src] - a.vcell[live]]; // its rank among the live bricks at or beyond L: that hole
+            if (piece == 0u) a.vbrick[src] = dst;
+            if (piece < mat_pieces) copy_piece<uint4>(a.material, a.bits, src, dst, piece);
+            else if (a.b == 8u) copy_piece<uint4>(a.occupancy, a.brick_bytes, src, dst, piece - mat_pieces);
+            else copy_piece<uint2>(a.occupancy, a.brick_bytes, src, dst, 0u);
+        }
+        return;
+    }
+    // the occupancy of bricks [L, A) in 8-byte pieces; their entries of binding 5
+    const uint32_t zero_pieces = (bricks - live) * (a.brick_bytes >> 3);
+    uint2 *tail = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(a.occupancy) + (uint64_t)live * a.brick_bytes);
+    for (uint32_t t = i; t < zero_pieces; t += stride) tail[t] = make_uint2(0u, 0u);
+    for (uint32_t t = live + i; t < bricks; t += stride) a.start[t] = kEditNone;
+    uint32_t lo = kEditNone, hi = 0;
+    for (uint64_t base = blockIdx.x * kEditBlock; base < a.cells; base += stride) { // (uniform trips per wave; 64-bit: cells reach 2^32 - 1)
+        const uint32_t cell = (uint32_t)base + threadIdx.x;
+        if (base + threadIdx.x < a.cells && ((a.status[cell >> 5] >> (cell & 31u)) & 1u)) {
+            const uint32_t brick = a.index[cell];
+            if (brick >= live) { // (validated: < A and live, so phase 0 gave it a new name)
+                a.index[cell] = a.vbrick[brick];
+                lo = min(lo, cell), hi = max(hi, cell);
+            }
+        }
+    }
+    wave_atomic_min(&a.out->cell_lo, lo);
+    wave_atomic_max(&a.out->cell_hi, hi);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     if (a.out->err) return;
     if (a.op == kEditOpRemove) {
         remove_write(a);
+        return;
+    }
+    if (a.op == kEditOpCompact) {
+        compact_write(a);
         return;
     }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
@@ -437,6 +541,26 @@ __global__ void __launch_bounds__(64) vrt_edit_finish(EditArgs a) {
     if (threadIdx.x != 0) return;
     EditState s = *a.state;
     EditStatus o = *a.out;
+    if (a.op == kEditOpCompact) {
+        const uint32_t live = o.new_bricks; // L
+        uint32_t freed = 0;
+        if (o.err == 0 && live < s.bricks) {
+            freed = s.bricks - live;
+            const uint32_t holes = live - a.vcell[live]; // dead bricks below L (P[L] live ones)
+            const uint32_t first = holes ? a.vslot[0] : live, last = holes ? a.vslot[holes - 1u] : 0u;
+            a.out->occ_lo = first * a.brick_bytes, a.out->occ_hi = s.bricks * a.brick_bytes - 1u;
+            if (holes) a.out->mat_lo = first * a.bits, a.out->mat_hi = (last + 1u) * a.bits - 1u; // (<= L B^3 - 1 < 2^31)
+            s.bricks = live;
+            s.cursor = (uint64_t)live * a.bits;
+            a.state->bricks = s.bricks;
+            a.state->cursor = s.cursor;
+        }
+        a.out->new_bricks = freed;
+        a.out->bricks = s.bricks;
+        a.out->cursor = s.cursor;
+        a.out->ok = s.ok;
+        return;
+    }
     if (o.err == 0 && o.new_bricks) {
         s.bricks += o.new_bricks;
         s.cursor += (uint64_t)o.new_bricks * a.bits;
@@ -456,8 +580,8 @@ namespace {
 
 // what every entry point checks before it touches the device: the scene is there, this context may edit it, and the small
 // buffers of the allocation state exist
-int edit_prepare(vrt_ctx *ctx, const char *what = "inserts") {
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, std::string("voxel ") + what + " are not available on a context of the multi-GPU pipeline");
+int edit_prepare(vrt_ctx *ctx, const char *what = "voxel inserts are") {
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, std::string(what) + " not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
     if (!ctx->d_edit_state) {
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_state, sizeof(vrt::EditState)));
@@ -660,6 +784,57 @@ int remove(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
     return VRT_OK;
 }
 
+// the scene's dead bricks given back: the chain over cells and bricks, as one scene write
+int compact(vrt_ctx *ctx, uint32_t out[2]) {
+    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
+    const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
+    const uint32_t brick_alloc = (uint32_t)(ctx->dsize[VRT_BUF_BRICK_START_INDEX] / 4u);
+    int rc = edit_scratch(ctx, std::max<uint64_t>(brick_alloc, 1u), false); // its scratch: the per-voxel words of a batch of brick_alloc voxels
+    if (rc != VRT_OK) return rc;
+    rc = begin_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, nullptr, nullptr, brick_alloc, !ctx->edit_state_valid);
+    a.op = vrt::kEditOpCompact;
+    a.cells = (uint32_t)cells;
+    const uint32_t brick_groups = a.groups; // (also what vrt_edit_scan_groups scans)
+    const uint32_t cell_groups = (uint32_t)((std::max<uint64_t>(cells, brick_alloc) + vrt::kEditBlock - 1u) / vrt::kEditBlock);
+    const uint32_t copy_groups = std::min<uint32_t>(cell_groups, vrt::kEditCopyGroups);
+    VRT_HIP(ctx, hipMemsetAsync(a.vinfo, 0, (size_t)brick_alloc * sizeof(uint32_t), ctx->stream)); // no brick is live yet
+    rc = launch_state(ctx, a);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, cell_groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, brick_groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, brick_groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, brick_groups, vrt::kEditBlock);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, copy_groups, vrt::kEditBlock);
+    a.phase = 1;
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, copy_groups, vrt::kEditBlock);
+    if (rc != VRT_OK) {
+        (void)wait_stream(ctx->stream);
+        ctx->edit_state_valid = false;
+        return rc;
+    }
+    rc = end_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditStatus s;
+    rc = read_status(ctx, a, &s);
+    if (rc != VRT_OK) return rc;
+    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
+    if (s.err & vrt::kEditErrSlot)
+        return fail(ctx, VRT_E_STATE, "an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3; nothing was compacted");
+    if (s.err & vrt::kEditErrCell)
+        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5); nothing was compacted");
+    if (out) out[0] = s.bricks + s.new_bricks, out[1] = s.bricks;
+    if (s.new_bricks == 0) return VRT_OK; // no dead brick: nothing was written
+    // exactly what was written: the renamed cells, the filled holes and the cleared tail, the entries of binding 5 that were unset
+    if (s.cell_lo <= s.cell_hi) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
+    mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
+    mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)s.bricks * 4u, (uint64_t)s.new_bricks * 4u);
+    ctx->edit_state_valid = true; // (the device state already holds L and its cursor: this write is the compaction's own)
+    if (s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    return VRT_OK;
+}
+
 int check_batch(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
     if (!xyz || !materials) return fail(ctx, VRT_E_INVALID_ARG, "xyz or materials is NULL");
     if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
@@ -709,7 +884,7 @@ int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
     if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
     if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
     DeviceGuard dg(ctx->device);
-    const int rc = edit_prepare(ctx, "removals");
+    const int rc = edit_prepare(ctx, "voxel removals are");
     if (rc != VRT_OK) return rc;
     return remove(ctx, xyz, n);
 }
@@ -720,7 +895,7 @@ int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
     if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
     if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
     DeviceGuard dg(ctx->device);
-    int rc = edit_prepare(ctx, "removals");
+    int rc = edit_prepare(ctx, "voxel removals are");
     if (rc != VRT_OK) return rc;
     // the batch into device memory through the pinned staging slots
     const uint64_t bytes = 12u * n;
@@ -733,6 +908,14 @@ int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
     rc = staged_copy_h2d(ctx, ctx->d_edit_input, xyz, bytes);
     if (rc != VRT_OK) return rc;
     return remove(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), n);
+}
+
+int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    DeviceGuard dg(ctx->device);
+    const int rc = edit_prepare(ctx, "brick compaction is");
+    if (rc != VRT_OK) return rc;
+    return compact(ctx, out);
 }
 
 int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]) {

@@ -80,6 +80,13 @@ class BrickGrid:
         xyz = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
         check(lib.vrt_grid_remove_many(self._h, xyz.ctypes.data, xyz.shape[0]))
 
+    def compact(self) -> Tuple[int, int]:
+        """vrt_grid_compact: the dead bricks give their slots back (the live bricks of the tail fill the holes); no frame changes.
+        Returns (allocated bricks before, after)."""
+        out = (C.c_uint32 * 2)()
+        check(lib.vrt_grid_compact(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -375,6 +382,13 @@ class VoxelRT:
             return
         x = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
         self._check(self._lib.vrt_remove_voxels(self._h, x.ctypes.data, x.shape[0]))
+
+    def compact_bricks(self) -> Tuple[int, int]:
+        """BrickGrid.compact on the scene the context holds (vrt_compact_bricks): bindings 2-6 afterwards equal the host grid's arrays
+        after compact(), and insert_voxels continues from the bricks that are left.  Returns (allocated bricks before, after)."""
+        out = (C.c_uint32 * 2)()
+        self._check(self._lib.vrt_compact_bricks(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
 
     def read_buffer(self, buf_id: int) -> np.ndarray:
         """Copy of scene buffer `buf_id` as frames see it now (vrt_read_buffer), typed: uint32 words for bindings 2, 3 and 5, bytes for
