@@ -266,6 +266,14 @@ pub const RayHit = extern struct {
     hit: u32,
 };
 pub const RAY_RAW_DIRECTION: u32 = 1 << 0;
+/// The planes of vrt_trace_aux / vrt_trace_aux_device, 32 bytes: row-major, width x height of the camera, tightly packed; null = not
+/// wanted.  depth is HitRecord.t (+inf for a miss); the 16-byte planes are dwords 0..3, 4..7 and 8..11 of RayHit (all zero for a miss).
+pub const AuxPlanes = extern struct {
+    depth: ?[*]f32 = null,
+    point_t: ?*anyopaque = null,
+    normal_material: ?*anyopaque = null,
+    voxel_hit: ?*anyopaque = null,
+};
 
 // BEGIN GENERATED extern declarations (tools/gen_zig_binding.py from include/vrt_hip.h) — do not edit by hand
 pub extern fn vrt_create(cfg: [*c]const Config, out: *?*Ctx) c_int;
@@ -332,6 +340,8 @@ pub extern fn vrt_upload_grid(ctx: ?*Ctx, g: ?*Grid) c_int;
 pub extern fn vrt_update_grid_delta(ctx: ?*Ctx, g: ?*Grid) c_int;
 pub extern fn vrt_cast_rays(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
 pub extern fn vrt_cast_rays_device(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
+pub extern fn vrt_trace_aux(ctx: ?*Ctx, camera: [*c]const CameraDevice, host_planes: [*c]const AuxPlanes) c_int;
+pub extern fn vrt_trace_aux_device(ctx: ?*Ctx, camera: [*c]const CameraDevice, device_planes: [*c]const AuxPlanes) c_int;
 pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;

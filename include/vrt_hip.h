@@ -515,6 +515,35 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_h
 /* rays and hits in device memory; ordered on the context's stream after every upload so far; asynchronous (vrt_wait).
  * The flags are not read on the host here: a ray with unknown flag bits gets a miss record. */
 int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits);
+/* ---- First-hit buffers of a camera's image ---------------------------------------------------------------------------
+ * Depth, normal, material and voxel per pixel: what a host needs to composite raster content against a traced frame (depth), to
+ * guide a filter after the present pass (normal, material) and to pick under a cursor or a box selection (voxel) — without making a
+ * ray per pixel and reading 48-byte records back.  The pass forms the camera rays in the kernel (vrt_ray_query_b4 / _b8 in their second
+ * mode), walks them in the frames' 8x8-pixel waves and writes only the planes asked for.
+ *
+ * CONTRACT.  For pixel (px, py) of a camera->image_width x image_height image, every plane element equals the matching bytes of the
+ * vrt_ray_hit that vrt_cast_rays returns for the ray of vrt_camera_pixel_ray(camera, px, py) with flags 0 and max_t = INFINITY.  A miss
+ * is all-zero in the three 16-byte planes and +INFINITY in depth (the one place where a miss is not zero: depth consumers compare).
+ * The image size is the camera's, not the context's target; the planes are the caller's.  samples_per_pixel and max_bounce are
+ * ignored: the ray is the un-jittered sample 0.
+ *
+ * ORDERING as for queries: the derived structures are refreshed first, on the context's primary stream, so a pass issued right after
+ * vrt_insert_voxels, vrt_remove_voxels, vrt_compact_bricks or vrt_update_grid_delta sees the edit without a vrt_wait.
+ *
+ * ERRORS.  VRT_E_INVALID_ARG: a NULL ctx, camera or planes; all four plane pointers NULL; an image width or height below 2
+ * (u = x / (w - 1)); more than 2^24 pixels; (device variant) a plane pointer that is not aligned, 16 bytes for the three wide planes
+ * and 4 for depth.  VRT_E_STATE: no grid state uploaded, a context of the multi-GPU pipeline, or a sharded context
+ * (shard_count > 1).  A failed call leaves the context usable. */
+typedef struct vrt_aux_planes {   /* row-major, width x height of the CAMERA, tightly packed; any pointer may be NULL = not wanted */
+    float    *depth;              /* 4 B / pixel: HitRecord.t of the first hit; +INFINITY for a miss                         */
+    void     *point_t;            /* 16 B / pixel: point.xyz, t          = dwords 0..3  of vrt_ray_hit                       */
+    void     *normal_material;    /* 16 B / pixel: normal.xyz, material  = dwords 4..7  of vrt_ray_hit                       */
+    void     *voxel_hit;          /* 16 B / pixel: voxel.xyz, hit        = dwords 8..11 of vrt_ray_hit                       */
+} vrt_aux_planes;
+/* planes in host memory; staged through device buffers the context owns (grown on demand); blocks until the planes are written */
+int vrt_trace_aux(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_planes *host_planes);
+/* planes in device memory; returns after the launch (vrt_wait) */
+int vrt_trace_aux_device(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_planes *device_planes);
 /* ---- Batched voxel inserts into the uploaded scene --------------------------------------------------------------
  * BrickGrid.insert (Grid.zig:129-194) for n voxels at once, on the GPU, on the scene buffers the context holds: after
  * vrt_insert_voxels(ctx, xyz, m, n) on a context whose bindings 2-6 equal a vrt_grid's arrays, bindings 2-6 equal that grid's

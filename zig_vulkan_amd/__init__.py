@@ -6,8 +6,8 @@ reference's scene / camera / renderer API used by tests and bench.py.
 Importing it loads the shared library and fails loudly if it is absent.
 """
 from . import _lib
-from .voxel_rt import (BrickGrid, Camera, CameraConfig, Config, MATERIAL_DTYPE, RAY_HIT_DTYPE, RAY_QUERY_DTYPE, Sun, SunConfig, VoxelRT,
+from .voxel_rt import (AUX_PLANES, AUX_PLANE_DTYPES, BrickGrid, Camera, CameraConfig, Config, MATERIAL_DTYPE, RAY_HIT_DTYPE, RAY_QUERY_DTYPE, Sun, SunConfig, VoxelRT,
                        default_materials, ray_queries)
 
-__all__ = ["BrickGrid", "Camera", "CameraConfig", "Config", "MATERIAL_DTYPE", "RAY_HIT_DTYPE", "RAY_QUERY_DTYPE", "Sun", "SunConfig",
+__all__ = ["AUX_PLANES", "AUX_PLANE_DTYPES", "BrickGrid", "Camera", "CameraConfig", "Config", "MATERIAL_DTYPE", "RAY_HIT_DTYPE", "RAY_QUERY_DTYPE", "Sun", "SunConfig",
            "VoxelRT", "default_materials", "ray_queries", "_lib"]

@@ -155,10 +155,14 @@ class RayHit(C.Structure):  # vrt_ray_hit (48 bytes)
                 ("voxel", C.c_int32 * 3), ("hit", C.c_uint32)]
 
 
+class AuxPlanes(C.Structure):  # vrt_aux_planes (32 bytes): NULL = not wanted
+    _fields_ = [("depth", C.c_void_p), ("point_t", C.c_void_p), ("normal_material", C.c_void_p), ("voxel_hit", C.c_void_p)]
+
+
 RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
 
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
-assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48
+assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -236,6 +240,8 @@ SIGNATURES = {
     "vrt_update_grid_delta": (C.c_int, [_ctx, _grid]),
     "vrt_cast_rays": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_cast_rays_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_trace_aux": (C.c_int, [_ctx, _P(CameraDevice), _P(AuxPlanes)]),
+    "vrt_trace_aux_device": (C.c_int, [_ctx, _P(CameraDevice), _P(AuxPlanes)]),
     "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_remove_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

@@ -217,6 +217,9 @@ struct vrt_ctx {
     vrt_ray_query *d_query_rays = nullptr;
     vrt_ray_hit *d_query_hits = nullptr;
     uint64_t query_capacity = 0;     // rays the two buffers hold
+    // the first-hit buffer pass (vrt_trace_aux): the host path's device buffer, the wanted planes one after another
+    uint8_t *d_aux_planes = nullptr;
+    uint64_t aux_capacity = 0;       // bytes it holds
     // batched voxel inserts (vrt_edit.hip): the allocation state binding 5 defines (on the device, and the host's copy of what the
     // last read-back said), and the scratch (kept, grown on demand)
     bool edit_state_valid = false;   // false: binding 5 was written since the state was computed (every write goes through mark_dirty)

@@ -173,6 +173,21 @@ class Camera:
         check(lib.vrt_camera_pixel_ray(C.byref(self.d_camera), px, py, C.byref(o), C.byref(d)))
         return np.array(o[:], dtype=np.float32), np.array(d[:], dtype=np.float32)
 
+    def pixel_rays(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(origins, directions), each (width * height, 3), of pixel_ray for every pixel in row-major order, bit for bit: the
+        arithmetic of vrt_camera_pixel_ray in float32 (direction = (horizontal * u + llc) + (v * vertical - origin), every
+        operation rounded; the fused build of the library is not mirrored here)."""
+        cam = self.d_camera
+        w, h = int(cam.image_width), int(cam.image_height)
+        f32 = np.float32
+        u = ((np.arange(w, dtype=f32) + f32(0.0)) / f32(w - 1))[None, :, None]
+        v = ((np.arange(h, dtype=f32) + f32(0.0)) / f32(h - 1))[:, None, None]
+        horizontal, vertical = np.array(cam.horizontal[:], dtype=f32), np.array(cam.vertical[:], dtype=f32)
+        llc, origin = np.array(cam.lower_left_corner[:], dtype=f32), np.array(cam.origin[:], dtype=f32)
+        directions = (horizontal * u + llc) + (v * vertical + (-origin))
+        origins = np.broadcast_to(origin, directions.shape)
+        return np.ascontiguousarray(origins).reshape(-1, 3), np.ascontiguousarray(directions, dtype=f32).reshape(-1, 3)
+
 
 @dataclass
 class SunConfig:  # Sun.zig:4-11
@@ -216,6 +231,18 @@ RAY_QUERY_DTYPE = np.dtype([("origin", np.float32, 3), ("max_t", np.float32), ("
 RAY_HIT_DTYPE = np.dtype([("point", np.float32, 3), ("t", np.float32), ("normal", np.float32, 3), ("material", np.uint32),
                           ("voxel", np.int32, 3), ("hit", np.uint32)])
 assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 48
+
+
+# vrt_aux_planes (include/vrt_hip.h): the planes of trace_aux in the struct's order, and one pixel of each as a numpy record — the
+# 16-byte planes are dwords 0..3, 4..7 and 8..11 of RAY_HIT_DTYPE, field for field
+AUX_PLANES = ("depth", "point_t", "normal_material", "voxel_hit")
+AUX_PLANE_DTYPES = {
+    "depth": np.dtype(np.float32),
+    "point_t": np.dtype([("point", np.float32, 3), ("t", np.float32)]),
+    "normal_material": np.dtype([("normal", np.float32, 3), ("material", np.uint32)]),
+    "voxel_hit": np.dtype([("voxel", np.int32, 3), ("hit", np.uint32)]),
+}
+assert all(AUX_PLANE_DTYPES[k].itemsize == 16 for k in AUX_PLANES[1:])
 
 
 def ray_queries(origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
@@ -450,6 +477,47 @@ class VoxelRT:
         self._check(self._lib.vrt_cast_rays_device(self._h, q.data_ptr(), n, hits.data_ptr()))
         self.wait()
         return hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
+
+    # -- first-hit buffers ------------------------------------------------------
+    def trace_aux(self, camera: Optional[Camera] = None, planes: Sequence[str] = AUX_PLANES, device: bool = False) -> dict:
+        """Per-pixel first-hit data of `camera`'s image (None: self.camera), by plane name (vrt_trace_aux): "depth" (h, w) float32, +inf
+        for a miss; "point_t" (h, w, 4) float32; "normal_material" and "voxel_hit" (h, w) records of AUX_PLANE_DTYPES, so that
+        ["normal"], ["material"], ["voxel"] and ["hit"] read as in RAY_HIT_DTYPE.  Every element equals the matching bytes of
+        cast_rays(*camera.pixel_rays()).  device=True: torch tensors on the GPU, written in place by vrt_trace_aux_device and waited
+        for — "depth" (h, w) float32, "point_t" (h, w, 4) float32, the two record planes (h, w, 4) int32 (normal.xyz as bits, material;
+        voxel.xyz, hit)."""
+        cam = (camera or self.camera).d_camera
+        w, h = int(cam.image_width), int(cam.image_height)
+        planes = tuple(planes)
+        unknown = [k for k in planes if k not in AUX_PLANES]
+        if unknown:
+            raise ValueError(f"unknown plane(s) {unknown}: one of {AUX_PLANES}")
+        ap = L.AuxPlanes()
+        out = {}
+        if device:
+            import torch
+            dev = torch.device("cuda", self._device_index())
+            for k in planes:
+                out[k] = torch.empty((h, w) if k == "depth" else (h, w, 4), dtype=torch.float32 if k in ("depth", "point_t") else torch.int32, device=dev)
+                setattr(ap, k, out[k].data_ptr())
+            torch.cuda.current_stream(dev).synchronize()  # (torch's allocator may hand out memory its stream still writes)
+            self._check(self._lib.vrt_trace_aux_device(self._h, C.byref(cam), C.byref(ap)))
+            self.wait()
+            return out
+        for k in planes:
+            out[k] = np.empty((h, w) if k == "depth" else (h, w, 4), dtype=np.float32 if k in ("depth", "point_t") else np.uint32)
+            setattr(ap, k, out[k].ctypes.data)
+        self._check(self._lib.vrt_trace_aux(self._h, C.byref(cam), C.byref(ap)))
+        for k in ("normal_material", "voxel_hit"):
+            if k in out:
+                out[k] = out[k].view(AUX_PLANE_DTYPES[k]).reshape(h, w)
+        return out
+
+    def _device_index(self) -> int:
+        if self.config.device_id >= 0:
+            return self.config.device_id
+        import torch
+        return torch.cuda.current_device()
 
     def region_begin(self) -> None:
         self._check(self._lib.vrt_region_begin(self._h))
