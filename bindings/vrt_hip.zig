@@ -274,6 +274,21 @@ pub const AuxPlanes = extern struct {
     normal_material: ?*anyopaque = null,
     voxel_hit: ?*anyopaque = null,
 };
+/// What vrt_get_voxels gives for a voxel that is not solid or lies outside the grid; a solid voxel gives its material entry, 0..255.
+pub const VOXEL_EMPTY: u16 = 0xFFFF;
+/// One box of vrt_query_boxes, 32 bytes: inclusive corners in voxels, in the coordinates vrt_grid_insert takes; clipped to the grid.
+pub const BoxQuery = extern struct {
+    lo: [3]i32,
+    hi: [3]i32,
+    flags: u32 = 0,
+    _reserved: u32 = 0,
+};
+/// Its answer, 32 bytes: the number of solid voxels in the clipped box and their tight bounds; all zero for none.
+pub const BoxResult = extern struct {
+    lo: [3]i32,
+    hi: [3]i32,
+    count: u64,
+};
 
 // BEGIN GENERATED extern declarations (tools/gen_zig_binding.py from include/vrt_hip.h) — do not edit by hand
 pub extern fn vrt_create(cfg: [*c]const Config, out: *?*Ctx) c_int;
@@ -342,6 +357,12 @@ pub extern fn vrt_cast_rays(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: 
 pub extern fn vrt_cast_rays_device(ctx: ?*Ctx, rays: [*c]const RayQuery, n: u64, hits: [*c]RayHit) c_int;
 pub extern fn vrt_trace_aux(ctx: ?*Ctx, camera: [*c]const CameraDevice, host_planes: [*c]const AuxPlanes) c_int;
 pub extern fn vrt_trace_aux_device(ctx: ?*Ctx, camera: [*c]const CameraDevice, device_planes: [*c]const AuxPlanes) c_int;
+pub extern fn vrt_get_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64, out: [*c]u16) c_int;
+pub extern fn vrt_get_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, n: u64, out: [*c]u16) c_int;
+pub extern fn vrt_grid_get_voxels(g: ?*const Grid, xyz: [*c]const u32, n: u64, out: [*c]u16) c_int;
+pub extern fn vrt_query_boxes(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
+pub extern fn vrt_query_boxes_device(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
+pub extern fn vrt_grid_query_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
 pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;

@@ -544,6 +544,57 @@ typedef struct vrt_aux_planes {   /* row-major, width x height of the CAMERA, ti
 int vrt_trace_aux(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_planes *host_planes);
 /* planes in device memory; returns after the launch (vrt_wait) */
 int vrt_trace_aux_device(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_planes *device_planes);
+/* ---- Volume queries against the uploaded scene -----------------------------------------------------------------------
+ * "What is at this place?" — the twin of the three writes (vrt_insert_voxels, vrt_remove_voxels, vrt_compact_bricks), in the
+ * coordinates they take: x, y, z of vrt_grid_insert, y counted as insert counts it (flipped inside, Grid.zig:135); the voxel of a
+ * vrt_ray_hit is in these coordinates too.  Both queries read bindings 2-6 of the scene the context holds and none of the structures
+ * derived from them (vrt_ray_query_b4 / _b8 in their modes 2 and 3); each has a CPU twin on a vrt_grid, which reads only the grid's
+ * arrays and registers no delta.  A voxel is SOLID when the status bit of its cell is 1 and its occupancy bit is 1.  The status bit
+ * decides first: after a removal or a compaction, brick_indices of a cell that is not loaded is stale and may name a brick that
+ * belongs to another cell.
+ *
+ * LOOK-UPS.  out[i] of a solid voxel = material_indices[(brick_start_indices[brick] & 0x7FFFFFFF) + nth_bit], 0..255: the entry the
+ * frames shade with (comp:422-425).  Everything else is VRT_VOXEL_EMPTY: a voxel outside the grid (a coordinate of 2^31 or more
+ * included), a cell that is not loaded, an occupancy bit that is 0.  A look-up never fails because of where a voxel lies.
+ *
+ * BOXES.  lo and hi are inclusive corners in voxels, signed.  The box is clipped to the grid and what lies outside is empty: a box
+ * that straddles the border or lies wholly outside is legal; lo > hi on any axis is an empty box.  count is the number of solid
+ * voxels in the clipped box (64 bits: a 512^3-cell grid of 8^3 bricks holds 2^36 voxels), lo / hi of the result their tight bounds;
+ * count == 0 gives an all-zero record.  flags and _reserved must be 0: the host entry point refuses the batch (VRT_E_INVALID_ARG, the
+ * error names the box, nothing is written); the device entry point and the CPU twin, which do not screen the batch, write an all-zero
+ * record for that box, as a ray with unknown flags gets a miss.  On the GPU a box is one wave's work however large it is.
+ *
+ * ERRORS AND ORDERING as for vrt_cast_rays / vrt_cast_rays_device.  VRT_E_INVALID_ARG: a NULL ctx (or grid); a NULL pointer with
+ * n > 0; (device variants) a pointer that is not aligned: 16 bytes for boxes and results, 4 for xyz, 2 for out.  VRT_E_STATE: no grid
+ * state uploaded, or a context of the multi-GPU pipeline.  n == 0: VRT_OK, nothing touched.  A failed call leaves the context usable.
+ * The calls are ordered on the context's primary stream behind every upload and edit so far: a query issued right after
+ * vrt_insert_voxels, vrt_remove_voxels, vrt_compact_bricks or vrt_update_grid_delta sees the edit without a vrt_wait.  The host
+ * variants stage through the ray queries' device buffers (grown on demand), 2^20 items at a time, and block until the answers are
+ * written; the device variants return after the launch (vrt_wait). */
+#define VRT_VOXEL_EMPTY 0xFFFFu
+typedef struct vrt_box_query {      /* 32 bytes */
+    int32_t lo[3];                  /* inclusive corners, in voxels, as vrt_grid_insert counts them */
+    int32_t hi[3];
+    uint32_t flags;                 /* 0 */
+    uint32_t _reserved;             /* 0 */
+} vrt_box_query;
+typedef struct vrt_box_result {     /* 32 bytes */
+    int32_t lo[3];                  /* tight bounds of the solid voxels in the clipped box; all zero when count == 0 */
+    int32_t hi[3];
+    uint64_t count;                 /* solid voxels in the clipped box */
+} vrt_box_result;
+/* xyz and out in host memory; blocks until out is written */
+int vrt_get_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out);
+/* xyz and out in device memory; asynchronous (vrt_wait) */
+int vrt_get_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out);
+/* the CPU twin on a host grid */
+int vrt_grid_get_voxels(const vrt_grid *g, const uint32_t *xyz, uint64_t n, uint16_t *out);
+/* boxes and results in host memory; blocks until the results are written */
+int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
+/* boxes and results in device memory, both 16-byte aligned; asynchronous (vrt_wait) */
+int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
+/* the CPU twin on a host grid */
+int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
 /* ---- Batched voxel inserts into the uploaded scene --------------------------------------------------------------
  * BrickGrid.insert (Grid.zig:129-194) for n voxels at once, on the GPU, on the scene buffers the context holds: after
  * vrt_insert_voxels(ctx, xyz, m, n) on a context whose bindings 2-6 equal a vrt_grid's arrays, bindings 2-6 equal that grid's

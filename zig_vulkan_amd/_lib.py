@@ -159,10 +159,20 @@ class AuxPlanes(C.Structure):  # vrt_aux_planes (32 bytes): NULL = not wanted
     _fields_ = [("depth", C.c_void_p), ("point_t", C.c_void_p), ("normal_material", C.c_void_p), ("voxel_hit", C.c_void_p)]
 
 
+class BoxQuery(C.Structure):  # vrt_box_query (32 bytes)
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class BoxResult(C.Structure):  # vrt_box_result (32 bytes)
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("count", C.c_uint64)]
+
+
 RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
+VOXEL_EMPTY = 0xFFFF        # VRT_VOXEL_EMPTY
 
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
+assert C.sizeof(BoxQuery) == 32 and C.sizeof(BoxResult) == 32
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -242,6 +252,12 @@ SIGNATURES = {
     "vrt_cast_rays_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_trace_aux": (C.c_int, [_ctx, _P(CameraDevice), _P(AuxPlanes)]),
     "vrt_trace_aux_device": (C.c_int, [_ctx, _P(CameraDevice), _P(AuxPlanes)]),
+    "vrt_get_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_get_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_grid_get_voxels": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_query_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_query_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_grid_query_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_remove_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

@@ -1,5 +1,6 @@
 // host_brick_grid.cpp — see host_brick_grid.hpp.
 #include "host_brick_grid.hpp"
+#include <algorithm>
 #include <limits>
 #include <new>
 
@@ -234,6 +235,75 @@ int BrickGrid::compact(uint32_t out[2]) {
     active_bricks_.store(l, std::memory_order_relaxed);
     material_cursor_.store(l * bits, std::memory_order_relaxed);
     return VRT_OK;
+}
+
+void BrickGrid::getVoxels(const uint32_t *xyz, uint64_t n, uint16_t *out) const {
+    const vrt_grid_state &d = device_state_;
+    const uint32_t b = brick_dimension_;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        out[i] = VRT_VOXEL_EMPTY;
+        if (x >= d.voxel_dim_x || y >= d.voxel_dim_y || z >= d.voxel_dim_z) continue;
+        const uint32_t flipped_y = d.voxel_dim_y - 1 - y; // Grid.zig:135
+        const size_t grid_index = (size_t)(x / b) + (size_t)d.dim_x * ((size_t)(z / b) + (size_t)d.dim_z * (size_t)(flipped_y / b)); // gridAt
+        if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue;
+        const uint32_t brick_index = brick_indices[grid_index];
+        const uint32_t nth_bit = (x % b) + b * ((z % b) + b * (flipped_y % b)); // voxelAt
+        if (!((brick_occupancy[(size_t)brick_index * brick_bytes_ + nth_bit / 8] >> (nth_bit % 8)) & 1u)) continue;
+        out[i] = material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu) + nth_bit]; // comp:422-425
+    }
+}
+
+void BrickGrid::queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) const {
+    const vrt_grid_state &d = device_state_;
+    const int64_t b = brick_dimension_;
+    for (uint64_t i = 0; i < n; i++) {
+        const vrt_box_query &q = boxes[i];
+        vrt_box_result r{};
+        const int64_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
+        int64_t lo[3], hi[3]; // the clipped box; y flipped from here on (Grid.zig:135)
+        bool empty = (q.flags | q._reserved) != 0;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = std::max<int64_t>(q.lo[k], 0);
+            hi[k] = std::min<int64_t>(q.hi[k], dim[k] - 1);
+            empty = empty || lo[k] > hi[k];
+        }
+        if (empty) {
+            results[i] = r;
+            continue;
+        }
+        const int64_t flipped_lo = dim[1] - 1 - hi[1], flipped_hi = dim[1] - 1 - lo[1];
+        lo[1] = flipped_lo, hi[1] = flipped_hi;
+        int64_t mn[3] = {dim[0], dim[1], dim[2]}, mx[3] = {-1, -1, -1};
+        uint64_t count = 0;
+        // cell by cell, and in a loaded cell row by row: the B voxels of a row (x) are B adjacent bits of one occupancy byte
+        for (int64_t cy = lo[1] / b; cy <= hi[1] / b; cy++)
+            for (int64_t cz = lo[2] / b; cz <= hi[2] / b; cz++)
+                for (int64_t cx = lo[0] / b; cx <= hi[0] / b; cx++) {
+                    const size_t grid_index = (size_t)cx + (size_t)d.dim_x * ((size_t)cz + (size_t)d.dim_z * (size_t)cy); // gridAt
+                    if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue;
+                    const uint8_t *occ = &brick_occupancy[(size_t)brick_indices[grid_index] * brick_bytes_];
+                    const int64_t x0 = std::max(lo[0], cx * b), x1 = std::min(hi[0], cx * b + b - 1);
+                    const uint32_t row_mask = ((1u << (x1 - x0 + 1)) - 1u) << (x0 - cx * b);
+                    for (int64_t y = std::max(lo[1], cy * b); y <= std::min(hi[1], cy * b + b - 1); y++)
+                        for (int64_t z = std::max(lo[2], cz * b); z <= std::min(hi[2], cz * b + b - 1); z++) {
+                            const uint32_t row_bit = (uint32_t)(b * ((z - cz * b) + b * (y - cy * b))); // voxelAt of the row's x = 0
+                            const uint32_t row = (occ[row_bit / 8] >> (row_bit % 8)) & row_mask;
+                            if (!row) continue;
+                            count += (uint64_t)__builtin_popcount(row);
+                            mn[0] = std::min<int64_t>(mn[0], cx * b + __builtin_ctz(row));
+                            mx[0] = std::max<int64_t>(mx[0], cx * b + 31 - __builtin_clz(row));
+                            mn[1] = std::min(mn[1], y), mx[1] = std::max(mx[1], y);
+                            mn[2] = std::min(mn[2], z), mx[2] = std::max(mx[2], z);
+                        }
+                }
+        if (count) {
+            r.lo[0] = (int32_t)mn[0], r.lo[1] = (int32_t)(dim[1] - 1 - mx[1]), r.lo[2] = (int32_t)mn[2];
+            r.hi[0] = (int32_t)mx[0], r.hi[1] = (int32_t)(dim[1] - 1 - mn[1]), r.hi[2] = (int32_t)mx[2];
+            r.count = count;
+        }
+        results[i] = r;
+    }
 }
 
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {

@@ -72,6 +72,15 @@ public:
     // out (may be null) = {A, L}.  Deltas: per array, the first to the last element whose value changed.  Single-threaded.
     int compact(uint32_t out[2]);
 
+    // Volume queries (the reference has none: include/vrt_hip.h defines them).  Coordinates as insert takes them.  They read the five
+    // arrays only and register no delta.  A voxel is solid when its cell's status bit and its occupancy bit are 1; the status bit is
+    // tested first (brick_indices of a cell that is not loaded is stale).
+    // out[i] = the material entry of voxel i, or VRT_VOXEL_EMPTY (not solid, or outside the grid)
+    void getVoxels(const uint32_t *xyz, uint64_t n, uint16_t *out) const;
+    // per box: the number and the tight bounds of the solid voxels in the box clipped to the grid; all zero for none, and for a box
+    // with flag bits or a non-zero _reserved
+    void queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) const;
+
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }
     uint32_t brickBits() const { return brick_bits_; }

@@ -260,6 +260,18 @@ int vrt_grid_compact(vrt_grid *g, uint32_t out[2]) {
     return reinterpret_cast<vrt::BrickGrid *>(g)->compact(out);
 }
 
+int vrt_grid_get_voxels(const vrt_grid *g, const uint32_t *xyz, uint64_t n, uint16_t *out) {
+    if (!g || (n && (!xyz || !out))) return VRT_E_INVALID_ARG;
+    reinterpret_cast<const vrt::BrickGrid *>(g)->getVoxels(xyz, n, out);
+    return VRT_OK;
+}
+
+int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
+    if (!g || (n && (!boxes || !results))) return VRT_E_INVALID_ARG;
+    reinterpret_cast<const vrt::BrickGrid *>(g)->queryBoxes(boxes, n, results);
+    return VRT_OK;
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

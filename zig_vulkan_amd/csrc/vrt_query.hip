@@ -1,13 +1,15 @@
 // vrt_query.hip — batched ray queries behind the C ABI (vrt_cast_rays, vrt_cast_rays_device): their kernels vrt_ray_query_b4 / _b8 and
 // their host side; the first-hit buffer pass (vrt_trace_aux, vrt_trace_aux_device), a second mode of the same two kernels: the
 // camera ray of every pixel, formed in the kernel, and only the planes of its hit record that were asked for; and the camera ray of a
-// pixel (vrt_camera_pixel_ray).  A query sees the scene as the next frame would: the structures
+// pixel (vrt_camera_pixel_ray); and the volume queries (vrt_get_voxels, vrt_query_boxes and their _device forms), modes 2 and 3 of the
+// same two kernels, which read bindings 2-6 only.  A ray query sees the scene as the next frame would: the structures
 // derived from the scene buffers are refreshed through the frames' own path (refresh_derived) on the primary stream, after every upload
 // so far.  The kernels are compiled with the product's arithmetic flags, so that a query is bit-equal to the shader's GridHit
 // (vrt_math.h's contract).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include "vrt_ctx.h"
@@ -17,6 +19,8 @@ namespace vrt {
 
 static_assert(sizeof(vrt_ray_query) == 32, "vrt_ray_query is two dwordx4");
 static_assert(sizeof(vrt_ray_hit) == 48, "vrt_ray_hit is three dwordx4");
+static_assert(sizeof(vrt_box_query) == 32 && sizeof(vrt_box_result) == 32, "vrt_box_query and vrt_box_result are two dwordx4 each");
+static_assert(offsetof(vrt_box_query, flags) == 24 && offsetof(vrt_box_result, count) == 24, "the kernel reads flags and writes count at dword 6");
 
 // The one kernel argument of vrt_ray_query_b4 / _b8: the scene as the frames see it, and one launch's share of the batch.
 struct QueryArgs {
@@ -34,13 +38,21 @@ struct QueryArgs {
     u32x4 *aux_point_t;        // dwords 0..3 of vrt_ray_hit (16-byte aligned, like the next two)
     u32x4 *aux_normal_material; // dwords 4..7
     u32x4 *aux_voxel_hit;      // dwords 8..11
+    // modes 2 and 3 (the volume queries): n voxels, one per lane, or n boxes, one per wave; rays and hits are not read
+    const uint32_t *vol_xyz;   // mode 2: x, y, z per voxel, y as vrt_grid_insert takes it
+    uint16_t *vol_materials;   // mode 2: the material entry, or VRT_VOXEL_EMPTY
+    const u32x4 *vol_boxes;    // mode 3: vrt_box_query as two dwordx4 (16-byte aligned, like the results)
+    u32x4 *vol_results;        // mode 3: vrt_box_result as two dwordx4
+    uint32_t vol_bricks;       // brick_alloc: a loaded cell that names a brick beyond it (no scene an edit or a host grid made) reads as empty
 };
-constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u;
+constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u, kQueryModeVoxels = 2u, kQueryModeBoxes = 3u;
 
 constexpr uint32_t kQueryBlock = 256u;             // threads per workgroup: four waves, one ray per lane
 constexpr uint64_t kQueryLaunchRays = 1ull << 24;  // rays per launch (65 536 workgroups); larger batches are launched in pieces
 constexpr uint64_t kQueryHostPieceRays = 1ull << 20; // vrt_cast_rays: rays per round trip through the context's device buffers
 constexpr uint64_t kAuxMaxPixels = 1ull << 24;     // first-hit buffer pass: pixels of the camera's image (one launch; pixel indices stay 32-bit)
+constexpr uint32_t kBoxesPerGroup = kQueryBlock / 64u; // box queries: one wave per box
+constexpr uint64_t kQueryLaunchBoxes = 1ull << 22; // boxes per launch (2^20 workgroups)
 
 VRT_DI float as_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
 VRT_DI bool finite3(f3 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
@@ -93,11 +105,154 @@ VRT_DI void aux_query(const QueryArgs &a) {
     if (a.aux_voxel_hit) a.aux_voxel_hit[pixel] = h2;
 }
 
+// ---- The volume queries: what is at a place, read from bindings 2-6 alone ----
+// A cell answers only while its status bit is set: after a removal or a compaction brick_index of an unloaded cell is stale and may name
+// a brick that now belongs to another cell.
+
+VRT_DI bool cell_loaded(const TraceParams &p, uint32_t cell) { return (p.brick_status[cell >> 5] >> (cell & 31u)) & 1u; }
+
+// Mode 2: one voxel per lane; a wave reads 768 contiguous bytes of xyz and stores 128 of materials.
+template <int B>
+VRT_DI void voxel_query(const QueryArgs &a) {
+    constexpr uint32_t kBits = (uint32_t)(B * B * B);
+    const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t *src = a.vol_xyz + 3u * i;
+    const uint32_t x = src[0], y = src[1], z = src[2];
+    const vrt_grid_state &g = a.p.grid;
+    uint32_t material = VRT_VOXEL_EMPTY;
+    if (x < g.voxel_dim_x && y < g.voxel_dim_y && z < g.voxel_dim_z) {
+        const uint32_t fy = g.voxel_dim_y - 1u - y;                                                      // Grid.zig:135
+        const uint32_t cell = x / (uint32_t)B + g.dim_x * (z / (uint32_t)B + g.dim_z * (fy / (uint32_t)B)); // gridAt
+        if (cell_loaded(a.p, cell)) {
+            const uint32_t brick = a.p.brick_index[cell];
+            const uint32_t nth_bit = (x % (uint32_t)B) + (uint32_t)B * ((z % (uint32_t)B) + (uint32_t)B * (fy % (uint32_t)B)); // voxelAt
+            if (brick < a.vol_bricks && ((a.p.brick_occupancy[brick * (kBits / 8u) + (nth_bit >> 3)] >> (nth_bit & 7u)) & 1u)) {
+                const uint32_t entry = (a.p.brick_start_index[brick] & 0x7FFFFFFFu) + nth_bit; // comp:422-425
+                if (entry < a.vol_bricks * kBits) material = a.p.material_index[entry];      // (brick_alloc * B^3 <= 2^31)
+            }
+        }
+    }
+    a.vol_materials[i] = (uint16_t)material;
+}
+
+// The bits [lo, hi] of every `width`-bit group of a 64-bit word (hi < width; ones: bit 0 of every group)
+VRT_DI uint64_t group_bits(uint32_t lo, uint32_t hi, uint64_t ones) { return ones * (uint64_t)(((2u << hi) - 1u) & ~((1u << lo) - 1u)); }
+// The whole `width`-bit groups [lo, hi] of a 64-bit word
+VRT_DI uint64_t group_range(uint32_t lo, uint32_t hi, uint32_t width) { return (~0ull >> (64u - width * (hi + 1u))) & (~0ull << (width * lo)); }
+
+// Mode 3: one wave per box.  With nth_bit = x + B (z + B y) and y flipped, one y layer of an 8^3 brick is one 64-bit word of eight z rows
+// of eight x bits, and a whole 4^3 brick one word of four layers of four rows of four bits.  The wave clips the box and turns it into a
+// range of cells; its lanes stride over the words of those cells (cell-major, the eight layers of a cell on adjacent lanes), skip the
+// cells whose status bit is 0 before any other load, and count word & mask, the mask being box intersected with cell.  The bounds come
+// from the first and last set bit of the rows' OR (x), of the word (z, and y of a 4^3 brick) and from the layer (y of an 8^3 brick).
+template <int B>
+VRT_DI void box_query(const QueryArgs &a) {
+    constexpr uint32_t kWords = B == 8 ? 8u : 1u;    // 64-bit occupancy words per brick
+    constexpr uint32_t kStride = 64u / kWords;       // cells a wave covers per trip
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t box = (uint64_t)blockIdx.x * kBoxesPerGroup + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (box >= a.n) return; // (uniform over the wave, like every branch up to the loop)
+    const u32x4 q0 = a.vol_boxes[2u * box], q1 = a.vol_boxes[2u * box + 1u]; // lo.xyz hi.x | hi.yz flags _reserved
+    const vrt_grid_state &g = a.p.grid;
+    // clipped to the grid, in 64 bits: the corners are signed and a voxel dimension may exceed 2^31
+    const int64_t lox = std::max<int64_t>((int32_t)q0.x, 0), hix = std::min<int64_t>((int32_t)q0.w, (int64_t)g.voxel_dim_x - 1);
+    const int64_t loy = std::max<int64_t>((int32_t)q0.y, 0), hiy = std::min<int64_t>((int32_t)q1.x, (int64_t)g.voxel_dim_y - 1);
+    const int64_t loz = std::max<int64_t>((int32_t)q0.z, 0), hiz = std::min<int64_t>((int32_t)q1.y, (int64_t)g.voxel_dim_z - 1);
+    uint64_t count = 0;
+    uint32_t min_x = ~0u, min_y = ~0u, min_z = ~0u, max_x = 0u, max_y = 0u, max_z = 0u; // (y flipped)
+    if ((q1.z | q1.w) == 0u && lox <= hix && loy <= hiy && loz <= hiz) { // unknown flags, an inverted box, a box outside: empty
+        const uint32_t x0 = (uint32_t)lox, x1 = (uint32_t)hix, z0 = (uint32_t)loz, z1 = (uint32_t)hiz;
+        const uint32_t y0 = g.voxel_dim_y - 1u - (uint32_t)hiy, y1 = g.voxel_dim_y - 1u - (uint32_t)loy; // Grid.zig:135
+        const uint32_t cx0 = x0 / (uint32_t)B, cy0 = y0 / (uint32_t)B, cz0 = z0 / (uint32_t)B;
+        const uint32_t ncx = x1 / (uint32_t)B - cx0 + 1u, ncy = y1 / (uint32_t)B - cy0 + 1u, ncz = z1 / (uint32_t)B - cz0 + 1u;
+        const uint64_t *occupancy = reinterpret_cast<const uint64_t *>(a.p.brick_occupancy);
+        // the lane's word and cell of the range, advanced by kStride cells per trip (a carry may pass several rows: ncx < kStride)
+        const uint32_t word = lane % kWords;
+        uint32_t cx = (lane / kWords) % ncx, cz = (lane / kWords) / ncx % ncz, cy = (lane / kWords) / ncx / ncz;
+        while (cy < ncy) {
+            const uint32_t gx = cx0 + cx, gy = cy0 + cy, gz = cz0 + cz;
+            const uint32_t cell = gx + g.dim_x * (gz + g.dim_z * gy); // gridAt
+            if (cell_loaded(a.p, cell)) {
+                const uint32_t brick = a.p.brick_index[cell];
+                const uint32_t bx = gx * (uint32_t)B, by = gy * (uint32_t)B, bz = gz * (uint32_t)B;
+                const uint32_t xl = x0 > bx ? x0 - bx : 0u, xh = std::min(x1 - bx, (uint32_t)B - 1u);
+                const uint32_t zl = z0 > bz ? z0 - bz : 0u, zh = std::min(z1 - bz, (uint32_t)B - 1u);
+                uint64_t mask;
+                if constexpr (B == 8) {
+                    mask = (by + word >= y0 && by + word <= y1) ? group_bits(xl, xh, 0x0101010101010101ull) & group_range(zl, zh, 8u) : 0ull;
+                } else {
+                    const uint32_t yl = y0 > by ? y0 - by : 0u, yh = std::min(y1 - by, 3u);
+                    mask = group_bits(xl, xh, 0x1111111111111111ull) & (0x0001000100010001ull * (group_range(zl, zh, 4u) & 0xFFFFull)) & group_range(yl, yh, 16u);
+                }
+                const uint64_t m = (brick < a.vol_bricks && mask) ? occupancy[(uint64_t)brick * kWords + word] & mask : 0ull;
+                if (m) {
+                    count += (uint64_t)__builtin_popcountll(m);
+                    const uint32_t first = (uint32_t)__builtin_ctzll(m), last = 63u - (uint32_t)__builtin_clzll(m);
+                    uint32_t rows = (uint32_t)m | (uint32_t)(m >> 32); // the OR of the x rows
+                    rows |= rows >> 16;
+                    rows |= rows >> 8;
+                    uint32_t zf, zl_, yf, yl_;
+                    if constexpr (B == 8) {
+                        rows &= 0xFFu;
+                        zf = first >> 3, zl_ = last >> 3, yf = yl_ = word;
+                    } else {
+                        const uint32_t layers = ((uint32_t)m | (uint32_t)(m >> 32)); // the OR of the y layers, 16 bits after the fold
+                        const uint32_t layer = (layers | (layers >> 16)) & 0xFFFFu;
+                        rows = (rows | (rows >> 4)) & 0xFu;
+                        zf = (uint32_t)__builtin_ctz(layer) >> 2, zl_ = (31u - (uint32_t)__builtin_clz(layer)) >> 2, yf = first >> 4, yl_ = last >> 4;
+                    }
+                    min_x = std::min(min_x, bx + (uint32_t)__builtin_ctz(rows));
+                    max_x = std::max(max_x, bx + 31u - (uint32_t)__builtin_clz(rows));
+                    min_z = std::min(min_z, bz + zf);
+                    max_z = std::max(max_z, bz + zl_);
+                    min_y = std::min(min_y, by + yf);
+                    max_y = std::max(max_y, by + yl_);
+                }
+            }
+            cx += kStride;
+            const uint32_t carry_x = cx / ncx;
+            cx -= carry_x * ncx;
+            cz += carry_x;
+            const uint32_t carry_z = cz / ncz;
+            cz -= carry_z * ncz;
+            cy += carry_z;
+        }
+        // over the wave, in registers
+        for (int offset = 32; offset > 0; offset >>= 1) {
+            count += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(count >> 32), offset) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)count, offset);
+            min_x = std::min(min_x, (uint32_t)__shfl_xor((int)min_x, offset));
+            min_y = std::min(min_y, (uint32_t)__shfl_xor((int)min_y, offset));
+            min_z = std::min(min_z, (uint32_t)__shfl_xor((int)min_z, offset));
+            max_x = std::max(max_x, (uint32_t)__shfl_xor((int)max_x, offset));
+            max_y = std::max(max_y, (uint32_t)__shfl_xor((int)max_y, offset));
+            max_z = std::max(max_z, (uint32_t)__shfl_xor((int)max_z, offset));
+        }
+    }
+    if (lane != 0u) return;
+    u32x4 r0 = {0u, 0u, 0u, 0u}, r1 = r0; // lo.xyz hi.x | hi.yz count
+    if (count) {
+        // y as vrt_grid_insert counts it: the largest flipped y is the smallest y
+        r0 = u32x4{min_x, g.voxel_dim_y - 1u - max_y, min_z, max_x};
+        r1 = u32x4{g.voxel_dim_y - 1u - min_y, max_z, (uint32_t)count, (uint32_t)(count >> 32)};
+    }
+    a.vol_results[2u * box] = r0;
+    a.vol_results[2u * box + 1u] = r1;
+}
+
 // One GridHit of the frames' own walk per ray, one ray per lane.
 template <int B>
 VRT_DI void ray_query(const QueryArgs &a) {
     if (a.mode == kQueryModeAux) { // (uniform)
         aux_query<B>(a);
+        return;
+    }
+    if (a.mode == kQueryModeVoxels) {
+        voxel_query<B>(a);
+        return;
+    }
+    if (a.mode == kQueryModeBoxes) {
+        box_query<B>(a);
         return;
     }
     const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
@@ -170,6 +325,64 @@ int launch_queries(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_
         a.hits = hits + first;
         a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchRays);
         const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
+        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
+    }
+    return VRT_OK;
+}
+
+// The host paths' two device buffers hold at least `want` rays (32 bytes in, 48 bytes out each)
+int query_buffers(vrt_ctx *ctx, uint64_t want) {
+    if (ctx->query_capacity >= want) return VRT_OK;
+    VRT_HIP(ctx, wait_stream(ctx->stream)); // (the previous query may still use the buffers)
+    ctx->res.drop(ctx->d_query_rays);
+    ctx->res.drop(ctx->d_query_hits);
+    ctx->query_capacity = 0;
+    VRT_HIP(ctx, ctx->res.device(&ctx->d_query_rays, want * sizeof(vrt_ray_query)));
+    VRT_HIP(ctx, ctx->res.device(&ctx->d_query_hits, want * sizeof(vrt_ray_hit)));
+    ctx->query_capacity = want;
+    return VRT_OK;
+}
+
+// What the volume queries check of the context.  They read bindings 2-6 alone, which every upload and edit writes on the primary stream:
+// launched there they see the scene as it is after every upload and edit so far, and no derived structure has to be current.
+int volume_begin(vrt_ctx *ctx) {
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, "volume queries are not available on a context of the multi-GPU pipeline");
+    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    const vrt_grid_state &g = ctx->params.grid;
+    if (g.dim_x != ctx->cfg.dim_x || g.dim_y != ctx->cfg.dim_y || g.dim_z != ctx->cfg.dim_z) // (the buffers are sized for the context's cells)
+        return fail(ctx, VRT_E_INVALID_ARG, "uploaded grid state has other brick dimensions than the context was created with");
+    return VRT_OK;
+}
+
+vrt::QueryArgs volume_args(vrt_ctx *ctx, uint32_t mode) {
+    vrt::QueryArgs a{};
+    a.p = ctx->params;
+    a.mode = mode;
+    a.vol_bricks = (uint32_t)ctx->cfg.brick_alloc; // (brick_alloc * B^3 <= 2^31)
+    return a;
+}
+
+// n voxels at `xyz` (device memory) -> out, in launches of at most kQueryLaunchRays voxels, on the primary stream
+int launch_voxel_queries(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
+    vrt::QueryArgs a = volume_args(ctx, vrt::kQueryModeVoxels);
+    for (uint64_t first = 0; first < n; first += vrt::kQueryLaunchRays) {
+        a.vol_xyz = xyz + 3u * first;
+        a.vol_materials = out + first;
+        a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchRays);
+        const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
+        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
+    }
+    return VRT_OK;
+}
+
+// n boxes at `boxes` (device memory) -> results, in launches of at most kQueryLaunchBoxes boxes, on the primary stream
+int launch_box_queries(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
+    vrt::QueryArgs a = volume_args(ctx, vrt::kQueryModeBoxes);
+    for (uint64_t first = 0; first < n; first += vrt::kQueryLaunchBoxes) {
+        a.vol_boxes = reinterpret_cast<const vrt::u32x4 *>(boxes + first);
+        a.vol_results = reinterpret_cast<vrt::u32x4 *>(results + first);
+        a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchBoxes);
+        const dim3 groups((uint32_t)((a.n + vrt::kBoxesPerGroup - 1u) / vrt::kBoxesPerGroup));
         VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
     }
     return VRT_OK;
@@ -292,21 +505,86 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_h
     if (rc != VRT_OK) return rc;
     // through the context's two device buffers, a piece of at most kQueryHostPieceRays rays at a time
     const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
-    if (ctx->query_capacity < want) {
-        VRT_HIP(ctx, wait_stream(ctx->stream)); // (the previous query may still use the buffers)
-        ctx->res.drop(ctx->d_query_rays);
-        ctx->res.drop(ctx->d_query_hits);
-        ctx->query_capacity = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_query_rays, want * sizeof(vrt_ray_query)));
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_query_hits, want * sizeof(vrt_ray_hit)));
-        ctx->query_capacity = want;
-    }
+    rc = query_buffers(ctx, want);
+    if (rc != VRT_OK) return rc;
     for (uint64_t first = 0; first < n; first += want) {
         const uint64_t m = std::min(n - first, want);
         VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays + first, m * sizeof(vrt_ray_query), hipMemcpyHostToDevice, ctx->stream));
         rc = launch_queries(ctx, ctx->d_query_rays, m, ctx->d_query_hits);
         if (rc != VRT_OK) return rc;
         VRT_HIP(ctx, hipMemcpyAsync(hits + first, ctx->d_query_hits, m * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VRT_HIP(ctx, wait_stream(ctx->stream));
+    return VRT_OK;
+}
+
+int vrt_get_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!xyz || !out) return fail(ctx, VRT_E_INVALID_ARG, "xyz or out is NULL");
+    if ((reinterpret_cast<uintptr_t>(xyz) & 3u) || (reinterpret_cast<uintptr_t>(out) & 1u)) return fail(ctx, VRT_E_INVALID_ARG, "xyz must be 4-byte and out 2-byte aligned");
+    DeviceGuard dg(ctx->device);
+    const int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    return launch_voxel_queries(ctx, xyz, n, out);
+}
+
+int vrt_get_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!xyz || !out) return fail(ctx, VRT_E_INVALID_ARG, "xyz or out is NULL");
+    DeviceGuard dg(ctx->device);
+    int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    // through the ray queries' two device buffers (12 bytes in, 2 bytes out per voxel: a ray's share holds both), a piece at a time
+    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
+    rc = query_buffers(ctx, want);
+    if (rc != VRT_OK) return rc;
+    uint32_t *d_xyz = reinterpret_cast<uint32_t *>(ctx->d_query_rays);
+    uint16_t *d_out = reinterpret_cast<uint16_t *>(ctx->d_query_hits);
+    for (uint64_t first = 0; first < n; first += want) {
+        const uint64_t m = std::min(n - first, want);
+        VRT_HIP(ctx, hipMemcpyAsync(d_xyz, xyz + 3u * first, m * 3u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_voxel_queries(ctx, d_xyz, m, d_out);
+        if (rc != VRT_OK) return rc;
+        VRT_HIP(ctx, hipMemcpyAsync(out + first, d_out, m * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VRT_HIP(ctx, wait_stream(ctx->stream));
+    return VRT_OK;
+}
+
+int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!boxes || !results) return fail(ctx, VRT_E_INVALID_ARG, "boxes or results is NULL");
+    if ((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(results)) & 15u) return fail(ctx, VRT_E_INVALID_ARG, "boxes and results must be 16-byte aligned");
+    DeviceGuard dg(ctx->device);
+    const int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    return launch_box_queries(ctx, boxes, n, results);
+}
+
+int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!boxes || !results) return fail(ctx, VRT_E_INVALID_ARG, "boxes or results is NULL");
+    for (uint64_t i = 0; i < n; i++)
+        if (boxes[i].flags | boxes[i]._reserved) return fail(ctx, VRT_E_INVALID_ARG, "box " + std::to_string(i) + " has unknown flag bits or a non-zero _reserved");
+    DeviceGuard dg(ctx->device);
+    int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    // through the ray queries' two device buffers (32 bytes in, 32 bytes out per box), a piece at a time
+    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
+    rc = query_buffers(ctx, want);
+    if (rc != VRT_OK) return rc;
+    vrt_box_query *d_boxes = reinterpret_cast<vrt_box_query *>(ctx->d_query_rays);
+    vrt_box_result *d_results = reinterpret_cast<vrt_box_result *>(ctx->d_query_hits);
+    for (uint64_t first = 0; first < n; first += want) {
+        const uint64_t m = std::min(n - first, want);
+        VRT_HIP(ctx, hipMemcpyAsync(d_boxes, boxes + first, m * sizeof(vrt_box_query), hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_box_queries(ctx, d_boxes, m, d_results);
+        if (rc != VRT_OK) return rc;
+        VRT_HIP(ctx, hipMemcpyAsync(results + first, d_results, m * sizeof(vrt_box_result), hipMemcpyDeviceToHost, ctx->stream));
     }
     VRT_HIP(ctx, wait_stream(ctx->stream));
     return VRT_OK;

@@ -87,6 +87,22 @@ class BrickGrid:
         check(lib.vrt_grid_compact(self._h, C.byref(out)))
         return int(out[0]), int(out[1])
 
+    def get_voxels(self, xyz) -> np.ndarray:
+        """vrt_grid_get_voxels: the material entry (0..255) of each voxel of xyz (n, 3), as insert_many takes it, or VOXEL_EMPTY where the
+        voxel is not solid or lies outside the grid; (n,) uint16."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty(xyz.shape[0], dtype=np.uint16)
+        check(lib.vrt_grid_get_voxels(self._h, xyz.ctypes.data, xyz.shape[0], out.ctypes.data))
+        return out
+
+    def query_boxes(self, lo, hi) -> np.ndarray:
+        """vrt_grid_query_boxes: per box of inclusive corners lo, hi (n, 3) in voxels (signed; clipped to the grid), a BOX_RESULT_DTYPE
+        record: the number of solid voxels and their tight bounds, all zero for none."""
+        q = box_queries(lo, hi)
+        out = np.zeros(q.shape[0], dtype=BOX_RESULT_DTYPE)
+        check(lib.vrt_grid_query_boxes(self._h, q.ctypes.data, q.shape[0], out.ctypes.data))
+        return out
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -243,6 +259,23 @@ AUX_PLANE_DTYPES = {
     "voxel_hit": np.dtype([("voxel", np.int32, 3), ("hit", np.uint32)]),
 }
 assert all(AUX_PLANE_DTYPES[k].itemsize == 16 for k in AUX_PLANES[1:])
+
+
+# vrt_box_query / vrt_box_result (include/vrt_hip.h) as numpy records, and what a look-up gives for a voxel that is not solid
+BOX_QUERY_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("flags", np.uint32), ("_reserved", np.uint32)])
+BOX_RESULT_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("count", np.uint64)])
+assert BOX_QUERY_DTYPE.itemsize == 32 and BOX_RESULT_DTYPE.itemsize == 32
+VOXEL_EMPTY = L.VOXEL_EMPTY
+
+
+def box_queries(lo, hi) -> np.ndarray:
+    """Host records of vrt_box_query: inclusive corners lo, hi (n, 3) in voxels, signed."""
+    lo = np.asarray(lo, dtype=np.int32).reshape(-1, 3)
+    hi = np.asarray(hi, dtype=np.int32).reshape(-1, 3)
+    assert lo.shape == hi.shape
+    q = np.zeros(lo.shape[0], dtype=BOX_QUERY_DTYPE)
+    q["lo"], q["hi"] = lo, hi
+    return q
 
 
 def ray_queries(origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
@@ -518,6 +551,47 @@ class VoxelRT:
             return self.config.device_id
         import torch
         return torch.cuda.current_device()
+
+    # -- volume queries ---------------------------------------------------------
+    def get_voxels(self, xyz) -> np.ndarray:
+        """What is at each voxel of xyz (n, 3), in the coordinates insert_voxels takes, in the scene the context holds (vrt_get_voxels):
+        the material entry (0..255), or VOXEL_EMPTY where the voxel is not solid or lies outside the grid; (n,) uint16.  Sees every
+        edit so far.  Given a torch tensor on the GPU, the voxels are read and answered in device memory (vrt_get_voxels_device, behind
+        torch's current stream) and only the answers are copied back."""
+        if getattr(xyz, "is_cuda", False):
+            import torch
+            x = xyz.reshape(-1, 3).to(torch.int32).contiguous()
+            out = torch.empty(x.shape[0], dtype=torch.int16, device=x.device)
+            torch.cuda.current_stream(x.device).synchronize()  # (the voxels are written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_get_voxels_device(self._h, x.data_ptr(), x.shape[0], out.data_ptr()))
+            self.wait()
+            return out.cpu().numpy().view(np.uint16)
+        x = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
+        out = np.empty(x.shape[0], dtype=np.uint16)
+        self._check(self._lib.vrt_get_voxels(self._h, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
+
+    def query_boxes(self, lo, hi) -> np.ndarray:
+        """Per box of inclusive corners lo, hi (n, 3) in voxels (signed; clipped to the grid), a BOX_RESULT_DTYPE record: the number of
+        solid voxels of the scene the context holds and their tight bounds, all zero for none (vrt_query_boxes).  Sees every edit so
+        far.  Given torch tensors on the GPU, the boxes are formed and answered in device memory (vrt_query_boxes_device, behind
+        torch's current stream) and only the results are copied back."""
+        if getattr(lo, "is_cuda", False):
+            import torch
+            lo_t = lo.reshape(-1, 3)
+            n = lo_t.shape[0]
+            q = torch.zeros((n, 8), dtype=torch.int32, device=lo_t.device)
+            q[:, 0:3] = lo_t
+            q[:, 3:6] = torch.as_tensor(hi, device=lo_t.device).reshape(-1, 3)
+            results = torch.empty((n, 8), dtype=torch.int32, device=lo_t.device)
+            torch.cuda.current_stream(lo_t.device).synchronize()  # (the boxes are written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_query_boxes_device(self._h, q.data_ptr(), n, results.data_ptr()))
+            self.wait()
+            return results.cpu().numpy().view(BOX_RESULT_DTYPE).reshape(n)
+        q = box_queries(lo, hi)
+        results = np.zeros(q.shape[0], dtype=BOX_RESULT_DTYPE)
+        self._check(self._lib.vrt_query_boxes(self._h, q.ctypes.data, q.shape[0], results.ctypes.data))
+        return results
 
     def region_begin(self) -> None:
         self._check(self._lib.vrt_region_begin(self._h))
