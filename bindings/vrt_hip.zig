@@ -90,6 +90,18 @@ pub const BufferId = enum(c_int) {
     material_index = 6,
 };
 
+/// vrt_read_derived / vrt_derived_size: a test and diagnosis aid; the layouts are the library's own and may change
+pub const DerivedId = enum(c_int) {
+    cell_bounds = 0,
+    status_bytes = 1,
+    status_halfblocks = 2,
+    cell_occupancy = 3,
+    cell_material = 4,
+    cell_box = 5,
+    start_is_slot = 6,
+    materials_plain = 7,
+};
+
 // ---- data contract structs: field for field include/vrt_hip.h (checked by tests/test_abi.py) ----
 pub const GridState = extern struct { // State.Device, State.zig:60-79
     voxel_dim_x: u32,
@@ -370,6 +382,8 @@ pub extern fn vrt_remove_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c
 pub extern fn vrt_compact_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
+pub extern fn vrt_derived_size(ctx: ?*const Ctx, id: DerivedId) u64;
+pub extern fn vrt_read_derived(ctx: ?*Ctx, id: DerivedId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_camera_pixel_ray(cam: [*c]const CameraDevice, px: u32, py: u32, origin: *[3]f32, direction: *[3]f32) c_int;
 pub extern fn vrt_camera_init(vertical_fov_deg: f32, image_width: u32, image_height: u32, cfg: [*c]const CameraConfig, out: [*c]CameraDevice) c_int;
 pub extern fn vrt_camera_set_forward(cam: [*c]CameraDevice, vertical_fov_deg: f32, viewport_height: f32, forward: *const [3]f32) c_int;

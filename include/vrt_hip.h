@@ -652,6 +652,32 @@ int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *
 /* out[0] = allocated bricks A, out[1] = next material entry (MaterialAllocator's cursor), as the next insert continues them.
  * VRT_E_STATE: no grid state uploaded, or binding 5 not allocation-shaped. */
 int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]);
+/* ---- Read-back of the derived scene structures: a test and diagnosis aid -------------------------------------------------
+ * Frames and ray queries walk structures the library derives from bindings 1-6 and keeps current itself.  This pair copies one of
+ * them out, so that a test can compare it with a model of its definition.  THE LAYOUTS ARE THE LIBRARY'S OWN AND MAY CHANGE with any
+ * release, as may which contexts keep which structure: nothing but tests and diagnosis tools should call these.
+ * vrt_derived_size: the structure's logical size in bytes, without the allocation's padding — cell_bounds 24 ({max -x, max -y, max -z,
+ * max x, max y, max z} of the loaded cells, int32), status_bytes 32 per status word, status_halfblocks 4 * (cells / 32),
+ * cell_occupancy cells * B^3 / 8, cell_material cells, cell_box 4 * cells, each flag 4 — or 0: this context keeps none (no kernel it
+ * selects reads it), a NULL ctx or a bad id.
+ * vrt_read_derived: bytes [byte_offset, byte_offset + nbytes) of the structure as the next frame or query would see it: the
+ * structures are brought up to date behind every upload and edit so far, then copied on the primary stream (blocking; no vrt_wait is
+ * needed in between, no kernel of its own is launched).  VRT_E_INVALID_ARG: a NULL ctx, a bad id or a NULL dst with nbytes > 0;
+ * VRT_E_OUT_OF_RANGE: beyond the structure's size; VRT_E_STATE: no grid state uploaded, a context of the multi-GPU pipeline, or a
+ * structure this context does not keep.  A failed call leaves the context usable. */
+typedef enum vrt_derived_id {
+    VRT_DERIVED_CELL_BOUNDS = 0,
+    VRT_DERIVED_STATUS_BYTES = 1,
+    VRT_DERIVED_STATUS_HALFBLOCKS = 2,
+    VRT_DERIVED_CELL_OCCUPANCY = 3,
+    VRT_DERIVED_CELL_MATERIAL = 4,
+    VRT_DERIVED_CELL_BOX = 5,
+    VRT_DERIVED_START_IS_SLOT = 6,
+    VRT_DERIVED_MATERIALS_PLAIN = 7,
+    VRT_DERIVED_COUNT = 8
+} vrt_derived_id;
+uint64_t vrt_derived_size(const vrt_ctx *ctx, vrt_derived_id id);
+int vrt_read_derived(vrt_ctx *ctx, vrt_derived_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);
 
 /* the un-normalised direction and the origin of the one-sample camera ray the frame traces for pixel (px, py), with
  * (px, py) as in the image vrt_read_rgba8 returns (CameraGetRay, comp:474-477, without jitter).  VRT_E_INVALID_ARG: a NULL

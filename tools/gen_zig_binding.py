@@ -24,7 +24,7 @@ STRUCTS = {"vrt_ctx": "Ctx", "vrt_grid": "Grid", "vrt_vox": "Vox", "vrt_benchmar
            "vrt_box_query": "BoxQuery", "vrt_box_result": "BoxResult"}
 OPAQUE = {"Ctx", "Grid", "Vox", "Benchmark"}
 SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64", "uint8_t": "u8", "uint16_t": "u16", "float": "f32",
-           "double": "f64", "void": "void", "vrt_buffer_id": "BufferId"}
+           "double": "f64", "void": "void", "vrt_buffer_id": "BufferId", "vrt_derived_id": "DerivedId"}
 
 
 def prototypes(text: str):

@@ -50,6 +50,12 @@ TUNE_NO_PATH_POOL = 8192  # frames with bounces on scenes larger than the caches
 BUF_GRID_STATE, BUF_MATERIALS, BUF_BRICK_STATUS, BUF_BRICK_INDEX, BUF_BRICK_OCCUPANCY, BUF_BRICK_START_INDEX, BUF_MATERIAL_INDEX = range(7)
 BUF_COUNT = 7
 
+# vrt_derived_id — the structures the library derives from the scene (vrt_read_derived: a test and diagnosis aid)
+(DERIVED_CELL_BOUNDS, DERIVED_STATUS_BYTES, DERIVED_STATUS_HALFBLOCKS, DERIVED_CELL_OCCUPANCY, DERIVED_CELL_MATERIAL, DERIVED_CELL_BOX,
+ DERIVED_START_IS_SLOT, DERIVED_MATERIALS_PLAIN) = range(8)
+DERIVED_COUNT = 8
+DERIVED_NAMES = ("cell_bounds", "status_bytes", "status_halfblocks", "cell_occupancy", "cell_material", "cell_box", "start_is_slot", "materials_plain")
+
 
 class VrtError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -264,6 +270,8 @@ SIGNATURES = {
     "vrt_remove_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
     "vrt_read_buffer": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_scene_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
+    "vrt_derived_size": (C.c_uint64, [_ctx, C.c_int]),
+    "vrt_read_derived": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_compact_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
     "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),

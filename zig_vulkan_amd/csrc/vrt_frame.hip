@@ -400,6 +400,51 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
     return VRT_OK;
 }
 
+// where derived structure `id` lies and its logical size (0, nullptr: this context keeps none)
+static uint64_t derived_span(const vrt_ctx *ctx, vrt_derived_id id, const void **ptr) {
+    const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
+    const uint64_t b = ctx->cfg.brick_dimension;
+    const void *p = nullptr;
+    uint64_t n = 0;
+    switch (id) {
+    case VRT_DERIVED_CELL_BOUNDS: p = ctx->d_cell_bounds, n = 6u * sizeof(int); break;
+    case VRT_DERIVED_STATUS_BYTES: p = ctx->d_status_bytes, n = ((cells + 31u) / 32u) * 32u; break;
+    case VRT_DERIVED_STATUS_HALFBLOCKS: p = ctx->d_status_halfblocks, n = (cells / 32u) * 4u; break;
+    case VRT_DERIVED_CELL_OCCUPANCY: p = ctx->d_cell_occupancy, n = cells * (b * b * b / 8u); break;
+    case VRT_DERIVED_CELL_MATERIAL: p = ctx->d_cell_material, n = cells; break;
+    case VRT_DERIVED_CELL_BOX: p = ctx->d_cell_box, n = cells * 4u; break;
+    case VRT_DERIVED_START_IS_SLOT: p = ctx->d_start_is_slot, n = 4u; break;
+    case VRT_DERIVED_MATERIALS_PLAIN: p = ctx->d_materials_plain, n = 4u; break;
+    default: break;
+    }
+    if (ptr) *ptr = p;
+    return p ? n : 0u;
+}
+
+uint64_t vrt_derived_size(const vrt_ctx *ctx, vrt_derived_id id) {
+    if (!ctx || (int)id < 0 || id >= VRT_DERIVED_COUNT) return 0;
+    return derived_span(ctx, id, nullptr);
+}
+
+int vrt_read_derived(vrt_ctx *ctx, vrt_derived_id id, uint64_t byte_offset, void *dst, uint64_t nbytes) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if ((int)id < 0 || id >= VRT_DERIVED_COUNT) return fail(ctx, VRT_E_INVALID_ARG, "bad derived-structure id");
+    if (nbytes && !dst) return fail(ctx, VRT_E_INVALID_ARG, "dst is NULL");
+    const void *src = nullptr;
+    const uint64_t size = derived_span(ctx, id, &src);
+    if (src && (byte_offset > size || nbytes > size - byte_offset)) return fail(ctx, VRT_E_OUT_OF_RANGE, "read exceeds the derived structure");
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, "the derived structures are not read back on a context of the multi-GPU pipeline");
+    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    if (!src) return fail(ctx, VRT_E_STATE, "this context keeps no such derived structure (no kernel it selects reads it)");
+    if (nbytes == 0) return VRT_OK;
+    DeviceGuard dg(ctx->device);
+    const int rc = refresh_derived(ctx); // (on the primary stream, behind every upload and edit so far)
+    if (rc != VRT_OK) return rc;
+    VRT_HIP(ctx, hipMemcpyAsync(dst, static_cast<const uint8_t *>(src) + byte_offset, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    VRT_HIP(ctx, wait_stream(ctx->stream));
+    return VRT_OK;
+}
+
 int vrt_bounce_autotune_info(vrt_ctx *ctx, double out[4]) {
     if (!ctx || !out) return VRT_E_INVALID_ARG;
     out[0] = !ctx->bounce_auto || ctx->dist ? 0.0 : (!ctx->auto_decided ? 1.0 : (ctx->auto_use_pool ? 3.0 : 2.0));

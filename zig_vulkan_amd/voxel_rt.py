@@ -21,6 +21,8 @@ import numpy as np
 from . import _lib as L
 from ._lib import lib, check
 
+_DERIVED_DTYPES = {L.DERIVED_CELL_BOUNDS: np.int32, L.DERIVED_STATUS_HALFBLOCKS: np.uint32, L.DERIVED_CELL_BOX: np.uint32,
+                   L.DERIVED_START_IS_SLOT: np.uint32, L.DERIVED_MATERIALS_PLAIN: np.uint32}
 _GRID_ARRAY_DTYPES = {
     L.BUF_BRICK_STATUS: np.uint32,
     L.BUF_BRICK_INDEX: np.uint32,
@@ -459,6 +461,19 @@ class VoxelRT:
         if buf_id == L.BUF_MATERIALS:
             return out[:n - n % MATERIAL_DTYPE.itemsize].view(MATERIAL_DTYPE)
         return out.view(_GRID_ARRAY_DTYPES.get(buf_id, np.uint8))
+
+    def derived_size(self, derived_id: int) -> int:
+        """Logical size in bytes of derived structure `derived_id` (L.DERIVED_*), 0 where this context keeps none (vrt_derived_size)."""
+        return int(self._lib.vrt_derived_size(self._h, derived_id))
+
+    def read_derived(self, derived_id: int) -> np.ndarray:
+        """Copy of derived structure `derived_id` as the next frame or query would see it (vrt_read_derived: a test and diagnosis aid,
+        the layouts are the library's own), typed: int32 for cell_bounds, uint32 words for status_halfblocks, cell_box and the two
+        flags, bytes for status_bytes, cell_occupancy and cell_material."""
+        n = self.derived_size(derived_id)
+        out = np.empty(n, dtype=np.uint8)
+        self._check(self._lib.vrt_read_derived(self._h, derived_id, 0, out.ctypes.data, n))
+        return out.view(_DERIVED_DTYPES.get(derived_id, np.uint8))
 
     def scene_bricks(self) -> Tuple[int, int]:
         """(allocated bricks, next material entry) as the next insert continues them (vrt_scene_bricks)."""
