@@ -301,6 +301,18 @@ pub const BoxResult = extern struct {
     hi: [3]i32,
     count: u64,
 };
+/// One shape of vrt_fill_shapes / vrt_clear_shapes, 32 bytes, in the coordinates vrt_grid_insert takes; clipped to the grid.
+/// Box: lo / hi are the inclusive corners.  Sphere: lo is the centre, hi[0] the radius (0..SHAPE_MAX_RADIUS), hi[1] = hi[2] = 0.
+pub const SHAPE_BOX: u32 = 0;
+pub const SHAPE_SPHERE: u32 = 1;
+pub const SHAPE_MAX_RADIUS: i32 = 16384;
+pub const SHAPES_MAX: u32 = 4096;
+pub const Shape = extern struct {
+    lo: [3]i32,
+    hi: [3]i32,
+    kind: u32 = SHAPE_BOX,
+    material: u32 = 0, // fill: 0..255, the material_indices byte; clear: 0
+};
 
 // BEGIN GENERATED extern declarations (tools/gen_zig_binding.py from include/vrt_hip.h) — do not edit by hand
 pub extern fn vrt_create(cfg: [*c]const Config, out: *?*Ctx) c_int;
@@ -380,6 +392,10 @@ pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_remove_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_compact_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
+pub extern fn vrt_grid_fill_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c_int;
+pub extern fn vrt_grid_clear_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c_int;
+pub extern fn vrt_fill_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;
+pub extern fn vrt_clear_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_derived_size(ctx: ?*const Ctx, id: DerivedId) u64;

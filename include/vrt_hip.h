@@ -646,6 +646,52 @@ int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
  * grid state and for one of the multi-GPU pipeline.  out (may be NULL) = {A, L}, on success.  The derived structures are refreshed for
  * the written ranges (the renamed cells, the filled holes, the cleared tail) before the next frame or query. */
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]);
+/* ---- Shape edits on the uploaded scene: fill and clear boxes and spheres ---------------------------------------------------
+ * The write-side twin of vrt_query_boxes: a host that edits with a brush (dig a sphere, place a box) sends 32 bytes per shape and
+ * not 13 bytes per voxel, and the device works per 32-bit occupancy word, not per voxel (two more modes of the vrt_edit_* kernels).
+ *
+ * COORDINATES are those vrt_grid_insert takes, y counted as insert counts it, signed.  Geometry never fails: a shape is clipped to
+ * the grid and what lies outside is ignored, as vrt_query_boxes does; a box with lo > hi on any axis is empty; a shape wholly
+ * outside the grid is a no-op.  A SPHERE holds voxel (x, y, z) when dx^2 + dy^2 + dz^2 <= r^2 in integers, d = voxel - centre; only
+ * voxels of the grid within [centre - r, centre + r] are considered, that range formed in 64-bit arithmetic.
+ *
+ * DEFINITION BY ENUMERATION.  fill is vrt_grid_insert_many of the following voxel list (every voxel with its shape's material),
+ * clear is vrt_grid_remove_many of it, byte for byte on bindings 2-6: shapes in array order; within a shape the grid cells in which
+ * the shape has at least one voxel, in ascending grid index (cx + dim_x * (cz + dim_z * cy_flipped), the index into brick_indices);
+ * within a cell any order.  So a fill numbers its new bricks shape-major, then by cell index; a cell of a sphere's bounding box that
+ * holds none of its voxels gets no brick; a voxel inside several shapes keeps the LAST shape's material.  A clear takes the status
+ * bit of every cell whose brick it empties, does not reuse the brick (see vrt_remove_voxels) and writes no material byte.
+ *
+ * ERRORS, all or nothing, on the host twins too (they count first; they do not stop partway as vrt_grid_insert_many does).
+ * VRT_E_INVALID_ARG: a NULL ctx or grid; NULL shapes with n > 0; n > VRT_SHAPES_MAX; an unknown kind; a fill material above 255 or a
+ * clear material other than 0; a sphere with r < 0, r > VRT_SHAPE_MAX_RADIUS, or hi[1] or hi[2] other than 0 — the error text names
+ * the shape.  VRT_E_OUT_OF_RANGE: the batch's work items (one per occupancy word of every cell of every shape's clipped cell box)
+ * would reach 2^31.  VRT_E_OOM: a fill needs more bricks or material entries than brick_alloc leaves.  VRT_E_STATE as for
+ * vrt_insert_voxels: no grid state uploaded, binding 5 not allocation-shaped, a loaded cell naming a brick >= A, a context of the
+ * multi-GPU pipeline.  n == 0, or every shape empty after clipping: VRT_OK, and the device is not touched.
+ *
+ * ORDERING AND STAGING as for vrt_insert_voxels: one scene write on the context's stream, one small status read-back ends the
+ * call; the derived structures are refreshed for the written ranges, so frames and queries issued right after see the edit without
+ * a vrt_wait.  There is no _device form: the host needs the shapes to size the launch.
+ *
+ * THE HOST TWINS give a vrt_grid the bytes and exactly the vrt_grid_delta ranges that vrt_grid_insert_many / vrt_grid_remove_many
+ * give it on the defining list; they work per cell and row. */
+#define VRT_SHAPE_BOX    0u
+#define VRT_SHAPE_SPHERE 1u
+#define VRT_SHAPE_MAX_RADIUS 16384
+#define VRT_SHAPES_MAX 4096u
+typedef struct vrt_shape {          /* 32 bytes */
+    int32_t lo[3];                  /* BOX: inclusive low corner.  SPHERE: centre                              */
+    int32_t hi[3];                  /* BOX: inclusive high corner. SPHERE: hi[0] = radius r, hi[1] = hi[2] = 0 */
+    uint32_t kind;                  /* VRT_SHAPE_BOX / VRT_SHAPE_SPHERE                                        */
+    uint32_t material;              /* fill: 0..255, the material_indices byte; clear: must be 0               */
+} vrt_shape;
+/* the CPU twins on a host grid */
+int vrt_grid_fill_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n);
+int vrt_grid_clear_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n);
+/* on the scene the context holds; shapes in host memory */
+int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n);
+int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n);
 /* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);

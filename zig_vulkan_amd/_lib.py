@@ -173,12 +173,19 @@ class BoxResult(C.Structure):  # vrt_box_result (32 bytes)
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("count", C.c_uint64)]
 
 
+class Shape(C.Structure):  # vrt_shape (32 bytes)
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("kind", C.c_uint32), ("material", C.c_uint32)]
+
+
+SHAPE_BOX, SHAPE_SPHERE = 0, 1  # VRT_SHAPE_BOX, VRT_SHAPE_SPHERE
+SHAPE_MAX_RADIUS = 16384        # VRT_SHAPE_MAX_RADIUS
+SHAPES_MAX = 4096               # VRT_SHAPES_MAX
 RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
 VOXEL_EMPTY = 0xFFFF        # VRT_VOXEL_EMPTY
 
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
-assert C.sizeof(BoxQuery) == 32 and C.sizeof(BoxResult) == 32
+assert C.sizeof(BoxQuery) == 32 and C.sizeof(BoxResult) == 32 and C.sizeof(Shape) == 32
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -273,6 +280,10 @@ SIGNATURES = {
     "vrt_derived_size": (C.c_uint64, [_ctx, C.c_int]),
     "vrt_read_derived": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_compact_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
+    "vrt_grid_fill_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
+    "vrt_grid_clear_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
+    "vrt_fill_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
+    "vrt_clear_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
     "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),
     "vrt_camera_set_forward": (C.c_int, [_P(CameraDevice), C.c_float, C.c_float, _P(C.c_float * 3)]),

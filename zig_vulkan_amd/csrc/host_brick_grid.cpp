@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <limits>
 #include <new>
+#include <string>
 
 namespace vrt {
 
@@ -304,6 +305,145 @@ void BrickGrid::queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_resul
         }
         results[i] = r;
     }
+}
+
+bool BrickGrid::shapeRows(const ClippedShape &s, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t rows[64]) const {
+    const uint32_t b = brick_dimension_;
+    std::fill(rows, rows + b * b, (uint8_t)0);
+    const uint32_t x0 = std::max(s.lo[0], cx * b), x1 = std::min(s.hi[0], cx * b + (b - 1u));
+    if (x0 > x1) return false;
+    const uint32_t box_mask = ((1u << (x1 - x0 + 1u)) - 1u) << (x0 - cx * b); // as queryBoxes clips a row
+    uint32_t any = 0;
+    for (uint32_t fy = std::max(s.lo[1], cy * b); fy <= std::min(s.hi[1], cy * b + (b - 1u)); fy++)
+        for (uint32_t z = std::max(s.lo[2], cz * b); z <= std::min(s.hi[2], cz * b + (b - 1u)); z++) {
+            uint32_t mask = box_mask;
+            if (s.kind == VRT_SHAPE_SPHERE) {
+                const int64_t dy = (int32_t)(fy - s.centre[1]), dz = (int32_t)(z - s.centre[2]);
+                const int64_t rem = (int64_t)s.r2 - dy * dy - dz * dz;
+                mask = 0;
+                for (uint32_t x = x0; x <= x1 && rem >= 0; x++) {
+                    const int64_t dx = (int32_t)(x - s.centre[0]);
+                    if (dx * dx <= rem) mask |= 1u << (x - cx * b);
+                }
+            }
+            rows[(z - cz * b) + b * (fy - cy * b)] = (uint8_t)mask; // voxelAt of the row's x = 0, over B
+            any |= mask;
+        }
+    return any != 0;
+}
+
+namespace {
+
+// f(cx, cy, cz, grid_index) for the cells of the shape's clipped box, in ascending grid index (gridAt)
+template <typename F>
+void for_cells(const ClippedShape &s, uint32_t b, const vrt_grid_state &d, F f) {
+    for (uint32_t cy = s.lo[1] / b; cy <= s.hi[1] / b; cy++)
+        for (uint32_t cz = s.lo[2] / b; cz <= s.hi[2] / b; cz++)
+            for (uint32_t cx = s.lo[0] / b; cx <= s.hi[0] / b; cx++)
+                f(cx, cy, cz, (size_t)cx + (size_t)d.dim_x * ((size_t)cz + (size_t)d.dim_z * (size_t)cy));
+}
+
+int clip_batch(const vrt_shape *shapes, uint64_t n, bool fill, const vrt_grid_state &d, std::vector<ClippedShape> *out) {
+    std::string why;
+    const int rc = screen_shapes(shapes, n, fill, &why);
+    if (rc != VRT_OK) return rc;
+    const uint32_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
+    for (uint64_t i = 0; i < n; i++) {
+        ClippedShape c;
+        if (clip_shape(shapes[i], dim, &c)) out->push_back(c);
+    }
+    return VRT_OK;
+}
+
+} // namespace
+
+int BrickGrid::fillShapes(const vrt_shape *shapes, uint64_t n) {
+    const vrt_grid_state &d = device_state_;
+    const uint32_t b = brick_dimension_;
+    std::vector<ClippedShape> clipped;
+    int rc = clip_batch(shapes, n, true, d, &clipped);
+    if (rc != VRT_OK) return rc;
+    uint8_t rows[64];
+    // all or nothing: the cells that need a brick, counted before the first write
+    std::vector<size_t> fresh;
+    for (const ClippedShape &s : clipped)
+        for_cells(s, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (!shapeRows(s, cx, cy, cz, rows)) return;
+            if (!((brick_statuses[g / 32] >> (g % 32)) & 1u)) fresh.push_back(g);
+            else if (brick_indices[g] >= brick_alloc_ || brick_start_indices[brick_indices[g]] == 0xFFFFFFFFu) rc = VRT_E_STATE;
+        });
+    if (rc != VRT_OK) return rc;
+    std::sort(fresh.begin(), fresh.end());
+    const uint64_t need = (uint64_t)(std::unique(fresh.begin(), fresh.end()) - fresh.begin());
+    if (activeBricks() + need > brick_alloc_) return VRT_E_OOM;
+    if (material_cursor_.load(std::memory_order_relaxed) + need * brick_bits_ > material_capacity_) return VRT_E_OOM;
+
+    for (const ClippedShape &s : clipped)
+        for_cells(s, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (!shapeRows(s, cx, cy, cz, rows)) return; // (a cell of a sphere's box that holds no voxel of it: no brick)
+            uint32_t brick;
+            if ((brick_statuses[g / 32] >> (g % 32)) & 1u) {
+                brick = brick_indices[g];
+            } else { // Grid.zig:147, 160-168, 188-193
+                brick = active_bricks_.fetch_add(1, std::memory_order_relaxed);
+                brick_start_indices[brick] = material_cursor_.fetch_add(brick_bits_, std::memory_order_relaxed) & 0x7FFFFFFFu;
+                bricks_start_indices_delta.registerDeltaUnlocked(brick);
+                brick_statuses[g / 32] |= 1u << (g % 32);
+                brick_indices[g] = brick;
+            }
+            brick_statuses_delta.registerDeltaUnlocked(g / 32); // (insert registers both for every voxel, loaded cell or not)
+            brick_indices_delta.registerDeltaUnlocked(g);
+            const size_t occupancy_from = (size_t)brick * brick_bytes_, start = brick_start_indices[brick] & 0x7FFFFFFFu;
+            for (uint32_t r = 0; r < b * b; r++) {
+                const uint32_t mask = rows[r];
+                if (!mask) continue;
+                const uint32_t bit = r * b; // the row's first voxel within the brick
+                brick_occupancy[occupancy_from + bit / 8] |= (uint8_t)(mask << (bit % 8));
+                bricks_occupancy_delta.registerDeltaUnlocked(occupancy_from + bit / 8);
+                for (uint32_t k = 0; k < b; k++)
+                    if ((mask >> k) & 1u) material_indices[start + bit + k] = (uint8_t)s.material;
+                material_indices_delta.registerDeltaUnlocked(start + bit + (uint32_t)__builtin_ctz(mask));
+                material_indices_delta.registerDeltaUnlocked(start + bit + 31u - (uint32_t)__builtin_clz(mask));
+            }
+        });
+    return VRT_OK;
+}
+
+int BrickGrid::clearShapes(const vrt_shape *shapes, uint64_t n) {
+    const vrt_grid_state &d = device_state_;
+    const uint32_t b = brick_dimension_;
+    std::vector<ClippedShape> clipped;
+    const int rc = clip_batch(shapes, n, false, d, &clipped);
+    if (rc != VRT_OK) return rc;
+    uint8_t rows[64];
+    std::vector<size_t> touched; // the loaded cells that hold a voxel of the batch
+    for (const ClippedShape &s : clipped)
+        for_cells(s, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (!((brick_statuses[g / 32] >> (g % 32)) & 1u)) return; // not loaded: a no-op
+            if (!shapeRows(s, cx, cy, cz, rows)) return;
+            touched.push_back(g);
+            const size_t occupancy_from = (size_t)brick_indices[g] * brick_bytes_;
+            for (uint32_t r = 0; r < b * b; r++) {
+                const uint32_t bit = r * b;
+                uint8_t &byte = brick_occupancy[occupancy_from + bit / 8];
+                const uint8_t lost = byte & (uint8_t)(rows[r] << (bit % 8));
+                if (!lost) continue; // already empty: a no-op
+                byte &= (uint8_t)~lost;
+                bricks_occupancy_delta.registerDeltaUnlocked(occupancy_from + bit / 8);
+            }
+        });
+    // after the whole batch, as removeImpl does
+    for (const size_t g : touched) {
+        const uint32_t bit = 1u << (g % 32);
+        if (!(brick_statuses[g / 32] & bit)) continue; // (the cell came up twice)
+        const uint8_t *occ = &brick_occupancy[(size_t)brick_indices[g] * brick_bytes_];
+        bool any = false;
+        for (uint32_t k = 0; k < brick_bytes_ && !any; k++) any = occ[k] != 0;
+        if (any) continue;
+        brick_statuses[g / 32] &= ~bit;
+        brick_statuses_delta.registerDeltaUnlocked(g / 32);
+    }
+    return VRT_OK;
 }
 
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {

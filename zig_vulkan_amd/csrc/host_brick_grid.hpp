@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/vrt_hip.h"
+#include "vrt_shapes.h"
 
 namespace vrt {
 
@@ -81,6 +82,13 @@ public:
     // with flag bits or a non-zero _reserved
     void queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) const;
 
+    // Shape edits (the reference has none: include/vrt_hip.h defines them).  The arrays and the deltas that insertUnlocked /
+    // removeManyUnlocked give on the shapes' voxels (shapes in array order, within a shape the cells that hold a voxel of it in
+    // ascending grid index), worked per cell and row.  All or nothing: VRT_E_INVALID_ARG for a batch that is refused; fill counts the
+    // bricks it needs first (VRT_E_OOM; VRT_E_STATE for a loaded cell whose brick has no material entries).  Single-threaded.
+    int fillShapes(const vrt_shape *shapes, uint64_t n);
+    int clearShapes(const vrt_shape *shapes, uint64_t n);
+
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }
     uint32_t brickBits() const { return brick_bits_; }
@@ -108,6 +116,8 @@ private:
     int insertImpl(uint64_t x, uint64_t y, uint64_t z, uint8_t material_index);
     template <bool Locked>
     int removeImpl(const uint32_t *xyz, uint64_t n);
+    // the shape's voxels in cell (cx, cy, cz) (cy flipped): per row (z % B + B * (fy % B)) its B bits along x; false: none
+    bool shapeRows(const ClippedShape &s, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t rows[64]) const;
 
     uint32_t brick_dimension_ = 4, brick_bits_ = 64, brick_bytes_ = 8;
     uint64_t brick_alloc_ = 0;

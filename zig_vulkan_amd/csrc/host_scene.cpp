@@ -272,6 +272,16 @@ int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t
     return VRT_OK;
 }
 
+int vrt_grid_fill_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->fillShapes(shapes, n);
+}
+
+int vrt_grid_clear_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->clearShapes(shapes, n);
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

@@ -44,19 +44,34 @@
 //                         loaded cells naming a brick >= L renamed; the range of those cells
 //   vrt_edit_finish       A = L, cursor = L B^3; the written ranges of bindings 4 and 6 from the first and the last hole
 // (vrt_edit_table is not launched: no cell's scratch word is touched.)
+//
+// Shape edits (vrt_fill_shapes, vrt_clear_shapes) are the fourth and fifth mode, EditArgs::op = kEditOpFill / kEditOpClear.
+// Their work item is not a voxel but one 32-bit occupancy word of one cell of one shape's clipped cell box, ordered shape-major,
+// cell-index-major, word-minor; the host uploads one ShapeRec per shape that holds a voxel of the grid, with the items before it, and a
+// kernel finds its shape by binary search.  The item's mask (the word's voxels inside the shape) stands for the voxel:
+//   vrt_edit_validate     per item: shape, cell, word, mask; a zero mask makes the item inert.  fill: as for inserts, with "first item"
+//                         for "first voxel"; clear: as for removals, the mask kept in the item's slot word
+//   vrt_edit_count / _scan_groups / _rank / _resolve   fill only, unchanged in meaning
+//   vrt_edit_table        clears the cells' scratch words (no last-writer table: see vrt_edit_write)
+//   vrt_edit_write        fill: one atomicOr of the mask; the material bytes of the mask's bits that no later shape of the batch covers,
+//                         whole words of four and whole runs of 32 at once; the first item of a new cell writes the cell's words.
+//                         clear: phase 0 one atomicAnd of ~mask, phase 1 as for removals
+//   vrt_edit_finish
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 #include "vrt_ctx.h"
+#include "vrt_shapes.h"
 
 namespace vrt {
 
 constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
-constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2; // EditArgs::op
+constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4; // EditArgs::op
 constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
@@ -91,6 +106,19 @@ struct EditStatus {
     uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
 };
 
+// One shape of a fill or clear batch as the kernels read it (64 bytes): ClippedShape (y flipped; index 0 = x, 1 = flipped y, 2 = z),
+// and where its items lie.  Only shapes that hold a voxel of the grid's range are uploaded.
+struct ShapeRec {
+    uint32_t lo[3], hi[3];  // the voxels considered
+    uint32_t centre[3];     // sphere: the centre modulo 2^32
+    uint32_t r2;            // sphere: r^2
+    uint32_t kind, material;
+    uint32_t first;         // items of the shapes before this one
+    uint32_t ncx, ncxz;     // cells of its clipped cell box along x, and in one layer of y
+    uint32_t _pad;
+};
+static_assert(sizeof(ShapeRec) == 64, "ShapeRec is four dwordx4");
+
 struct EditArgs {
     // the scene (the context's buffers)
     uint32_t *status;        // binding 2
@@ -101,10 +129,12 @@ struct EditArgs {
     // the batch
     const uint32_t *xyz;     // 3 per voxel, y as vrt_grid_insert takes it
     const uint8_t *materials;
+    const ShapeRec *shapes;  // fill / clear: the batch's shapes (n is then the number of items)
+    uint32_t shape_count;
     uint32_t n;
     uint32_t groups;         // ceil(n / kEditBlock)
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
-    uint32_t op;             // kEditOpInsert / kEditOpRemove (uniform: every kernel of a chain sees the same)
+    uint32_t op;             // kEditOpInsert / kEditOpRemove / kEditOpCompact / kEditOpFill / kEditOpClear (uniform: every kernel of a chain sees the same)
     uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks;
                              // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells
     // scratch (the context's, grown on demand)
@@ -189,6 +219,98 @@ __device__ inline void copy_piece(void *base, uint64_t record_bytes, uint32_t sr
     *reinterpret_cast<T *>(p + dst * record_bytes + piece * sizeof(T)) = *reinterpret_cast<const T *>(p + src * record_bytes + piece * sizeof(T));
 }
 
+// ---- shape edits: item i = one 32-bit occupancy word of one cell of one shape's clipped cell box ----
+struct ShapeItem {
+    uint32_t shape, x, y, z, word; // the cell's first voxel (y flipped)
+};
+
+// shape t of the batch (a 32-bit offset from the uniform base: t < 4096)
+__device__ inline const ShapeRec &shape_rec(const EditArgs &a, uint32_t t) {
+    return *reinterpret_cast<const ShapeRec *>(reinterpret_cast<const uint8_t *>(a.shapes) + (t << 6));
+}
+
+__device__ inline ShapeItem shape_item(const EditArgs &a, uint32_t i) {
+    uint32_t lo = 0, hi = a.shape_count; // the last shape whose first item is at or below i (first of shape 0 is 0; every shape has items)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (shape_rec(a, mid).first <= i) lo = mid;
+        else hi = mid;
+    }
+    const ShapeRec &r = shape_rec(a, lo);
+    const uint32_t word_shift = a.b == 8u ? 4u : 1u; // 16 or 2 words per brick
+    const uint32_t local = i - r.first, c = local >> word_shift, layer = c % r.ncxz;
+    ShapeItem it;
+    it.shape = lo;
+    it.word = local & ((1u << word_shift) - 1u);
+    const uint32_t log_b = a.b == 8u ? 3u : 2u;
+    it.x = ((r.lo[0] >> log_b) + layer % r.ncx) << log_b;
+    it.z = ((r.lo[2] >> log_b) + layer / r.ncx) << log_b;
+    it.y = ((r.lo[1] >> log_b) + c / r.ncxz) << log_b;
+    return it;
+}
+
+// Shape r as the cell whose first voxel is (x, y, z) sees it, in few registers: the clipped row along x, the rows of the cell inside the shape's range, and the
+// cell's origin relative to the sphere's centre.
+struct CellShape {
+    uint32_t box_row;   // bits x % B of the voxels of lo[0]..hi[0] in this cell (0: the shape's range misses the cell)
+    uint32_t rows;      // bit z % B: z inside the range; bit 8 + fy % B: fy inside the range; bit 31: a sphere
+    int32_t ox, oy, oz; // sphere: the cell's first voxel - centre (exact: within r + B of 0 for a cell the range reaches)
+    uint32_t r2;
+};
+
+// bits first..last (both below 32)
+__device__ inline uint32_t bit_run(uint32_t first, uint32_t last) { return ((2u << last) - 1u) & ~((1u << first) - 1u); }
+
+// (written so that nothing but the cell's first voxel is the same for every shape of vrt_edit_write's loop over the later shapes: what
+// is, the compiler keeps in registers across the loop)
+__device__ inline CellShape cell_shape(const ShapeRec &r, uint32_t b, uint32_t x, uint32_t y, uint32_t z) {
+    const uint32_t last = b - 1u;
+    CellShape c;
+    c.box_row = 0u, c.rows = 0u;
+    if ((r.lo[0] & ~last) <= x && r.hi[0] >= x && (r.lo[1] & ~last) <= y && r.hi[1] >= y && (r.lo[2] & ~last) <= z && r.hi[2] >= z) {
+        c.box_row = bit_run(r.lo[0] > x ? r.lo[0] - x : 0u, min(r.hi[0] - x, last));
+        c.rows = bit_run(r.lo[2] > z ? r.lo[2] - z : 0u, min(r.hi[2] - z, last)) | (bit_run(r.lo[1] > y ? r.lo[1] - y : 0u, min(r.hi[1] - y, last)) << 8) |
+                 (r.kind == VRT_SHAPE_SPHERE ? 1u << 31 : 0u);
+    }
+    c.ox = (int32_t)(x - r.centre[0]), c.oy = (int32_t)(y - r.centre[1]), c.oz = (int32_t)(z - r.centre[2]);
+    c.r2 = r.r2;
+    return c;
+}
+
+// the voxels of word `word` of the cell that the shape holds: bit k is voxel nth_bit = 32 word + k = x % B + B (z % B + B (fy % B)), so the
+// word is 32 / B rows along x.  A box is clipped rows.  A sphere's row is the voxels with dx^2 <= r^2 - dy^2 - dz^2 =: rem, in integers
+// (|voxel - centre| <= r <= 16384 for every voxel of lo..hi, so the sums stay below 2^30): |dx| <= s = floor(sqrt(rem)), s formed in
+// float (off by one at the most: rem < 2^29 and a float sqrt are both good to 2^-23) and set right by the two integer tests.
+__device__ inline uint32_t word_mask(const CellShape &c, uint32_t b, uint32_t word) {
+    if (c.box_row == 0u) return 0u;
+    const uint32_t rows = 32u / b, log_b = b == 8u ? 3u : 2u;
+    uint32_t mask = 0;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable) // (rolled: the shape modes stay within the kernels' 32 VGPRs, tests/test_kernel_resources.py)
+    for (uint32_t row = word * rows; row == word * rows || (row & (rows - 1u)); row++) { // the word's rows: word * rows is a multiple of rows
+        const uint32_t z = row & (b - 1u), y = row >> log_b;
+        if (!((c.rows >> z) & (c.rows >> (8u + y)) & 1u)) continue;
+        uint32_t m = c.box_row;
+        if ((int32_t)c.rows < 0) {
+            const int32_t dy = c.oy + (int32_t)y, dz = c.oz + (int32_t)z;
+            const int32_t rem = (int32_t)c.r2 - dy * dy - dz * dz;
+            m = 0;
+            if (rem >= 0) {
+                int32_t s = (int32_t)__fsqrt_rn((float)rem);
+                if (s * s > rem) s--;
+                if ((s + 1) * (s + 1) <= rem) s++;
+                const int32_t first = max(-s - c.ox, 0), last = min(s - c.ox, (int32_t)b - 1); // dx = ox + x in [-s, s]
+                if (first <= last) m = c.box_row & bit_run((uint32_t)first, (uint32_t)last);
+            }
+        }
+        mask |= m << ((row & (rows - 1u)) * b);
+    }
+    return mask;
+}
+
+__device__ inline uint32_t shape_mask(const ShapeRec &r, uint32_t b, const ShapeItem &it) {
+    return word_mask(cell_shape(r, b, it.x, it.y, it.z), b, it.word);
+}
+
 } // namespace
 
 extern "C" {
@@ -264,9 +386,56 @@ __device__ inline void compact_validate(const EditArgs &a) {
     wave_atomic_or(&a.out->err, err);
 }
 
+// a fill's or a clear's items (every lane gets to the reduction)
+__device__ inline void shape_validate(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool ok = a.state->ok != 0, fill = a.op == kEditOpFill;
+    const uint32_t bricks = a.state->bricks;
+    uint32_t cell = kEditNone, info = 0, err = 0;
+    if (i < a.n && ok) {
+        const ShapeItem it = shape_item(a, i);
+        const uint32_t mask = shape_mask(shape_rec(a, it.shape), a.b, it);
+        if (mask) { // (a zero mask: the item is inert, cell stays kEditNone)
+            const uint32_t log_b = a.b == 8u ? 3u : 2u;
+            const uint32_t g = (it.x >> log_b) + a.dim_x * ((it.z >> log_b) + a.dim_z * (it.y >> log_b)); // gridAt (below the grid's cells, which fit 32 bits)
+            const uint32_t first_bit = it.word << 5;                        // voxelAt of the word's bit 0
+            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
+                const uint32_t brick = a.index[g];
+                if (brick >= bricks) {
+                    err = kEditErrCell;
+                } else {
+                    a.vbrick[i] = brick;
+                    if (fill) {
+                        a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + first_bit; // the entry of binding 6 of the word's bit 0
+                    } else {
+                        a.vslot[i] = mask;               // (a clear writes no entry of binding 6: the word holds the mask for phase 0)
+                        atomicMin(&a.cell_first[g], i);  // the cell's elected item
+                    }
+                    cell = g;
+                    info = first_bit;
+                }
+            } else if (fill) { // (a clear of a cell that is not loaded: a no-op)
+                atomicMin(&a.cell_first[g], i); // the minimum ranks the new cells shape-major, then by cell index
+                cell = g;
+                info = 0x80000000u | first_bit;
+            }
+        }
+    }
+    if (i < a.n) {
+        a.vcell[i] = cell;
+        a.vinfo[i] = info;
+    }
+    if (!ok && i == 0) err = kEditErrShape;
+    wave_atomic_or(&a.out->err, err);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
     if (a.op == kEditOpCompact) {
         compact_validate(a);
+        return;
+    }
+    if (a.op == kEditOpFill || a.op == kEditOpClear) {
+        shape_validate(a);
         return;
     }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
@@ -409,11 +578,12 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     if (i >= a.n) return;
     const uint32_t cell = a.vcell[i];
-    if (a.op == kEditOpRemove) { // (removal used the words of the loaded cells it touched, and needs no last writer)
+    if (a.op == kEditOpRemove || a.op == kEditOpClear) { // (removal used the words of the loaded cells it touched, and needs no last writer)
         if (cell != kEditNone) a.cell_first[cell] = kEditNone;
         return;
     }
     if (a.vinfo[i] & 0x80000000u) a.cell_first[cell] = kEditNone; // (whatever the error word says: the scratch is clean for the next batch)
+    if (a.op == kEditOpFill) return; // (no two items write one entry of binding 6: vrt_edit_write tests the later shapes instead)
     if (a.out->err || cell == kEditNone) return;
     const uint32_t key = a.vslot[i] + 1u;
     uint32_t h = table_hash(key, a.table_mask);
@@ -433,7 +603,11 @@ __device__ inline void remove_write(const EditArgs &a) {
     const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
     uint32_t lo = kEditNone, hi = 0;
     if (a.phase == 0) {
-        if (cell != kEditNone) {
+        if (cell != kEditNone && a.op == kEditOpClear) { // the item's word at once: the bytes of it that lost a bit
+            const uint32_t mask = a.vslot[i], word = a.vbrick[i] * (a.brick_bytes >> 2) + (a.vinfo[i] >> 5);
+            const uint32_t lost = atomicAnd(&a.occupancy[word], ~mask) & mask;
+            if (lost) lo = word * 4u + ((uint32_t)__builtin_ctz(lost) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(lost)) >> 3);
+        } else if (cell != kEditNone) {
             const uint32_t nth = a.vinfo[i] & 0x1FFu;
             const uint32_t byte = a.vbrick[i] * a.brick_bytes + (nth >> 3);
             const uint32_t bit = 1u << ((byte & 3u) * 8u + (nth & 7u));
@@ -496,10 +670,74 @@ __device__ inline void compact_write(const EditArgs &a) {
     wave_atomic_max(&a.out->cell_hi, hi);
 }
 
+// a fill's items (every lane of the wave gets to the three pairs of reductions).  The loop over the later shapes comes first, with little
+// else alive, and what follows it reads the item's words again: so the kernel stays within its 32 VGPRs.
+__device__ inline void fill_write(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool active = i < a.n && a.vcell[i] != kEditNone;
+    uint32_t mask = 0, keep = 0, word = 0, material = 0;
+    if (active) {
+        const ShapeItem it = shape_item(a, i);
+        const ShapeRec &r = shape_rec(a, it.shape);
+        // the item's mask (not zero: the item is not inert), and Grid.zig:174, the last write of an entry wins: this item writes the
+        // entries that no later shape of the batch covers (the rows are tested only for the shapes whose range reaches into the cell)
+        mask = keep = shape_mask(r, a.b, it);
+        material = r.material;
+        word = it.word;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (uint32_t t = it.shape + 1u; t < a.shape_count && keep; t++) keep &= ~shape_mask(shape_rec(a, t), a.b, it);
+    }
+    uint32_t lo = kEditNone, hi = 0;
+    if (active && (a.vinfo[i] & 0x40000000u)) { // the first item of a cell that was not loaded: Grid.zig:160-168, 188-193
+        const uint32_t cell = a.vcell[i], brick = a.vbrick[i];
+        atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
+        a.index[cell] = brick;
+        a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
+        lo = hi = cell;
+    }
+    wave_atomic_min(&a.out->cell_lo, lo);
+    wave_atomic_max(&a.out->cell_hi, hi);
+    lo = kEditNone, hi = 0;
+    if (active) { // Grid.zig:180-185 for the word's voxels at once
+        word += a.vbrick[i] * (a.brick_bytes >> 2);
+        atomicOr(&a.occupancy[word], mask);
+        lo = word * 4u + ((uint32_t)__builtin_ctz(mask) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(mask)) >> 3);
+    }
+    wave_atomic_min(&a.out->occ_lo, lo);
+    wave_atomic_max(&a.out->occ_hi, hi);
+    lo = kEditNone, hi = 0;
+    if (keep) {
+        const uint32_t slot = a.vslot[i], four = material * 0x01010101u;
+        uint8_t *entries = a.material + slot; // (slot + 31 lies within the brick's B^3 entries)
+        if (keep == 0xFFFFFFFFu && !(slot & 15u)) { // a whole run of 32 entries
+            reinterpret_cast<uint4 *>(entries)[0] = make_uint4(four, four, four, four);
+            reinterpret_cast<uint4 *>(entries)[1] = make_uint4(four, four, four, four);
+        } else {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (uint32_t k = 0; k < 32u; k += 4u) {
+                const uint32_t nibble = (keep >> k) & 15u;
+                if (nibble == 15u && !(slot & 3u)) { // four entries at once
+                    *reinterpret_cast<uint32_t *>(entries + k) = four;
+                } else {
+                    for (uint32_t j = 0; j < 4u; j++)
+                        if ((nibble >> j) & 1u) entries[k + j] = (uint8_t)material;
+                }
+            }
+        }
+        lo = slot + (uint32_t)__builtin_ctz(keep), hi = slot + 31u - (uint32_t)__builtin_clz(keep);
+    }
+    wave_atomic_min(&a.out->mat_lo, lo);
+    wave_atomic_max(&a.out->mat_hi, hi);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     if (a.out->err) return;
-    if (a.op == kEditOpRemove) {
+    if (a.op == kEditOpRemove || a.op == kEditOpClear) {
         remove_write(a);
+        return;
+    }
+    if (a.op == kEditOpFill) {
+        fill_write(a);
         return;
     }
     if (a.op == kEditOpCompact) {
@@ -835,6 +1073,104 @@ int compact(vrt_ctx *ctx, uint32_t out[2]) {
     return VRT_OK;
 }
 
+// n shapes (host memory) filled into or cleared from the scene: the batch screened and clipped on the host, one record per shape that
+// holds a voxel of the grid's range staged into device memory, then the fill's or the clear's part of the chain as one scene write
+int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
+    std::string why;
+    int rc = vrt::screen_shapes(shapes, n, fill, &why);
+    if (rc != VRT_OK) return fail(ctx, rc, why + (fill ? "; nothing was filled" : "; nothing was cleared"));
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, "shape edits are not available on a context of the multi-GPU pipeline");
+    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    const uint32_t b = ctx->cfg.brick_dimension, words = b * b * b / 32u;
+    const uint32_t dim[3] = {ctx->cfg.dim_x * b, ctx->cfg.dim_y * b, ctx->cfg.dim_z * b};
+    std::vector<vrt::ShapeRec> recs;
+    uint64_t items = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        vrt::ClippedShape c;
+        if (!vrt::clip_shape(shapes[i], dim, &c)) continue;
+        vrt::ShapeRec r{};
+        uint64_t cells[3];
+        for (int k = 0; k < 3; k++) {
+            r.lo[k] = c.lo[k], r.hi[k] = c.hi[k], r.centre[k] = c.centre[k];
+            cells[k] = (uint64_t)(c.hi[k] / b) - c.lo[k] / b + 1u;
+        }
+        r.r2 = c.r2, r.kind = c.kind, r.material = c.material;
+        r.first = (uint32_t)items;
+        r.ncx = (uint32_t)cells[0];
+        r.ncxz = (uint32_t)(cells[0] * cells[2]); // (below the grid's cells, which fit 32 bits)
+        items += cells[0] * cells[1] * cells[2] * words; // (< 2^32 * 16 each, and the sum is tested before it can wrap: items < 2^31 so far)
+        if (items >= (1ull << 31))
+            return fail(ctx, VRT_E_OUT_OF_RANGE, "shape " + std::to_string(i) + ": the batch's work items (one per occupancy word of every cell of every shape's clipped cell box) reach 2^31");
+        recs.push_back(r);
+    }
+    if (recs.empty()) return VRT_OK; // every shape empty after clipping: the device is not touched
+    DeviceGuard dg(ctx->device);
+    rc = edit_prepare(ctx, "shape edits are");
+    if (rc != VRT_OK) return rc;
+    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
+    const uint64_t bytes = recs.size() * sizeof(vrt::ShapeRec);
+    if (ctx->edit_input_bytes < bytes) {
+        ctx->res.drop(ctx->d_edit_input);
+        ctx->edit_input_bytes = 0;
+        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_input, bytes));
+        ctx->edit_input_bytes = bytes;
+    }
+    rc = staged_copy_h2d(ctx, ctx->d_edit_input, recs.data(), bytes);
+    if (rc == VRT_OK) rc = edit_scratch(ctx, items, false);
+    if (rc != VRT_OK) return rc;
+    rc = begin_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, nullptr, nullptr, (uint32_t)items, !ctx->edit_state_valid);
+    a.op = fill ? vrt::kEditOpFill : vrt::kEditOpClear;
+    a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
+    a.shape_count = (uint32_t)recs.size();
+    const uint32_t groups = a.groups;
+    rc = launch_state(ctx, a);
+    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
+    if (fill) {
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+    } else {
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+        a.phase = 1;
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
+    }
+    if (rc != VRT_OK) {
+        (void)wait_stream(ctx->stream);
+        ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
+        ctx->edit_state_valid = false;
+        return rc;
+    }
+    rc = end_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    vrt::EditStatus s;
+    rc = read_status(ctx, a, &s);
+    if (rc != VRT_OK) return rc;
+    const char *nothing = fill ? "; nothing was filled" : "; nothing was cleared";
+    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
+    if (s.err & vrt::kEditErrCell)
+        return fail(ctx, VRT_E_STATE, std::string("a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5)") + nothing);
+    if (s.err & vrt::kEditErrOom)
+        return fail(ctx, VRT_E_OOM, "the batch needs " + std::to_string(s.new_bricks) + " new bricks: brick_alloc or the material entries are exhausted" + nothing);
+    // the derived structures follow exactly what was written, as for inserts and removals
+    if (s.cell_lo <= s.cell_hi) {
+        mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
+        if (fill) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
+    }
+    if (s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
+    if (fill && s.new_bricks) {
+        mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)(s.bricks - s.new_bricks) * 4u, (uint64_t)s.new_bricks * 4u);
+        ctx->edit_state_valid = true; // (the device state already counts these bricks: this write is the fill's own)
+    }
+    if (fill && s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    return VRT_OK;
+}
+
 int check_batch(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
     if (!xyz || !materials) return fail(ctx, VRT_E_INVALID_ARG, "xyz or materials is NULL");
     if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
@@ -908,6 +1244,18 @@ int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
     rc = staged_copy_h2d(ctx, ctx->d_edit_input, xyz, bytes);
     if (rc != VRT_OK) return rc;
     return remove(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), n);
+}
+
+int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    return edit_shapes(ctx, shapes, n, true);
+}
+
+int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    return edit_shapes(ctx, shapes, n, false);
 }
 
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {

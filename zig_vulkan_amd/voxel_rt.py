@@ -89,6 +89,17 @@ class BrickGrid:
         check(lib.vrt_grid_compact(self._h, C.byref(out)))
         return int(out[0]), int(out[1])
 
+    def fill_shapes(self, shapes) -> None:
+        """vrt_grid_fill_shapes: the shapes (box(...) / sphere(...) records, or a SHAPE_DTYPE array) filled with their materials, as
+        insert_many of their voxels, shapes in array order; all or nothing."""
+        s = shape_records(shapes)
+        check(lib.vrt_grid_fill_shapes(self._h, s.ctypes.data, s.shape[0]))
+
+    def clear_shapes(self, shapes) -> None:
+        """vrt_grid_clear_shapes: the shapes' voxels removed, as remove_many of them; material must be 0.  Emptied bricks are not reused."""
+        s = shape_records(shapes)
+        check(lib.vrt_grid_clear_shapes(self._h, s.ctypes.data, s.shape[0]))
+
     def get_voxels(self, xyz) -> np.ndarray:
         """vrt_grid_get_voxels: the material entry (0..255) of each voxel of xyz (n, 3), as insert_many takes it, or VOXEL_EMPTY where the
         voxel is not solid or lies outside the grid; (n,) uint16."""
@@ -280,6 +291,35 @@ def box_queries(lo, hi) -> np.ndarray:
     return q
 
 
+# vrt_shape (include/vrt_hip.h) as a numpy record
+SHAPE_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("kind", np.uint32), ("material", np.uint32)])
+assert SHAPE_DTYPE.itemsize == 32
+
+
+def box(lo, hi, material: int = 0) -> np.ndarray:
+    """One vrt_shape record: the box of inclusive corners lo, hi in voxels (signed; clipped to the grid by the edit)."""
+    s = np.zeros(1, dtype=SHAPE_DTYPE)
+    s["lo"], s["hi"], s["kind"], s["material"] = np.asarray(lo, dtype=np.int32), np.asarray(hi, dtype=np.int32), L.SHAPE_BOX, material
+    return s
+
+
+def sphere(centre, r: int, material: int = 0) -> np.ndarray:
+    """One vrt_shape record: the voxels within r of centre (dx^2 + dy^2 + dz^2 <= r^2 in integers)."""
+    s = np.zeros(1, dtype=SHAPE_DTYPE)
+    s["lo"], s["kind"], s["material"] = np.asarray(centre, dtype=np.int32), L.SHAPE_SPHERE, material
+    s["hi"][0, 0] = r
+    return s
+
+
+def shape_records(shapes) -> np.ndarray:
+    """A contiguous SHAPE_DTYPE array of one record, an array of them, or a sequence of either (box(...), sphere(...))."""
+    if isinstance(shapes, np.ndarray):
+        assert shapes.dtype == SHAPE_DTYPE
+        return np.ascontiguousarray(shapes).reshape(-1)
+    shapes = list(shapes)
+    return np.ascontiguousarray(np.concatenate([shape_records(s) for s in shapes])) if shapes else np.zeros(0, dtype=SHAPE_DTYPE)
+
+
 def ray_queries(origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
     """Host records of vrt_ray_query: origins (n, 3) or one (3,) for all, directions (n, 3), max_t None (no limit), a number or (n,)."""
     d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
@@ -444,6 +484,17 @@ class VoxelRT:
             return
         x = np.ascontiguousarray(xyz, dtype=np.uint32).reshape(-1, 3)
         self._check(self._lib.vrt_remove_voxels(self._h, x.ctypes.data, x.shape[0]))
+
+    def fill_shapes(self, shapes) -> None:
+        """BrickGrid.fill_shapes on the scene the context holds (vrt_fill_shapes): boxes and spheres (box(...) / sphere(...) records)
+        filled with their materials, 32 bytes per shape whatever its size; all or nothing."""
+        s = shape_records(shapes)
+        self._check(self._lib.vrt_fill_shapes(self._h, s.ctypes.data, s.shape[0]))
+
+    def clear_shapes(self, shapes) -> None:
+        """BrickGrid.clear_shapes on the scene the context holds (vrt_clear_shapes): the shapes' voxels removed; material must be 0."""
+        s = shape_records(shapes)
+        self._check(self._lib.vrt_clear_shapes(self._h, s.ctypes.data, s.shape[0]))
 
     def compact_bricks(self) -> Tuple[int, int]:
         """BrickGrid.compact on the scene the context holds (vrt_compact_bricks): bindings 2-6 afterwards equal the host grid's arrays
