@@ -416,6 +416,45 @@ def test_device_path_equals_host_path_and_batches_beyond_one_launch():
     rt.deinit()
 
 
+@pytest.mark.parametrize("b", [4, 8])
+def test_host_path_beyond_one_staged_piece(b):
+    """More rays than one round trip through the context's device buffers takes (1 << 20): the host path answers them as two host calls
+    split there do, and as the device path does.  The last five rays run from outside the box at the centres of solid voxels: they
+    hit, so a tail that was never written cannot pass."""
+    import torch
+    grid = make_scene("terrain", b)
+    rt = renderer(grid)
+    rng = np.random.default_rng(40 + b)
+    piece = 1 << 20
+    n = piece + 5
+    o, d = make_rays(rng, grid, n)
+    lo, hi, _ = grid_box(grid)
+    solid, _ = solid_voxels(grid)
+    cells = np.argwhere(solid)
+    pick = cells[rng.integers(0, len(cells), 5)]
+    o[-5:] = (lo - 0.25 * (hi - lo)).astype(np.float32)
+    d[-5:] = (lo + (pick + 0.5) * (hi - lo) / np.array(solid.shape) - o[-5:]).astype(np.float32)
+    whole = rt.cast_rays(o, d)
+    split = np.concatenate([rt.cast_rays(o[:piece], d[:piece]), rt.cast_rays(o[piece:], d[piece:])])
+    assert whole.tobytes() == split.tobytes()
+    assert whole.tobytes() == rt.cast_rays(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()).tobytes()
+    assert whole["hit"][-5:].all() and whole["hit"][:piece].any() and not whole["hit"].all()
+    rt.deinit()
+
+
+def test_host_path_grows_its_buffers_on_one_context():
+    """A small batch, a larger one (the two device buffers are made anew), a small one again: each as the device path answers it."""
+    import torch
+    grid = make_scene("sparse", 8)
+    rt = renderer(grid)
+    o, d = make_rays(np.random.default_rng(9), grid, 300_000)
+    for part in (slice(0, 1000), slice(0, 300_000), slice(299_000, 300_000)):
+        host = rt.cast_rays(o[part], d[part])
+        assert host.tobytes() == rt.cast_rays(torch.from_numpy(o[part]).cuda(), torch.from_numpy(d[part]).cuda()).tobytes()
+        assert host["hit"].any()
+    rt.deinit()
+
+
 def test_errors_and_edge_cases():
     grid = make_scene("terrain", 4)
     rt = renderer(grid)

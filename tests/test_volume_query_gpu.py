@@ -284,3 +284,97 @@ def test_a_64_cubed_cell_grid_of_8_cubed_bricks():
     assert np.array_equal(get_both(rt, xyz), g.get_voxels(xyz))
     rt.deinit()
     g.deinit()
+
+
+def solid_tail(g, rng, n=5):
+    """n solid voxels of the grid."""
+    c, nth = solid_of(g, loaded_cells(g))
+    pick = rng.integers(0, c.size, n)
+    return voxels_of(g, c[pick], nth[pick])
+
+
+def random_voxels(g, rng, n):
+    """n voxels of the grid, the last five of them solid: their answers are not zero, so a tail that was never written cannot pass."""
+    shape = [d * g.brick_dimension for d in g.dim]
+    xyz = np.stack([rng.integers(0, s, n) for s in shape], axis=1).astype(np.uint32)
+    xyz[-5:] = solid_tail(g, rng)
+    return xyz
+
+
+def small_boxes(g, rng, n):
+    """n boxes of one to three voxels a side, some partly outside the grid; the last five are single solid voxels (count 1)."""
+    shape = [d * g.brick_dimension for d in g.dim]
+    lo = np.stack([rng.integers(-2, s + 1, n) for s in shape], axis=1).astype(np.int32)
+    hi = lo + rng.integers(0, 3, (n, 3)).astype(np.int32)
+    lo[-5:] = hi[-5:] = solid_tail(g, rng).astype(np.int32)
+    return lo, hi
+
+
+@pytest.mark.parametrize("b", [4, 8])
+def test_host_paths_beyond_one_staged_piece(b):
+    """More voxels and more boxes than one round trip through the context's device buffers takes (1 << 20): the host paths answer
+    them as two host calls split there do, and as the device paths do."""
+    rng = np.random.default_rng(20 + b)
+    g = make_grid("terrain", (13, 7, 9), b)
+    rt = context(g)
+    piece = 1 << 20
+    n = piece + 5
+    xyz = random_voxels(g, rng, n)
+    whole = rt.get_voxels(xyz)
+    assert whole.tobytes() == np.concatenate([rt.get_voxels(xyz[:piece]), rt.get_voxels(xyz[piece:])]).tobytes()
+    assert whole.tobytes() == rt.get_voxels(cuda(xyz)).tobytes()
+    assert np.all(whole[-5:] != VOXEL_EMPTY) and np.any(whole[:piece] != VOXEL_EMPTY) and np.any(whole == VOXEL_EMPTY)
+    lo, hi = small_boxes(g, rng, n)
+    whole = rt.query_boxes(lo, hi)
+    assert whole.tobytes() == np.concatenate([rt.query_boxes(lo[:piece], hi[:piece]), rt.query_boxes(lo[piece:], hi[piece:])]).tobytes()
+    assert whole.tobytes() == rt.query_boxes(cuda(lo), cuda(hi)).tobytes()
+    assert np.all(whole["count"][-5:] == 1) and np.any(whole["count"][:piece] > 1) and np.any(whole["count"] == 0)
+    rt.deinit()
+    g.deinit()
+
+
+def test_host_paths_grow_their_buffers_on_one_context():
+    """A small batch, a larger one (the two device buffers are made anew), a small one again, of voxels and then of boxes: each equals
+    the CPU twin."""
+    rng = np.random.default_rng(31)
+    g = make_grid("terrain", (13, 7, 9), 8)
+    rt = context(g)
+    xyz = random_voxels(g, rng, 300_000)
+    lo, hi = small_boxes(g, rng, 300_000)
+    want_v, want_b = g.get_voxels(xyz), g.query_boxes(lo, hi)
+    assert np.any(want_v[:1000] != VOXEL_EMPTY) and np.any(want_b["count"][:1000] > 0)
+    for part in (slice(0, 1000), slice(0, 300_000), slice(299_000, 300_000)):
+        assert np.array_equal(rt.get_voxels(xyz[part]), want_v[part]), part
+    for part in (slice(0, 1000), slice(0, 300_000), slice(299_000, 300_000)):
+        assert np.array_equal(rt.query_boxes(lo[part], hi[part]), want_b[part]), part
+    rt.deinit()
+    g.deinit()
+
+
+def test_device_paths_batch_beyond_one_launch():
+    """More voxels than one launch takes (1 << 24) and more boxes (1 << 22): the launches after the first answer their elements as a
+    batch of their own would."""
+    import torch
+    g = make_grid("terrain", (13, 7, 9), 8)
+    rt = context(g)
+    shape = torch.tensor([d * 8 for d in g.dim], device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    first = 1 << 24
+    n = first + 5000
+    xyz = (torch.rand((n, 3), generator=gen, device="cuda") * shape).to(torch.int32)
+    big = rt.get_voxels(xyz)
+    host = xyz.cpu().numpy().astype(np.uint32)
+    for a, z in ((0, 4000), (first - 3000, n)):
+        assert big[a:z].tobytes() == rt.get_voxels(host[a:z]).tobytes()
+    assert np.any(big[first:] != VOXEL_EMPTY)
+    del xyz
+    first = 1 << 22
+    n = first + 5000
+    at = (torch.rand((n, 3), generator=gen, device="cuda") * shape).to(torch.int32)   # one-voxel boxes
+    big = rt.query_boxes(at, at)
+    host = at.cpu().numpy()
+    for a, z in ((0, 4000), (first - 3000, n)):
+        assert big[a:z].tobytes() == rt.query_boxes(host[a:z], host[a:z]).tobytes()
+    assert np.any(big["count"][first:] == 1)
+    rt.deinit()
+    g.deinit()

@@ -326,6 +326,24 @@ inline hipError_t wait_event(hipEvent_t ev) {
     return e == hipErrorNotReady ? hipEventSynchronize(ev) : e;
 }
 
+// Grow-only device buffers: the buffers named (`p, bytes` pairs, one or two that share a capacity) hold `cap` of the caller's units;
+// where `want` is more they are made anew at the byte sizes given, their contents lost.  wait_first: work queued on the primary stream
+// may still use them.  The capacity is zero while they are being made, so that a failed allocation leaves the context consistent.
+inline hipError_t renew_device(vrt::Resources &) { return hipSuccess; }
+template <class T, class... More> hipError_t renew_device(vrt::Resources &res, T *&p, uint64_t bytes, More &&...more) {
+    res.drop(p);
+    const hipError_t e = res.device(&p, bytes);
+    return e != hipSuccess ? e : renew_device(res, more...);
+}
+template <class... Bufs> int grow_device(vrt_ctx *ctx, uint64_t &cap, uint64_t want, bool wait_first, Bufs &&...bufs) {
+    if (cap >= want) return VRT_OK;
+    if (wait_first) VRT_HIP(ctx, wait_stream(ctx->stream));
+    cap = 0;
+    VRT_HIP(ctx, renew_device(ctx->res, bufs...));
+    cap = want;
+    return VRT_OK;
+}
+
 // ---- vrt_api.hip ----
 void free_ctx(vrt_ctx *c);
 // Scene writes happen on the primary stream.  With several streams of frames they must not overtake a frame that is still reading

@@ -829,38 +829,42 @@ int edit_prepare(vrt_ctx *ctx, const char *what = "voxel inserts are") {
     return VRT_OK;
 }
 
+int not_shaped(vrt_ctx *ctx) {
+    return fail(ctx, VRT_E_STATE, "binding 5 (brick_start_indices) is not allocation-shaped: entries [0, A) set with type bit 0, the rest "
+                                  "0xFFFFFFFF, and the largest start + B^3 within binding 6 (vrt_upload_grid makes it so)");
+}
+
 // scratch for a batch of n voxels: the per-cell words (once, all 0xFFFFFFFF; every batch leaves them so), the per-voxel words, the
 // per-workgroup counts and the last-writer table (a power of two of at least 2n entries; inserts only).  No kernel of an earlier batch
-// is in flight: every batch ends with a wait for its status.
-int edit_scratch(vrt_ctx *ctx, uint64_t n, bool with_table = true) {
+// is in flight: every batch ends with a wait for its status.  Nothing to launch where the state is known not to be allocation-shaped.
+int edit_scratch(vrt_ctx *ctx, uint64_t n, bool with_table = false) {
+    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
     if (!ctx->d_edit_cell_first) {
         const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_cell_first, cells * sizeof(uint32_t)));
         VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_cell_first, 0xFF, cells * sizeof(uint32_t), ctx->stream));
     }
-    if (ctx->edit_capacity < n) {
-        const uint64_t cap = (n + vrt::kEditBlock - 1u) / vrt::kEditBlock * vrt::kEditBlock;
-        ctx->res.drop(ctx->d_edit_voxels);
-        ctx->res.drop(ctx->d_edit_groups);
-        ctx->edit_capacity = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_voxels, 4u * cap * sizeof(uint32_t)));
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_groups, cap / vrt::kEditBlock * sizeof(uint32_t)));
-        ctx->edit_capacity = cap;
-    }
-    if (!with_table) return VRT_OK;
+    const uint64_t cap = (n + vrt::kEditBlock - 1u) / vrt::kEditBlock * vrt::kEditBlock;
+    int rc = grow_device(ctx, ctx->edit_capacity, cap, false, ctx->d_edit_voxels, 4u * cap * sizeof(uint32_t), ctx->d_edit_groups,
+                         cap / vrt::kEditBlock * sizeof(uint32_t));
+    if (rc != VRT_OK || !with_table) return rc;
     uint64_t entries = 1024;
     while (entries < 2u * n) entries <<= 1;
-    if (ctx->edit_table_entries < entries) {
-        ctx->res.drop(ctx->d_edit_table);
-        ctx->edit_table_entries = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_table, entries * sizeof(uint2)));
-        ctx->edit_table_entries = entries;
-    }
-    return VRT_OK;
+    return grow_device(ctx, ctx->edit_table_entries, entries, false, ctx->d_edit_table, entries * sizeof(uint2));
 }
 
-vrt::EditArgs edit_args(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint32_t n, bool rescan) {
+// a batch given in host memory, into d_edit_input through the pinned staging slots: `first`, then `second` behind it
+int stage_input(vrt_ctx *ctx, const void *first, uint64_t first_bytes, const void *second = nullptr, uint64_t second_bytes = 0) {
+    const uint64_t bytes = first_bytes + second_bytes;
+    int rc = grow_device(ctx, ctx->edit_input_bytes, bytes, false, ctx->d_edit_input, bytes);
+    if (rc == VRT_OK) rc = staged_copy_h2d(ctx, ctx->d_edit_input, first, first_bytes);
+    if (rc == VRT_OK && second_bytes) rc = staged_copy_h2d(ctx, ctx->d_edit_input + first_bytes, second, second_bytes);
+    return rc;
+}
+
+vrt::EditArgs edit_args(vrt_ctx *ctx, uint32_t op, const uint32_t *xyz, const uint8_t *materials, uint32_t n) {
     vrt::EditArgs a{};
+    a.op = op;
     a.status = static_cast<uint32_t *>(ctx->dbuf[VRT_BUF_BRICK_STATUS]);
     a.index = static_cast<uint32_t *>(ctx->dbuf[VRT_BUF_BRICK_INDEX]);
     a.occupancy = static_cast<uint32_t *>(ctx->dbuf[VRT_BUF_BRICK_OCCUPANCY]);
@@ -870,7 +874,7 @@ vrt::EditArgs edit_args(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materi
     a.materials = materials;
     a.n = n;
     a.groups = (n + vrt::kEditBlock - 1u) / vrt::kEditBlock;
-    a.rescan = rescan ? 1u : 0u;
+    a.rescan = ctx->edit_state_valid ? 0u : 1u; // (binding 5 was written since the state was computed)
     a.cell_first = ctx->d_edit_cell_first;
     const uint64_t cap = ctx->edit_capacity;
     a.vcell = ctx->d_edit_voxels;
@@ -929,156 +933,153 @@ int read_status(vrt_ctx *ctx, vrt::EditArgs &a, vrt::EditStatus *out) {
     return VRT_OK;
 }
 
-int not_shaped(vrt_ctx *ctx) {
-    return fail(ctx, VRT_E_STATE, "binding 5 (brick_start_indices) is not allocation-shaped: entries [0, A) set with type bit 0, the rest "
-                                  "0xFFFFFFFF, and the largest start + B^3 within binding 6 (vrt_upload_grid makes it so)");
+// One kernel of an op's chain, between launch_state and read_status.  phase1: EditArgs::phase becomes 1 before this step.
+struct EditStep {
+    void (*fn)(vrt::EditArgs);
+    uint32_t groups;
+    uint32_t threads = vrt::kEditBlock;
+    bool phase1 = false;
+};
+using EditSteps = std::vector<EditStep>;
+
+// The chains of the five ops (the header comment of this file says what each kernel does in each).  Inserts and fills over the g
+// workgroups of the batch's voxels or items:
+EditSteps insert_steps(uint32_t g) {
+    return {{vrt_edit_validate, g}, {vrt_edit_count, g}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, g},
+            {vrt_edit_resolve, g}, {vrt_edit_table, g}, {vrt_edit_write, g}};
+}
+// ... removals and clears:
+EditSteps remove_steps(uint32_t g) {
+    return {{vrt_edit_validate, g}, {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
+}
+// ... compaction: over the cells (and bricks), over the bricks (also what vrt_edit_scan_groups scans), and its grid-stride passes
+EditSteps compact_steps(uint32_t cells, uint32_t bricks, uint32_t copy) {
+    return {{vrt_edit_validate, cells}, {vrt_edit_count, bricks}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, bricks},
+            {vrt_edit_resolve, bricks}, {vrt_edit_write, copy}, {vrt_edit_write, copy, vrt::kEditBlock, true}};
 }
 
-// n voxels at xyz / materials (device memory) into the scene: the whole chain on the primary stream as one scene write
-int insert(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx); // (nothing to launch: the state has not changed)
-    int rc = edit_scratch(ctx, n);
+// An edit as one scene write: the whole chain on the primary stream, and its status read back into *s.  drop_cell_first: a chain
+// cut short may leave the cells' scratch words set (compaction's touches none), so they are made anew, clean, by the next batch.
+int run_edit(vrt_ctx *ctx, vrt::EditArgs &a, const EditSteps &steps, bool drop_cell_first, vrt::EditStatus *s) {
+    int rc = begin_scene_write(ctx);
     if (rc != VRT_OK) return rc;
-    rc = begin_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, xyz, materials, (uint32_t)n, !ctx->edit_state_valid);
-    a.op = vrt::kEditOpInsert;
-    const uint32_t groups = a.groups;
-    VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
     rc = launch_state(ctx, a);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
+    for (const EditStep &st : steps) {
+        if (st.phase1) a.phase = 1;
+        if (rc == VRT_OK) rc = launch(ctx, st.fn, a, st.groups, st.threads);
+    }
     if (rc != VRT_OK) {
         (void)wait_stream(ctx->stream);
-        ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
+        if (drop_cell_first) ctx->res.drop(ctx->d_edit_cell_first);
         ctx->edit_state_valid = false;
         return rc;
     }
     rc = end_scene_write(ctx);
     if (rc != VRT_OK) return rc;
-    vrt::EditStatus s;
-    rc = read_status(ctx, a, &s);
-    if (rc != VRT_OK) return rc;
-    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
-    if (s.err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, "a voxel lies outside the grid; nothing was inserted");
-    if (s.err & vrt::kEditErrCell)
-        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5); nothing was inserted");
-    if (s.err & vrt::kEditErrOom)
-        return fail(ctx, VRT_E_OOM, "the batch needs " + std::to_string(s.new_bricks) + " new bricks: brick_alloc or the material entries are exhausted; nothing was inserted");
-    // the derived structures follow exactly what was written (refresh_derived, before the next frame or query)
-    const uint64_t bpw = 4u;
-    if (s.cell_lo <= s.cell_hi) {
-        mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * bpw, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * bpw);
-        mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * bpw, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * bpw);
-    }
-    if (s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
-    if (s.new_bricks) {
-        mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)(s.bricks - s.new_bricks) * bpw, (uint64_t)s.new_bricks * bpw);
-        ctx->edit_state_valid = true; // (the device state already counts these bricks: this write is the inserts' own)
-    }
-    if (s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    return read_status(ctx, a, s);
+}
+
+// EditStatus::err -> the return code and the message.  `applies`: the errors the op reports (the others are not looked at), in this
+// order of precedence; `nothing`: the op's "; nothing was ..." tail
+int edit_error(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t applies, const char *nothing) {
+    const uint32_t err = s.err & applies;
+    if (err & vrt::kEditErrShape) return not_shaped(ctx);
+    if (err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, std::string("a voxel lies outside the grid") + nothing);
+    if (err & vrt::kEditErrSlot)
+        return fail(ctx, VRT_E_STATE, std::string("an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3") + nothing);
+    if (err & vrt::kEditErrCell)
+        return fail(ctx, VRT_E_STATE, std::string("a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5)") + nothing);
+    if (err & vrt::kEditErrOom)
+        return fail(ctx, VRT_E_OOM, "the batch needs " + std::to_string(s.new_bricks) + " new bricks: brick_alloc or the material entries are exhausted" + nothing);
     return VRT_OK;
 }
+constexpr uint32_t kErrsOfInsert = vrt::kEditErrShape | vrt::kEditErrRange | vrt::kEditErrCell | vrt::kEditErrOom;
+constexpr uint32_t kErrsOfRemove = vrt::kEditErrShape | vrt::kEditErrRange | vrt::kEditErrCell;
+constexpr uint32_t kErrsOfCompact = vrt::kEditErrShape | vrt::kEditErrSlot | vrt::kEditErrCell;
+constexpr uint32_t kErrsOfFill = vrt::kEditErrShape | vrt::kEditErrCell | vrt::kEditErrOom;
+constexpr uint32_t kErrsOfClear = vrt::kEditErrShape | vrt::kEditErrCell;
 
-// n voxels at xyz (device memory) out of the scene: removal's subset of the chain, as one scene write
-int remove(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
-    int rc = edit_scratch(ctx, n, false);
-    if (rc != VRT_OK) return rc;
-    rc = begin_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, xyz, nullptr, (uint32_t)n, !ctx->edit_state_valid);
-    a.op = vrt::kEditOpRemove;
-    const uint32_t groups = a.groups;
-    rc = launch_state(ctx, a);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
-    a.phase = 1;
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
-    if (rc != VRT_OK) {
-        (void)wait_stream(ctx->stream);
-        ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
-        ctx->edit_state_valid = false;
-        return rc;
+// The derived structures follow exactly what was written (refresh_derived, before the next frame or query): the status ranges of the
+// buffers the op writes (`writes`: a bit per vrt_buffer_id), marked dirty.  start_first: the first of the s.new_bricks entries of
+// binding 5 that the op wrote; the device state already accounts for them, so that write, the op's own, leaves the state valid.
+constexpr uint32_t buf_bit(vrt_buffer_id id) { return 1u << id; }
+constexpr uint32_t kWritesOfRemove = buf_bit(VRT_BUF_BRICK_STATUS) | buf_bit(VRT_BUF_BRICK_OCCUPANCY); // (a batch of no-ops: nothing)
+constexpr uint32_t kWritesOfInsert = kWritesOfRemove | buf_bit(VRT_BUF_BRICK_INDEX) | buf_bit(VRT_BUF_BRICK_START_INDEX) | buf_bit(VRT_BUF_MATERIAL_INDEX);
+constexpr uint32_t kWritesOfCompact = kWritesOfInsert & ~buf_bit(VRT_BUF_BRICK_STATUS);
+void mark_written(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t writes, uint32_t start_first) {
+    if (s.cell_lo <= s.cell_hi) {
+        if (writes & buf_bit(VRT_BUF_BRICK_STATUS))
+            mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
+        if (writes & buf_bit(VRT_BUF_BRICK_INDEX)) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
     }
-    rc = end_scene_write(ctx);
+    if ((writes & buf_bit(VRT_BUF_BRICK_OCCUPANCY)) && s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
+    if ((writes & buf_bit(VRT_BUF_BRICK_START_INDEX)) && s.new_bricks) {
+        mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)start_first * 4u, (uint64_t)s.new_bricks * 4u);
+        ctx->edit_state_valid = true;
+    }
+    if ((writes & buf_bit(VRT_BUF_MATERIAL_INDEX)) && s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+}
+
+// What vrt_insert_voxels / vrt_remove_voxels and their _device forms (host: xyz and materials are host memory, staged into device
+// memory first) check and do; insert false: a removal, which has no materials.  The batch's subset of the chain runs as one scene write.
+int edit_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n, bool insert, bool host) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (insert && (!xyz || !materials)) return fail(ctx, VRT_E_INVALID_ARG, "xyz or materials is NULL");
+    if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
+    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
+    DeviceGuard dg(ctx->device);
+    int rc = edit_prepare(ctx, insert ? "voxel inserts are" : "voxel removals are");
     if (rc != VRT_OK) return rc;
+    if (host) { // xyz, then the material bytes behind it
+        const uint64_t xyz_bytes = 12u * n;
+        rc = stage_input(ctx, xyz, xyz_bytes, materials, insert ? n : 0u);
+        if (rc != VRT_OK) return rc;
+        xyz = reinterpret_cast<const uint32_t *>(ctx->d_edit_input);
+        materials = insert ? ctx->d_edit_input + xyz_bytes : nullptr;
+    }
+    rc = edit_scratch(ctx, n, insert);
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, insert ? vrt::kEditOpInsert : vrt::kEditOpRemove, xyz, materials, (uint32_t)n);
+    if (insert) VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
     vrt::EditStatus s;
-    rc = read_status(ctx, a, &s);
+    rc = run_edit(ctx, a, insert ? insert_steps(a.groups) : remove_steps(a.groups), true, &s);
+    if (rc == VRT_OK) rc = insert ? edit_error(ctx, s, kErrsOfInsert, "; nothing was inserted") : edit_error(ctx, s, kErrsOfRemove, "; nothing was removed");
     if (rc != VRT_OK) return rc;
-    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
-    if (s.err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, "a voxel lies outside the grid; nothing was removed");
-    if (s.err & vrt::kEditErrCell)
-        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5); nothing was removed");
-    // exactly what lost a bit: the status words of the cells that became unloaded, the occupancy bytes (a batch of no-ops: nothing)
-    if (s.cell_lo <= s.cell_hi) mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
-    if (s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
+    mark_written(ctx, s, insert ? kWritesOfInsert : kWritesOfRemove, s.bricks - s.new_bricks);
     return VRT_OK;
 }
 
 // the scene's dead bricks given back: the chain over cells and bricks, as one scene write
 int compact(vrt_ctx *ctx, uint32_t out[2]) {
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
     const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
     const uint32_t brick_alloc = (uint32_t)(ctx->dsize[VRT_BUF_BRICK_START_INDEX] / 4u);
-    int rc = edit_scratch(ctx, std::max<uint64_t>(brick_alloc, 1u), false); // its scratch: the per-voxel words of a batch of brick_alloc voxels
+    int rc = edit_scratch(ctx, std::max<uint64_t>(brick_alloc, 1u)); // its scratch: the per-voxel words of a batch of brick_alloc voxels
     if (rc != VRT_OK) return rc;
-    rc = begin_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, nullptr, nullptr, brick_alloc, !ctx->edit_state_valid);
-    a.op = vrt::kEditOpCompact;
+    vrt::EditArgs a = edit_args(ctx, vrt::kEditOpCompact, nullptr, nullptr, brick_alloc);
     a.cells = (uint32_t)cells;
-    const uint32_t brick_groups = a.groups; // (also what vrt_edit_scan_groups scans)
     const uint32_t cell_groups = (uint32_t)((std::max<uint64_t>(cells, brick_alloc) + vrt::kEditBlock - 1u) / vrt::kEditBlock);
-    const uint32_t copy_groups = std::min<uint32_t>(cell_groups, vrt::kEditCopyGroups);
     VRT_HIP(ctx, hipMemsetAsync(a.vinfo, 0, (size_t)brick_alloc * sizeof(uint32_t), ctx->stream)); // no brick is live yet
-    rc = launch_state(ctx, a);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, cell_groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, brick_groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, brick_groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, brick_groups, vrt::kEditBlock);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, copy_groups, vrt::kEditBlock);
-    a.phase = 1;
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, copy_groups, vrt::kEditBlock);
-    if (rc != VRT_OK) {
-        (void)wait_stream(ctx->stream);
-        ctx->edit_state_valid = false;
-        return rc;
-    }
-    rc = end_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
     vrt::EditStatus s;
-    rc = read_status(ctx, a, &s);
+    rc = run_edit(ctx, a, compact_steps(cell_groups, a.groups, std::min<uint32_t>(cell_groups, vrt::kEditCopyGroups)), false, &s);
+    if (rc == VRT_OK) rc = edit_error(ctx, s, kErrsOfCompact, "; nothing was compacted");
     if (rc != VRT_OK) return rc;
-    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
-    if (s.err & vrt::kEditErrSlot)
-        return fail(ctx, VRT_E_STATE, "an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3; nothing was compacted");
-    if (s.err & vrt::kEditErrCell)
-        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5); nothing was compacted");
     if (out) out[0] = s.bricks + s.new_bricks, out[1] = s.bricks;
-    if (s.new_bricks == 0) return VRT_OK; // no dead brick: nothing was written
-    // exactly what was written: the renamed cells, the filled holes and the cleared tail, the entries of binding 5 that were unset
-    if (s.cell_lo <= s.cell_hi) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
-    mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
-    mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)s.bricks * 4u, (uint64_t)s.new_bricks * 4u);
-    ctx->edit_state_valid = true; // (the device state already holds L and its cursor: this write is the compaction's own)
-    if (s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    // the renamed cells, the filled holes and the cleared tail (a range whenever a brick was freed), the entries of binding 5 that were
+    // unset; no dead brick: nothing was written
+    if (s.new_bricks) mark_written(ctx, s, kWritesOfCompact, s.bricks);
     return VRT_OK;
 }
 
 // n shapes (host memory) filled into or cleared from the scene: the batch screened and clipped on the host, one record per shape that
 // holds a voxel of the grid's range staged into device memory, then the fill's or the clear's part of the chain as one scene write
 int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    const char *nothing = fill ? "; nothing was filled" : "; nothing was cleared";
     std::string why;
     int rc = vrt::screen_shapes(shapes, n, fill, &why);
-    if (rc != VRT_OK) return fail(ctx, rc, why + (fill ? "; nothing was filled" : "; nothing was cleared"));
+    if (rc != VRT_OK) return fail(ctx, rc, why + nothing);
     if (ctx->dist) return fail(ctx, VRT_E_STATE, "shape edits are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
     const uint32_t b = ctx->cfg.brick_dimension, words = b * b * b / 32u;
@@ -1108,72 +1109,17 @@ int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
     rc = edit_prepare(ctx, "shape edits are");
     if (rc != VRT_OK) return rc;
     if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
-    const uint64_t bytes = recs.size() * sizeof(vrt::ShapeRec);
-    if (ctx->edit_input_bytes < bytes) {
-        ctx->res.drop(ctx->d_edit_input);
-        ctx->edit_input_bytes = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_input, bytes));
-        ctx->edit_input_bytes = bytes;
-    }
-    rc = staged_copy_h2d(ctx, ctx->d_edit_input, recs.data(), bytes);
-    if (rc == VRT_OK) rc = edit_scratch(ctx, items, false);
+    rc = stage_input(ctx, recs.data(), recs.size() * sizeof(vrt::ShapeRec));
+    if (rc == VRT_OK) rc = edit_scratch(ctx, items);
     if (rc != VRT_OK) return rc;
-    rc = begin_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, nullptr, nullptr, (uint32_t)items, !ctx->edit_state_valid);
-    a.op = fill ? vrt::kEditOpFill : vrt::kEditOpClear;
+    vrt::EditArgs a = edit_args(ctx, fill ? vrt::kEditOpFill : vrt::kEditOpClear, nullptr, nullptr, (uint32_t)items);
     a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
     a.shape_count = (uint32_t)recs.size();
-    const uint32_t groups = a.groups;
-    rc = launch_state(ctx, a);
-    if (rc == VRT_OK) rc = launch(ctx, vrt_edit_validate, a, groups, vrt::kEditBlock);
-    if (fill) {
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_count, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_scan_groups, a, 1, vrt::kEditScanBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_rank, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_resolve, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
-    } else {
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
-        a.phase = 1;
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_write, a, groups, vrt::kEditBlock);
-        if (rc == VRT_OK) rc = launch(ctx, vrt_edit_table, a, groups, vrt::kEditBlock);
-    }
-    if (rc != VRT_OK) {
-        (void)wait_stream(ctx->stream);
-        ctx->res.drop(ctx->d_edit_cell_first); // (a chain cut short may leave scratch words set: made anew, clean, by the next batch)
-        ctx->edit_state_valid = false;
-        return rc;
-    }
-    rc = end_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
     vrt::EditStatus s;
-    rc = read_status(ctx, a, &s);
+    rc = run_edit(ctx, a, fill ? insert_steps(a.groups) : remove_steps(a.groups), true, &s);
+    if (rc == VRT_OK) rc = edit_error(ctx, s, fill ? kErrsOfFill : kErrsOfClear, nothing);
     if (rc != VRT_OK) return rc;
-    const char *nothing = fill ? "; nothing was filled" : "; nothing was cleared";
-    if (s.err & vrt::kEditErrShape) return not_shaped(ctx);
-    if (s.err & vrt::kEditErrCell)
-        return fail(ctx, VRT_E_STATE, std::string("a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5)") + nothing);
-    if (s.err & vrt::kEditErrOom)
-        return fail(ctx, VRT_E_OOM, "the batch needs " + std::to_string(s.new_bricks) + " new bricks: brick_alloc or the material entries are exhausted" + nothing);
-    // the derived structures follow exactly what was written, as for inserts and removals
-    if (s.cell_lo <= s.cell_hi) {
-        mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
-        if (fill) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
-    }
-    if (s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
-    if (fill && s.new_bricks) {
-        mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)(s.bricks - s.new_bricks) * 4u, (uint64_t)s.new_bricks * 4u);
-        ctx->edit_state_valid = true; // (the device state already counts these bricks: this write is the fill's own)
-    }
-    if (fill && s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
-    return VRT_OK;
-}
-
-int check_batch(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
-    if (!xyz || !materials) return fail(ctx, VRT_E_INVALID_ARG, "xyz or materials is NULL");
-    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
+    mark_written(ctx, s, fill ? kWritesOfInsert : kWritesOfRemove, s.bricks - s.new_bricks);
     return VRT_OK;
 }
 
@@ -1181,82 +1127,12 @@ int check_batch(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uin
 
 extern "C" {
 
-int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    int rc = check_batch(ctx, xyz, materials, n);
-    if (rc != VRT_OK) return rc;
-    DeviceGuard dg(ctx->device);
-    rc = edit_prepare(ctx);
-    if (rc != VRT_OK) return rc;
-    return insert(ctx, xyz, materials, n);
-}
-
-int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    int rc = check_batch(ctx, xyz, materials, n);
-    if (rc != VRT_OK) return rc;
-    DeviceGuard dg(ctx->device);
-    rc = edit_prepare(ctx);
-    if (rc != VRT_OK) return rc;
-    // the batch into device memory through the pinned staging slots (xyz, then the material bytes behind it)
-    const uint64_t xyz_bytes = 12u * n, bytes = xyz_bytes + n;
-    if (ctx->edit_input_bytes < bytes) {
-        ctx->res.drop(ctx->d_edit_input);
-        ctx->edit_input_bytes = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_input, bytes));
-        ctx->edit_input_bytes = bytes;
-    }
-    rc = staged_copy_h2d(ctx, ctx->d_edit_input, xyz, xyz_bytes);
-    if (rc == VRT_OK) rc = staged_copy_h2d(ctx, ctx->d_edit_input + xyz_bytes, materials, n);
-    if (rc != VRT_OK) return rc;
-    return insert(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), ctx->d_edit_input + xyz_bytes, n);
-}
-
-int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
-    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
-    DeviceGuard dg(ctx->device);
-    const int rc = edit_prepare(ctx, "voxel removals are");
-    if (rc != VRT_OK) return rc;
-    return remove(ctx, xyz, n);
-}
-
-int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
-    if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
-    DeviceGuard dg(ctx->device);
-    int rc = edit_prepare(ctx, "voxel removals are");
-    if (rc != VRT_OK) return rc;
-    // the batch into device memory through the pinned staging slots
-    const uint64_t bytes = 12u * n;
-    if (ctx->edit_input_bytes < bytes) {
-        ctx->res.drop(ctx->d_edit_input);
-        ctx->edit_input_bytes = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_input, bytes));
-        ctx->edit_input_bytes = bytes;
-    }
-    rc = staged_copy_h2d(ctx, ctx->d_edit_input, xyz, bytes);
-    if (rc != VRT_OK) return rc;
-    return remove(ctx, reinterpret_cast<const uint32_t *>(ctx->d_edit_input), n);
-}
-
-int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    return edit_shapes(ctx, shapes, n, true);
-}
-
-int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    return edit_shapes(ctx, shapes, n, false);
-}
+int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, false); }
+int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, true); }
+int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, false); }
+int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, true); }
+int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, true); }
+int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, false); }
 
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     if (!ctx) return VRT_E_INVALID_ARG;
@@ -1273,7 +1149,7 @@ int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     int rc = edit_prepare(ctx);
     if (rc != VRT_OK) return rc;
     if (!ctx->edit_state_valid) {
-        vrt::EditArgs a = edit_args(ctx, nullptr, nullptr, 0, true);
+        vrt::EditArgs a = edit_args(ctx, vrt::kEditOpInsert, nullptr, nullptr, 0);
         rc = launch_state(ctx, a);
         if (rc != VRT_OK) return rc;
         vrt::EditStatus s;

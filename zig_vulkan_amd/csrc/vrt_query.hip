@@ -300,47 +300,19 @@ using namespace vrt_impl;
 
 namespace {
 
-// vrt_ray_query_b4 / _b8 over `groups` workgroups: the a.n rays of one launch, or the tiles of the first-hit buffer pass
+// vrt_ray_query_b4 / _b8 over `groups` workgroups: the a.n elements of one launch, or the tiles of the first-hit buffer pass
 hipError_t launch_ray_query(const vrt::QueryArgs &a, int brick_dimension, hipStream_t stream, dim3 groups) {
     if (brick_dimension == 8) VRT_LAUNCH(vrt_ray_query_b8, groups, dim3(vrt::kQueryBlock), 0, stream, a);
     else VRT_LAUNCH(vrt_ray_query_b4, groups, dim3(vrt::kQueryBlock), 0, stream, a);
     return hipGetLastError();
 }
 
-// What both entry points check and do before their first launch: the scene is there, and the derived structures are current (on the
-// primary stream, behind the uploads).
+// What the ray queries and the first-hit buffer pass check and do before their first launch: the scene is there, and the derived
+// structures are current (on the primary stream, behind the uploads).
 int query_begin(vrt_ctx *ctx) {
     if (ctx->dist) return fail(ctx, VRT_E_STATE, "ray queries are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
     return refresh_derived(ctx);
-}
-
-// n rays at `rays` (device memory) -> hits, in launches of at most kQueryLaunchRays rays, on the primary stream
-int launch_queries(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits) {
-    vrt::QueryArgs a{};
-    a.p = ctx->params;
-    a.mode = vrt::kQueryModeRays;
-    for (uint64_t first = 0; first < n; first += vrt::kQueryLaunchRays) {
-        a.rays = rays + first;
-        a.hits = hits + first;
-        a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchRays);
-        const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
-        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
-    }
-    return VRT_OK;
-}
-
-// The host paths' two device buffers hold at least `want` rays (32 bytes in, 48 bytes out each)
-int query_buffers(vrt_ctx *ctx, uint64_t want) {
-    if (ctx->query_capacity >= want) return VRT_OK;
-    VRT_HIP(ctx, wait_stream(ctx->stream)); // (the previous query may still use the buffers)
-    ctx->res.drop(ctx->d_query_rays);
-    ctx->res.drop(ctx->d_query_hits);
-    ctx->query_capacity = 0;
-    VRT_HIP(ctx, ctx->res.device(&ctx->d_query_rays, want * sizeof(vrt_ray_query)));
-    VRT_HIP(ctx, ctx->res.device(&ctx->d_query_hits, want * sizeof(vrt_ray_hit)));
-    ctx->query_capacity = want;
-    return VRT_OK;
 }
 
 // What the volume queries check of the context.  They read bindings 2-6 alone, which every upload and edit writes on the primary stream:
@@ -354,37 +326,54 @@ int volume_begin(vrt_ctx *ctx) {
     return VRT_OK;
 }
 
-vrt::QueryArgs volume_args(vrt_ctx *ctx, uint32_t mode) {
+// The three batched queries: the kernels' mode, the elements one launch takes at most and one workgroup takes, and the bytes of an
+// element going in and coming out
+struct QueryKind {
+    uint32_t mode;
+    uint64_t per_launch;
+    uint32_t per_group;
+    uint32_t in_bytes, out_bytes;
+};
+constexpr QueryKind kRays = {vrt::kQueryModeRays, vrt::kQueryLaunchRays, vrt::kQueryBlock, sizeof(vrt_ray_query), sizeof(vrt_ray_hit)};
+constexpr QueryKind kVoxels = {vrt::kQueryModeVoxels, vrt::kQueryLaunchRays, vrt::kQueryBlock, 3u * sizeof(uint32_t), sizeof(uint16_t)};
+constexpr QueryKind kBoxes = {vrt::kQueryModeBoxes, vrt::kQueryLaunchBoxes, vrt::kBoxesPerGroup, sizeof(vrt_box_query), sizeof(vrt_box_result)};
+static_assert(kVoxels.in_bytes <= kRays.in_bytes && kBoxes.in_bytes <= kRays.in_bytes && kVoxels.out_bytes <= kRays.out_bytes && kBoxes.out_bytes <= kRays.out_bytes,
+              "a ray's share of the host forms' device buffers holds an element of any kind");
+
+// n elements at `in` (device memory) -> out, in launches of at most k.per_launch elements, on the primary stream
+int launch_batch(vrt_ctx *ctx, const QueryKind &k, const void *in, uint64_t n, void *out) {
     vrt::QueryArgs a{};
     a.p = ctx->params;
-    a.mode = mode;
-    a.vol_bricks = (uint32_t)ctx->cfg.brick_alloc; // (brick_alloc * B^3 <= 2^31)
-    return a;
-}
-
-// n voxels at `xyz` (device memory) -> out, in launches of at most kQueryLaunchRays voxels, on the primary stream
-int launch_voxel_queries(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
-    vrt::QueryArgs a = volume_args(ctx, vrt::kQueryModeVoxels);
-    for (uint64_t first = 0; first < n; first += vrt::kQueryLaunchRays) {
-        a.vol_xyz = xyz + 3u * first;
-        a.vol_materials = out + first;
-        a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchRays);
-        const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
+    a.mode = k.mode;
+    if (k.mode != vrt::kQueryModeRays) a.vol_bricks = (uint32_t)ctx->cfg.brick_alloc; // (brick_alloc * B^3 <= 2^31)
+    for (uint64_t first = 0; first < n; first += k.per_launch) {
+        const void *src = static_cast<const uint8_t *>(in) + first * k.in_bytes;
+        void *dst = static_cast<uint8_t *>(out) + first * k.out_bytes;
+        if (k.mode == vrt::kQueryModeRays) a.rays = static_cast<const vrt_ray_query *>(src), a.hits = static_cast<vrt_ray_hit *>(dst);
+        else if (k.mode == vrt::kQueryModeVoxels) a.vol_xyz = static_cast<const uint32_t *>(src), a.vol_materials = static_cast<uint16_t *>(dst);
+        else a.vol_boxes = static_cast<const vrt::u32x4 *>(src), a.vol_results = static_cast<vrt::u32x4 *>(dst);
+        a.n = std::min<uint64_t>(n - first, k.per_launch);
+        const dim3 groups((uint32_t)((a.n + k.per_group - 1u) / k.per_group));
         VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
     }
     return VRT_OK;
 }
 
-// n boxes at `boxes` (device memory) -> results, in launches of at most kQueryLaunchBoxes boxes, on the primary stream
-int launch_box_queries(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
-    vrt::QueryArgs a = volume_args(ctx, vrt::kQueryModeBoxes);
-    for (uint64_t first = 0; first < n; first += vrt::kQueryLaunchBoxes) {
-        a.vol_boxes = reinterpret_cast<const vrt::u32x4 *>(boxes + first);
-        a.vol_results = reinterpret_cast<vrt::u32x4 *>(results + first);
-        a.n = std::min<uint64_t>(n - first, vrt::kQueryLaunchBoxes);
-        const dim3 groups((uint32_t)((a.n + vrt::kBoxesPerGroup - 1u) / vrt::kBoxesPerGroup));
-        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
+// The host forms: n elements at `in` (host memory) -> out, through the context's two device buffers, a piece of at most
+// kQueryHostPieceRays elements at a time (a ray's share of the buffers, 32 bytes in and 48 out, holds an element of any kind), and
+// one wait at the end
+int staged_batch(vrt_ctx *ctx, const QueryKind &k, const void *in, uint64_t n, void *out) {
+    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
+    int rc = grow_device(ctx, ctx->query_capacity, want, true, ctx->d_query_rays, want * sizeof(vrt_ray_query), ctx->d_query_hits, want * sizeof(vrt_ray_hit));
+    if (rc != VRT_OK) return rc;
+    for (uint64_t first = 0; first < n; first += want) {
+        const uint64_t m = std::min(n - first, want);
+        VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, static_cast<const uint8_t *>(in) + first * k.in_bytes, m * k.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_batch(ctx, k, ctx->d_query_rays, m, ctx->d_query_hits);
+        if (rc != VRT_OK) return rc;
+        VRT_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(out) + first * k.out_bytes, ctx->d_query_hits, m * k.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
+    VRT_HIP(ctx, wait_stream(ctx->stream));
     return VRT_OK;
 }
 
@@ -460,13 +449,8 @@ int vrt_trace_aux(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_p
     uint64_t want = 0;
     for (int k = 0; k < 4; k++)
         if (host[k]) want += pixels * (k < 3 ? 16u : 4u);
-    if (ctx->aux_capacity < want) {
-        VRT_HIP(ctx, wait_stream(ctx->stream)); // (the previous pass may still use the buffer)
-        ctx->res.drop(ctx->d_aux_planes);
-        ctx->aux_capacity = 0;
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_aux_planes, want));
-        ctx->aux_capacity = want;
-    }
+    rc = grow_device(ctx, ctx->aux_capacity, want, true, ctx->d_aux_planes, want); // (waits: the previous pass may still use the buffer)
+    if (rc != VRT_OK) return rc;
     uint8_t *dev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t at = 0;
     for (int k = 0; k < 4; k++)
@@ -491,7 +475,7 @@ int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vr
     DeviceGuard dg(ctx->device);
     const int rc = query_begin(ctx);
     if (rc != VRT_OK) return rc;
-    return launch_queries(ctx, rays, n, hits);
+    return launch_batch(ctx, kRays, rays, n, hits);
 }
 
 int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_hit *hits) {
@@ -501,21 +485,9 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vrt_ray_h
     for (uint64_t i = 0; i < n; i++)
         if (rays[i].flags & ~VRT_RAY_RAW_DIRECTION) return fail(ctx, VRT_E_INVALID_ARG, "ray " + std::to_string(i) + " has unknown flag bits");
     DeviceGuard dg(ctx->device);
-    int rc = query_begin(ctx);
+    const int rc = query_begin(ctx);
     if (rc != VRT_OK) return rc;
-    // through the context's two device buffers, a piece of at most kQueryHostPieceRays rays at a time
-    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
-    rc = query_buffers(ctx, want);
-    if (rc != VRT_OK) return rc;
-    for (uint64_t first = 0; first < n; first += want) {
-        const uint64_t m = std::min(n - first, want);
-        VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays + first, m * sizeof(vrt_ray_query), hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_queries(ctx, ctx->d_query_rays, m, ctx->d_query_hits);
-        if (rc != VRT_OK) return rc;
-        VRT_HIP(ctx, hipMemcpyAsync(hits + first, ctx->d_query_hits, m * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VRT_HIP(ctx, wait_stream(ctx->stream));
-    return VRT_OK;
+    return staged_batch(ctx, kRays, rays, n, hits);
 }
 
 int vrt_get_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
@@ -526,7 +498,7 @@ int vrt_get_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_
     DeviceGuard dg(ctx->device);
     const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
-    return launch_voxel_queries(ctx, xyz, n, out);
+    return launch_batch(ctx, kVoxels, xyz, n, out);
 }
 
 int vrt_get_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out) {
@@ -534,23 +506,9 @@ int vrt_get_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n, uint16_t *out)
     if (n == 0) return VRT_OK;
     if (!xyz || !out) return fail(ctx, VRT_E_INVALID_ARG, "xyz or out is NULL");
     DeviceGuard dg(ctx->device);
-    int rc = volume_begin(ctx);
+    const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
-    // through the ray queries' two device buffers (12 bytes in, 2 bytes out per voxel: a ray's share holds both), a piece at a time
-    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
-    rc = query_buffers(ctx, want);
-    if (rc != VRT_OK) return rc;
-    uint32_t *d_xyz = reinterpret_cast<uint32_t *>(ctx->d_query_rays);
-    uint16_t *d_out = reinterpret_cast<uint16_t *>(ctx->d_query_hits);
-    for (uint64_t first = 0; first < n; first += want) {
-        const uint64_t m = std::min(n - first, want);
-        VRT_HIP(ctx, hipMemcpyAsync(d_xyz, xyz + 3u * first, m * 3u * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_voxel_queries(ctx, d_xyz, m, d_out);
-        if (rc != VRT_OK) return rc;
-        VRT_HIP(ctx, hipMemcpyAsync(out + first, d_out, m * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VRT_HIP(ctx, wait_stream(ctx->stream));
-    return VRT_OK;
+    return staged_batch(ctx, kVoxels, xyz, n, out);
 }
 
 int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
@@ -561,7 +519,7 @@ int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n,
     DeviceGuard dg(ctx->device);
     const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
-    return launch_box_queries(ctx, boxes, n, results);
+    return launch_batch(ctx, kBoxes, boxes, n, results);
 }
 
 int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) {
@@ -571,23 +529,9 @@ int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_bo
     for (uint64_t i = 0; i < n; i++)
         if (boxes[i].flags | boxes[i]._reserved) return fail(ctx, VRT_E_INVALID_ARG, "box " + std::to_string(i) + " has unknown flag bits or a non-zero _reserved");
     DeviceGuard dg(ctx->device);
-    int rc = volume_begin(ctx);
+    const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
-    // through the ray queries' two device buffers (32 bytes in, 32 bytes out per box), a piece at a time
-    const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
-    rc = query_buffers(ctx, want);
-    if (rc != VRT_OK) return rc;
-    vrt_box_query *d_boxes = reinterpret_cast<vrt_box_query *>(ctx->d_query_rays);
-    vrt_box_result *d_results = reinterpret_cast<vrt_box_result *>(ctx->d_query_hits);
-    for (uint64_t first = 0; first < n; first += want) {
-        const uint64_t m = std::min(n - first, want);
-        VRT_HIP(ctx, hipMemcpyAsync(d_boxes, boxes + first, m * sizeof(vrt_box_query), hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_box_queries(ctx, d_boxes, m, d_results);
-        if (rc != VRT_OK) return rc;
-        VRT_HIP(ctx, hipMemcpyAsync(results + first, d_results, m * sizeof(vrt_box_result), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VRT_HIP(ctx, wait_stream(ctx->stream));
-    return VRT_OK;
+    return staged_batch(ctx, kBoxes, boxes, n, results);
 }
 
 // CameraGetRay (comp:474-477) for sample 0 (hash12(0) = 0: no jitter), as vrt_trace_kernel forms it: u = x / (w - 1), v = y / (h - 1),
