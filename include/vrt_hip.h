@@ -774,10 +774,19 @@ typedef struct vrt_denoise_config {
 } vrt_denoise_config;
 int vrt_denoise(vrt_ctx *ctx, const vrt_denoise_config *cfg /* NULL => reference defaults */, uint32_t out_w, uint32_t out_h,
                 uint32_t want_float);
+/* The image of the MOST RECENT vrt_denoise call, whatever is still in flight: the reads wait for that pass and for nothing else.  A
+ * context with two frames in flight keeps one output image per frame slot — consecutive passes run on the two frame streams and never
+ * share an image or an event, and neither stream waits for the other — so an earlier, slower pass can neither overwrite the image that
+ * is read nor be read in its place.
+ * vrt_read_denoised_rgba32f: the float image exists only if the most recent pass was asked for it: after a vrt_denoise with
+ * want_float = 0 it returns VRT_E_STATE until a pass with want_float = 1 has run (never an older pass's image).
+ * vrt_device_denoised_rgba8: the device image of the most recent pass, written on that pass's stream (vrt_wait, or a read, before
+ * another stream uses it).  With two frames in flight the pointer alternates between the two slots' images from one vrt_denoise to the
+ * next: ask again after every pass; a change of the output size frees both. */
 int vrt_read_denoised_rgba8(vrt_ctx *ctx, void *dst, uint64_t nbytes);
 int vrt_read_denoised_rgba32f(vrt_ctx *ctx, void *dst, uint64_t nbytes);
 void *vrt_device_denoised_rgba8(vrt_ctx *ctx);
-/* hipEvent time of the most recent vrt_denoise launch in milliseconds (waits for it); <0 if none was issued.  With
+/* hipEvent time of the most recent vrt_denoise launch in milliseconds (waits for it; that pass's own two events, on its own stream); <0 if none was issued.  With
  * vrt_last_kernel_ms this is the app's whole frame: trace (ComputePipeline.zig:417-463) + present (GraphicsPipeline.zig:27-39). */
 double vrt_last_denoise_ms(vrt_ctx *ctx);
 

@@ -253,8 +253,10 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     }
     VRT_CREATE_HIP(c->res.event(&c->ev_start));
     VRT_CREATE_HIP(c->res.event(&c->ev_stop));
-    VRT_CREATE_HIP(c->res.event(&c->ev_post_start));
-    VRT_CREATE_HIP(c->res.event(&c->ev_post_stop));
+    for (int k = 0; k < 2; k++) {
+        VRT_CREATE_HIP(c->res.event(&c->ev_post_start[k]));
+        VRT_CREATE_HIP(c->res.event(&c->ev_post_stop[k]));
+    }
 
     // buffer sizes as Pipeline.zig:273-283 derives them from the State slices
     c->dsize[VRT_BUF_GRID_STATE] = sizeof(vrt_grid_state);

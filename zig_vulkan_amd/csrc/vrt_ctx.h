@@ -173,7 +173,13 @@ struct vrt_ctx {
     uint64_t sched_seq = 0, b_seen_sched = 0;
     hipEvent_t ev_sched = nullptr, ev_b_sched = nullptr;
     bool b_sched_recorded = false;
-    void *d_denoised8 = nullptr, *d_denoised32f = nullptr;       // output of the present/denoise pass
+    // Output of the present / denoise pass, one image per frame slot: with two frames in flight consecutive passes run on the two frame
+    // streams with nothing ordering them, so each writes its own slot's image (a slot's passes follow one another on one stream) and
+    // denoised_slot names the image of the most recent pass — what vrt_read_denoised_* and vrt_device_denoised_rgba8 hand out.
+    // denoised_float: that pass wrote the float image too.
+    void *d_denoised8[2] = {nullptr, nullptr}, *d_denoised32f[2] = {nullptr, nullptr};
+    int denoised_slot = 0;
+    bool denoised_float = false;
     Dist *dist = nullptr;                                        // multi-GPU frame pipeline (vrt_dist_*)
     uint32_t denoised_w = 0, denoised_h = 0;
     hipStream_t denoised_stream = nullptr;
@@ -239,7 +245,7 @@ struct vrt_ctx {
     bool split_ok = false;   // small frames may go to half-tile workgroups (vrt_create's conditions other than the number of waves)
     uint32_t simds = 1024u;
     hipEvent_t ev_region[4] = {}; // vrt_region_begin / _end: {begin, end} on the primary stream, {begin, end} on the second
-    hipEvent_t ev_post_start = nullptr, ev_post_stop = nullptr; // around the most recent present / denoise pass (vrt_last_denoise_ms)
+    hipEvent_t ev_post_start[2] = {nullptr, nullptr}, ev_post_stop[2] = {nullptr, nullptr}; // around each slot's most recent present / denoise pass (vrt_last_denoise_ms: denoised_slot's)
     // Round 6, VRT_TUNE_PRESENT_OWN_STREAM: contexts with two frames in flight run the present pass on a stream of its own, behind an
     // event of the frame it reads — the reference's graphics queue behind the compute queue's semaphore (Pipeline.zig:494-517); the frame
     // after next waits for the pass to have read its target (ev_post_done[slot]).  Not the default: see vrt_denoise.

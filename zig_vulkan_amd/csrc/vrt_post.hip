@@ -334,14 +334,23 @@ int vrt_denoise(vrt_ctx *ctx, const vrt_denoise_config *cfg, uint32_t out_w, uin
         }
         s = ctx->stream_post;
     }
-    if (ctx->denoised_w != out_w || ctx->denoised_h != out_h || (want_float && !ctx->d_denoised32f)) {
+    // One output image per frame slot (vrt_ctx.h): this pass and the previous one — on the other frame stream when two frames are in
+    // flight — never write the same image, and no stream waits for the other.
+    if (ctx->denoised_w != out_w || ctx->denoised_h != out_h || (want_float && !ctx->d_denoised32f[0])) {
         VRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->stream_b) VRT_HIP(ctx, hipStreamSynchronize(ctx->stream_b));
         if (ctx->stream_post) VRT_HIP(ctx, hipStreamSynchronize(ctx->stream_post));
-        ctx->res.drop(ctx->d_denoised8);
-        ctx->res.drop(ctx->d_denoised32f);
-        VRT_HIP(ctx, ctx->res.device(&ctx->d_denoised8, (size_t)out_w * out_h * 4u));
-        if (want_float) VRT_HIP(ctx, ctx->res.device(&ctx->d_denoised32f, (size_t)out_w * out_h * 16u));
+        const bool with_float = want_float || ctx->d_denoised32f[0];
+        ctx->denoised_w = ctx->denoised_h = 0;
+        ctx->denoised_float = false;
+        for (int k = 0; k < 2; k++) {
+            ctx->res.drop(ctx->d_denoised8[k]);
+            ctx->res.drop(ctx->d_denoised32f[k]);
+        }
+        for (int k = 0; k < (ctx->stream_b ? 2 : 1); k++) {
+            VRT_HIP(ctx, ctx->res.device(&ctx->d_denoised8[k], (size_t)out_w * out_h * 4u));
+            if (with_float) VRT_HIP(ctx, ctx->res.device(&ctx->d_denoised32f[k], (size_t)out_w * out_h * 16u));
+        }
         ctx->denoised_w = out_w;
         ctx->denoised_h = out_h;
     }
@@ -350,31 +359,34 @@ int vrt_denoise(vrt_ctx *ctx, const vrt_denoise_config *cfg, uint32_t out_w, uin
         VRT_HIP(ctx, hipEventRecord(ctx->ev_post_src[slot], frame_stream));
         VRT_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_post_src[slot], 0));
     }
-    VRT_HIP(ctx, hipEventRecord(ctx->ev_post_start, s));
+    VRT_HIP(ctx, hipEventRecord(ctx->ev_post_start[slot], s));
     VRT_HIP(ctx, vrt::launch_denoise(img, (int)ctx->cfg.width, (int)ctx->cfg.height, c.samples, c.distribution_bias, c.pixel_multiplier,
-                                     c.inverse_hue_tolerance, (int)out_w, (int)out_h, ctx->d_denoised8, want_float ? ctx->d_denoised32f : nullptr, s));
-    VRT_HIP(ctx, hipEventRecord(ctx->ev_post_stop, s));
+                                     c.inverse_hue_tolerance, (int)out_w, (int)out_h, ctx->d_denoised8[slot], want_float ? ctx->d_denoised32f[slot] : nullptr, s));
+    VRT_HIP(ctx, hipEventRecord(ctx->ev_post_stop[slot], s));
     if (overlap) { // (the next frame into this target waits until the pass has read it: do_dispatch)
         VRT_HIP(ctx, hipEventRecord(ctx->ev_post_done[slot], s));
         ctx->post_pending[slot] = true;
     }
     ctx->post_timed = true;
     ctx->denoised_stream = s;
+    ctx->denoised_slot = slot;
+    ctx->denoised_float = want_float != 0; // (a pass without the float image leaves an older pass's there: not this pass's, so not readable)
     return VRT_OK;
 }
 
 double vrt_last_denoise_ms(vrt_ctx *ctx) {
     if (!ctx || !ctx->post_timed) return -1.0;
     DeviceGuard dg(ctx->device);
-    if (wait_event(ctx->ev_post_stop) != hipSuccess) return -1.0;
+    const int k = ctx->denoised_slot; // (the most recent pass's own pair of events, both recorded on its stream)
+    if (wait_event(ctx->ev_post_stop[k]) != hipSuccess) return -1.0;
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, ctx->ev_post_start, ctx->ev_post_stop) != hipSuccess) return -1.0;
+    if (hipEventElapsedTime(&ms, ctx->ev_post_start[k], ctx->ev_post_stop[k]) != hipSuccess) return -1.0;
     return (double)ms;
 }
 
 static int read_denoised(vrt_ctx *ctx, void *dst, uint64_t nbytes, const void *src, uint64_t avail) {
     if (!ctx || !dst) return VRT_E_INVALID_ARG;
-    if (!src) return fail(ctx, VRT_E_STATE, "no denoised image (call vrt_denoise first; want_float for the float image)");
+    if (!src) return fail(ctx, VRT_E_STATE, "no denoised image of the most recent pass (call vrt_denoise first; want_float for the float image)");
     if (nbytes > avail) return fail(ctx, VRT_E_OUT_OF_RANGE, "read exceeds the denoised image");
     DeviceGuard dg(ctx->device);
     VRT_HIP(ctx, hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, ctx->denoised_stream));
@@ -382,11 +394,13 @@ static int read_denoised(vrt_ctx *ctx, void *dst, uint64_t nbytes, const void *s
     return VRT_OK;
 }
 int vrt_read_denoised_rgba8(vrt_ctx *ctx, void *dst, uint64_t nbytes) {
-    return read_denoised(ctx, dst, nbytes, ctx ? ctx->d_denoised8 : nullptr, ctx ? (uint64_t)ctx->denoised_w * ctx->denoised_h * 4u : 0);
+    return read_denoised(ctx, dst, nbytes, ctx ? ctx->d_denoised8[ctx->denoised_slot] : nullptr, ctx ? (uint64_t)ctx->denoised_w * ctx->denoised_h * 4u : 0);
 }
 int vrt_read_denoised_rgba32f(vrt_ctx *ctx, void *dst, uint64_t nbytes) {
-    return read_denoised(ctx, dst, nbytes, ctx ? ctx->d_denoised32f : nullptr, ctx ? (uint64_t)ctx->denoised_w * ctx->denoised_h * 16u : 0);
+    // (only the most recent pass's float image: after a pass without one, an older pass's is not handed out)
+    return read_denoised(ctx, dst, nbytes, ctx && ctx->denoised_float ? ctx->d_denoised32f[ctx->denoised_slot] : nullptr,
+                         ctx ? (uint64_t)ctx->denoised_w * ctx->denoised_h * 16u : 0);
 }
-void *vrt_device_denoised_rgba8(vrt_ctx *ctx) { return ctx ? ctx->d_denoised8 : nullptr; }
+void *vrt_device_denoised_rgba8(vrt_ctx *ctx) { return ctx ? ctx->d_denoised8[ctx->denoised_slot] : nullptr; }
 
 } // extern "C"
