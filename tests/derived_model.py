@@ -1,5 +1,5 @@
 """A plain numpy model of the structures the library derives from the scene (refresh_derived; read back with VoxelRT.read_derived),
-written from their definitions (the comments of vrt_trace.hip, include/vrt_hip.h), not from the builders: tests/test_derived_model.py
+written from their definitions (the comments of vrt_derived.hip, include/vrt_hip.h), not from the builders: tests/test_derived_model.py
 checks it by hand-made cases, tests/test_derived_structures_gpu.py compares the device's copies with it byte for byte.
 
 Every function takes scene arrays as VoxelRT.read_buffer / BrickGrid.array give them (status, brick index and start index as uint32

@@ -24,6 +24,38 @@ CASES = [(f, b, d) for f in FAMILY_NAMES for b in (4, 8) for d in (ODD, EVEN)]
 IDS = [f"{f}-b{b}-{'x'.join(map(str, d))}" for f, b, d in CASES]
 KINDS = ("terrain", "clumps", "interleaved", "empty")
 SPARE = 600
+# What each context keeps (the ids of kept(rt), vrt_derived_id: 0 cell_bounds, 1 status_bytes, 2 status_halfblocks, 3 cell_occupancy,
+# 4 cell_material, 5 cell_box, 6 start_is_slot, 7 materials_plain), recorded by running kept(rt) on the library of the commit BEFORE the derived
+# structures moved into a unit of their own — not on the library under test: which kernel entry reads which structure is what moved.
+KEPT = {
+    ("single", 4, ODD): [0, 1, 3, 6, 7],
+    ("single", 4, EVEN): [0, 1, 3, 6, 7],
+    ("single", 8, ODD): [0, 1, 3, 5, 6, 7],
+    ("single", 8, EVEN): [0, 1, 3, 5, 6, 7],
+    ("single_v5", 4, ODD): [0, 3, 6, 7],
+    ("single_v5", 4, EVEN): [0, 3, 6, 7],
+    ("single_v5", 8, ODD): [0, 3, 6, 7],
+    ("single_v5", 8, EVEN): [0, 3, 6, 7],
+    ("samples", 4, ODD): [0, 1, 3, 6, 7],
+    ("samples", 4, EVEN): [0, 1, 3, 6, 7],
+    ("samples", 8, ODD): [0, 1, 3, 5, 6, 7],
+    ("samples", 8, EVEN): [0, 1, 3, 5, 6, 7],
+    ("lockstep", 4, ODD): [0, 1, 3, 6, 7],
+    ("lockstep", 4, EVEN): [0, 1, 3, 6, 7],
+    ("lockstep", 8, ODD): [0, 1, 3, 5, 6, 7],
+    ("lockstep", 8, EVEN): [0, 1, 3, 5, 6, 7],
+    ("path", 4, ODD): [0, 1, 3, 6, 7],
+    ("path", 4, EVEN): [0, 1, 2, 3, 6, 7],
+    ("path", 8, ODD): [0, 1, 3, 5, 6, 7],
+    ("path", 8, EVEN): [0, 1, 2, 3, 5, 6, 7],
+    ("pool", 4, ODD): [0, 1, 3, 6, 7],
+    ("pool", 4, EVEN): [0, 1, 2, 3, 4, 6, 7],
+    ("pool", 8, ODD): [0, 1, 3, 5, 6, 7],
+    ("pool", 8, EVEN): [0, 1, 2, 3, 4, 5, 6, 7],
+}
+# ... and a context told to do without every structure a tuning flag can switch off (recorded in the same way)
+FEWEST = L.TUNE_NO_CELL_OCCUPANCY | L.TUNE_NO_CELL_MATERIAL | L.TUNE_NO_DEFERRED_MATERIAL | L.TUNE_NO_START_SHORTCUT
+KEPT_FEWEST = [0, 1, 5]   # ("single", 8, ODD)
 
 
 # ---- the comparison ---------------------------------------------------------------------------------------------------------------
@@ -175,6 +207,7 @@ def test_a_whole_upload(family, b, dims):
     for kind in KINDS:
         g = scene_grid(kind, dims, b)
         rt = _family_context(g, family)
+        assert kept(rt) == KEPT[(family, b, dims)], (family, b, dims, kind)
         got = assert_derived(rt, f"{family} b{b} {dims} {kind}", g)
         if kind == "empty":
             assert got[L.DERIVED_CELL_BOUNDS].view(np.uint32).tolist() == [0x80808080] * 6
@@ -199,6 +232,21 @@ def test_every_structure_is_kept_by_some_case():
         print(f"{family} b{b} {'x'.join(map(str, dims))}: {', '.join(L.DERIVED_NAMES[i] for i in ids)}")
     for i in range(L.DERIVED_COUNT):
         assert any(i in ids for ids in seen.values()), f"no case keeps {L.DERIVED_NAMES[i]}"
+
+
+def test_a_context_that_keeps_the_fewest_structures():
+    """refresh_derived clears the flags and ranges of structures the context does not keep: after an insert the few it keeps are current,
+    and equal a fresh context's."""
+    g = make_grid("clumps", ODD, 8, brick_alloc=SPARE, seed=11)
+    rt = _family_context(g, "single", tuning_flags=FEWEST)
+    assert kept(rt) == KEPT_FEWEST
+    e = Edits(rt, g, "single b8 13x7x9, the fewest structures")
+    e.check("upload")
+    cell = int(loaded_cells(g)[0])
+    e.insert([cell], [e.empty_voxel(cell)], [3], "one insert")
+    assert_equals_a_fresh_context(rt, "single", e.tag, tuning_flags=FEWEST)
+    rt.deinit()
+    g.deinit()
 
 
 # ---- 2-9. edits, one after another, on one context ------------------------------------------------------------------------------------

@@ -223,8 +223,9 @@ FRAME_CASES = [(f, b) for f in FAMILIES for b in (4, 8)]
 
 def _family_context(g, family, **extra):
     spp, bounces, kw, _ = FAMILIES[family]
+    kw = {**kw, **extra, "tuning_flags": kw.get("tuning_flags", 0) | extra.get("tuning_flags", 0)}   # (a caller's tuning flags join the family's)
     cfg = Config(internal_resolution_width=E.WIDTH, internal_resolution_height=E.HEIGHT, camera=E.camera_config(spp, bounces),
-                 sun=SunConfig(enabled=True, radius=5.0 if bounces else 0.0), want_float_output=True, **kw, **extra)
+                 sun=SunConfig(enabled=True, radius=5.0 if bounces else 0.0), want_float_output=True, **kw)
     rt = VoxelRT(g, cfg)
     rt.push_materials(default_materials(256))
     return rt

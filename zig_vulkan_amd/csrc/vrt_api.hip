@@ -1,6 +1,6 @@
 // vrt_api.hip — the context behind the C ABI of include/vrt_hip.h: creation (device buffers, streams, events, kernel
 // selection), destruction, the seven stream-ordered uploads through a pinned staging ring, read-back, counters.
-// The frame itself is vrt_frame.hip, the multi-GPU pipeline vrt_dist.hip, the present pass vrt_post.hip.
+// The structures derived from the scene are vrt_derived.hip, the frame vrt_frame.hip, the multi-GPU pipeline vrt_dist.hip, the present pass vrt_post.hip.
 //
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.  There is no CPU fallback:
@@ -57,37 +57,6 @@ int end_scene_write(vrt_ctx *c) {
         c->upload_seq++;
     }
     return VRT_OK;
-}
-
-// which derived structures a write to scene buffer `id` invalidates (rebuilt before the next frame, pre_dispatch)
-void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t nbytes) {
-    if (id == VRT_BUF_BRICK_STATUS) ctx->status_dirty = true;
-    if (id == VRT_BUF_BRICK_START_INDEX) ctx->start_dirty = true, ctx->edit_state_valid = false; // (the inserts' allocation state comes from brick_start_indices)
-    if (id == VRT_BUF_MATERIALS) ctx->materials_dirty = true;
-    if (id == VRT_BUF_GRID_STATE || id == VRT_BUF_MATERIALS) return;
-    auto widen = [](uint64_t &lo, uint64_t &hi, uint64_t a, uint64_t b) {
-        if (lo >= hi) lo = a, hi = b;
-        else lo = std::min(lo, a), hi = std::max(hi, b);
-    };
-    const uint64_t end = byte_offset + nbytes;
-    const uint64_t brick_bytes = (uint64_t)ctx->cfg.brick_dimension * ctx->cfg.brick_dimension * ctx->cfg.brick_dimension / 8u;
-    // (both by-cell structures follow the cells and the occupancy slots; the material byte also the start indices and the entries of binding 7)
-    if (id == VRT_BUF_BRICK_STATUS) {
-        widen(ctx->occ_cell_lo, ctx->occ_cell_hi, byte_offset * 8u, end * 8u);
-        widen(ctx->cm_cell_lo, ctx->cm_cell_hi, byte_offset * 8u, end * 8u);
-    } else if (id == VRT_BUF_BRICK_INDEX) {
-        widen(ctx->occ_cell_lo, ctx->occ_cell_hi, byte_offset / 4u, (end + 3u) / 4u);
-        widen(ctx->cm_cell_lo, ctx->cm_cell_hi, byte_offset / 4u, (end + 3u) / 4u);
-    } else if (id == VRT_BUF_BRICK_OCCUPANCY) {
-        widen(ctx->occ_slot_lo, ctx->occ_slot_hi, byte_offset / brick_bytes, (end + brick_bytes - 1u) / brick_bytes);
-        widen(ctx->cm_slot_lo, ctx->cm_slot_hi, byte_offset / brick_bytes, (end + brick_bytes - 1u) / brick_bytes);
-    } else if (id == VRT_BUF_BRICK_START_INDEX) {
-        widen(ctx->cm_slot_lo, ctx->cm_slot_hi, byte_offset / 4u, (end + 3u) / 4u);
-    } else {
-        widen(ctx->cm_mat_lo, ctx->cm_mat_hi, byte_offset, end);
-    }
-    if (id == VRT_BUF_BRICK_STATUS || id == VRT_BUF_BRICK_INDEX || id == VRT_BUF_BRICK_OCCUPANCY) ctx->occupancy_dirty = true;
-    ctx->cell_material_dirty = true;
 }
 
 // the unit counters and (contexts that select vrt_pool_kernel) the path records of one stream of persistent-kernel frames
@@ -361,10 +330,6 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         VRT_CREATE_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(vrt::DeviceCounters), c->stream));
     }
     const uint32_t nbx = (cfg->dim_x + 3u) / 4u, nby = (cfg->dim_y + 3u) / 4u, nbz = (cfg->dim_z + 3u) / 4u;
-    VRT_CREATE_HIP(c->res.device(&c->d_cell_bounds, 6 * sizeof(int)));
-    VRT_CREATE_HIP(hipMemsetAsync(c->d_cell_bounds, 0x80, 6 * sizeof(int), c->stream)); // no cell occupied yet
-    // (the other derived copies of the status bits — byte per cell, half-block words, 4^3 block words — are allocated further
-    // down, each only when a kernel this context selects reads it)
     {
         // tile schedule starts as reverse raster (bottom rows first); the feedback kernel refines it
         const uint32_t n = sh.owned_tiles ? sh.owned_tiles : 1u;
@@ -554,79 +519,10 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
             return fail(nullptr, VRT_E_INVALID_ARG, "no kernel for this kernel_variant in the product build of libvrt_hip (development variants: make dev)");
 #endif
         }
-        // derived copies of the status bits, each only if a kernel of this context reads it
-        auto any_kernel = [&](auto pred) {
-            const vrt::KernelFn fns[12] = {c->kernel, c->kernel_lockstep, c->kernel_single, c->kernel_single1, c->product[0], c->product[1], c->product[2],
-                                           c->kernel_grid_exit, c->product_grid_exit, c->kernel_grid_exit_path, c->product_grid_exit_path, c->bounce_auto};
-            for (vrt::KernelFn fn : fns) {
-                const vrt::KernelEntry *e = fn ? vrt::kernel_entry_of(fn) : nullptr;
-                if (e && pred(*e)) return true;
-            }
-            return false;
-        };
-        if (any_kernel([](const vrt::KernelEntry &e) { return !e.path && e.mode == vrt::kStatusBytes; })) {
-            const size_t status_bytes_size = (size_t)((cells + 31u) / 32u) * 32u + 64u; // 32 bytes per status word
-            VRT_CREATE_HIP(c->res.device(&c->d_status_bytes, status_bytes_size));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_status_bytes, 0, status_bytes_size, c->stream));
-        }
-        if (any_kernel([](const vrt::KernelEntry &e) { return e.path && (e.half || e.dil); })) {
-            const size_t bytes_hb = (size_t)(cells / 32u) * 4u + 64u;
-            VRT_CREATE_HIP(c->res.device(&c->d_status_halfblocks, bytes_hb));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_status_halfblocks, 0, bytes_hb, c->stream));
-        }
-        if (any_kernel([](const vrt::KernelEntry &e) { return e.path && e.dist; })) {
-            VRT_CREATE_HIP(c->res.device(&c->d_cell_distance, (size_t)cells + 64u));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_cell_distance, 0xFF, (size_t)cells + 64u, c->stream));
-        }
-        // the by-cell copy of the occupancy bits, for the persistent-lane kernel (scenes larger than the caches, where a brick entry
-        // is a chain of dependent misses): at most 2 GiB, and — walked in global memory instead of LDS — a 32-bit bit index
-        const uint64_t by_cell_bytes = cells * (bits / 8u);
-        const bool lds_walk = cfg->brick_dimension == 8u && !(cfg->tuning_flags & VRT_TUNE_NO_PATH_BRICK_LDS);
-        // (an optional structure — within a quarter of the memory that is free now, and a failed allocation means "no
-        // by-cell copy", not a failed vrt_create: the kernels then reach a brick's bits through brick_index as the shader does)
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = 0;
-        // (round 4: also for the lockstep bounce kernel on scenes that stay in the caches — up to 64 MiB of it —, whose brick entries then
-        // request the bits without waiting for brick_index[cell]: brick_walk_gfx950<..., BY_CELL>)
-        const bool persistent = any_kernel([](const vrt::KernelEntry &e) { return e.path != 0; });
-        const bool lockstep_bounce = any_kernel([](const vrt::KernelEntry &e) { return e.path == 0 && e.shade == 0 && !e.count; }) &&
-                                     by_cell_bytes <= (64ull << 20) && cells * bits <= (1ull << 32);
-        if ((persistent || lockstep_bounce) && !(cfg->tuning_flags & VRT_TUNE_NO_CELL_OCCUPANCY) &&
-            by_cell_bytes <= (2ull << 30) && by_cell_bytes + 64u <= mem_free / 4u && (lds_walk || cells * bits <= (1ull << 32))) {
-            if (c->res.device(&c->d_cell_occupancy, by_cell_bytes + 64u) != hipSuccess) {
-                (void)hipGetLastError();
-                c->d_cell_occupancy = nullptr;
-            } else {
-                VRT_CREATE_HIP(hipMemsetAsync(c->d_cell_occupancy, 0, by_cell_bytes + 64u, c->stream));
-                c->cell_occupancy_lockstep = lockstep_bounce;
-            }
-        }
-        // (round 5) the material a cell's brick is made of, for the hits vrt_pool_kernel shades in its rounds of transitions
-        if (!(cfg->tuning_flags & (VRT_TUNE_NO_CELL_MATERIAL | VRT_TUNE_NO_DEFERRED_MATERIAL)) && any_kernel([](const vrt::KernelEntry &e) { return e.path == 2; })) {
-            VRT_CREATE_HIP(c->res.device(&c->d_cell_material, (size_t)cells + 64u));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_cell_material, 0xFF, (size_t)cells + 64u, c->stream));
-        }
-        // the box of a cell's solid voxels, for the brick rejection test of the one-sample kernel on 8^3 bricks (brick_reject): 4 bytes per
-        // cell, 1 MiB at 64^3 cells; at most 16 MiB (not on the 2048^3 scenes, whose frames the persistent kernels trace; without the
-        // array the kernel rejects nothing).  Starts as the whole brick, which never rejects; the first frame builds it for every occupied cell.
-        if (cells <= (1ull << 22) && any_kernel([](const vrt::KernelEntry &e) { return vrt::reads_cell_box(e); })) {
-            VRT_CREATE_HIP(c->res.device(&c->d_cell_box, (size_t)cells * 4u + 64u));
-            VRT_CREATE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_cell_box), (int)vrt::full_cell_box(cfg->brick_dimension), cells + 16u, c->stream));
-        }
-        if (!(cfg->tuning_flags & VRT_TUNE_NO_DEFERRED_MATERIAL)) {
-            VRT_CREATE_HIP(c->res.device(&c->d_materials_plain, 64u));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_materials_plain, 0, 64u, c->stream));
-        }
-        if (!(cfg->tuning_flags & VRT_TUNE_NO_START_SHORTCUT)) {
-            VRT_CREATE_HIP(c->res.device(&c->d_start_is_slot, 64u));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_start_is_slot, 0, 64u, c->stream));
-        }
-        if (any_kernel([](const vrt::KernelEntry &e) { return (e.path && (e.filter || e.dil == 3)) || (!e.path && (e.mode == vrt::kStatusBlocked || e.mode == vrt::kStatusBlockedLds)); })) {
-            const size_t nblocks = (size_t)nbx * nby * nbz;
-            const size_t status_blocks_bytes = nblocks * 8u + ((nblocks + 31u) / 32u) * 4u + 16u;
-            VRT_CREATE_HIP(c->res.device(&c->d_status_blocks, status_blocks_bytes));
-            VRT_CREATE_HIP(hipMemsetAsync(c->d_status_blocks, 0, status_blocks_bytes, c->stream));
-        }
+        // the structures derived from the scene buffers, each only if one of these kernels reads it
+        const vrt::KernelFn fns[12] = {c->kernel, c->kernel_lockstep, c->kernel_single, c->kernel_single1, c->product[0], c->product[1], c->product[2],
+                                       c->kernel_grid_exit, c->product_grid_exit, c->kernel_grid_exit_path, c->product_grid_exit_path, c->bounce_auto};
+        VRT_CREATE_HIP(derived_create(c, fns, 12));
     }
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
@@ -707,17 +603,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     // the hand-written voxel-level loop addresses brick_occupancy by a 32-bit global bit index: brick_alloc * B^3 <= 2^31
     // (the u31 start-index check above), so it always reaches
     p.occupancy_words = (uint32_t)(c->dsize[VRT_BUF_BRICK_OCCUPANCY] / 4u);
-    p.status_blocks = static_cast<const uint2 *>(c->d_status_blocks);
-    p.cell_bounds = c->d_cell_bounds;
-    p.status_bytes = c->d_status_bytes;
-    p.status_halfblocks = c->d_status_halfblocks;
-    p.cell_distance = c->d_cell_distance;
-    p.cell_occupancy = c->d_cell_occupancy;
-    p.cell_occupancy_lockstep = (c->d_cell_occupancy && c->cell_occupancy_lockstep) ? 1u : 0u;
-    p.start_is_slot = c->d_start_is_slot;
-    p.materials_plain = c->d_materials_plain;
-    p.cell_material = c->d_cell_material;
-    p.cell_box = c->d_cell_box;
+    derived_bind(c->derived, p);
     p.status_cells = (uint32_t)cells;
     // (order_auto: frames that alternate between the two streams of a frames_in_flight = 2 context take reverse raster (3)
     // instead, see do_dispatch and DESIGN.md §4)

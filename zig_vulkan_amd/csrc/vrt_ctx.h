@@ -1,10 +1,11 @@
 // vrt_ctx.h — the context behind the C ABI of include/vrt_hip.h, shared by the units that implement it:
-//   vrt_api.hip    creation / destruction, the seven uploads (pinned staging ring), read-back, counters
-//   vrt_frame.hip  one frame: refresh of the derived structures, kernel choice, tile schedule, launch, timing
-//   vrt_dist.hip   the multi-GPU frame pipeline (RCCL through dlopen)
-//   vrt_post.hip   the present / denoise pass
-//   vrt_query.hip  batched ray queries (their kernels and host side)
-//   vrt_edit.hip   batched voxel inserts (their kernels and host side)
+//   vrt_api.hip      creation / destruction, the seven uploads (pinned staging ring), read-back, counters
+//   vrt_derived.hip  the structures derived from the scene buffers (vrt::Derived): their builder kernels, allocation, invalidation, refresh, read-back
+//   vrt_frame.hip    one frame: kernel choice, tile schedule, launch, timing
+//   vrt_dist.hip     the multi-GPU frame pipeline (RCCL through dlopen)
+//   vrt_post.hip     the present / denoise pass
+//   vrt_query.hip    batched ray queries, the first-hit buffer pass and the volume queries — voxel look-ups, box counts (their kernels and host side)
+//   vrt_edit.hip     batched voxel inserts and removals, shape edits, brick compaction (their kernels and host side)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
 #pragma once
@@ -33,17 +34,6 @@ hipError_t launch_schedule(const uint32_t *cost, uint32_t *snap, const uint32_t 
                            hipStream_t stream);
 hipError_t launch_assemble_rgb(const void *gathered, void *frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_count,
                                uint32_t tiles_per_rank, const TileOwnership &own, hipStream_t stream, uint32_t frames, uint32_t frame_src_stride_bytes);
-hipError_t launch_build_status_blocks(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
-hipError_t launch_build_status_bytes(const TraceParams &p, hipStream_t stream);
-hipError_t launch_build_status_halfblocks(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
-hipError_t launch_build_cell_distance(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
-hipError_t launch_build_cell_bounds(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream);
-hipError_t launch_build_cell_occupancy(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
-                                       uint64_t slot_hi, hipStream_t stream);
-hipError_t launch_build_cell_material(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
-                                      uint64_t slot_hi, uint64_t mat_lo, uint64_t mat_hi, hipStream_t stream);
-hipError_t launch_check_start_is_slot(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, hipStream_t stream);
-hipError_t launch_check_materials_plain(const TraceParams &p, uint32_t count, hipStream_t stream);
 hipError_t launch_denoise(const void *img, int W, int H, int samples, float bias, float mult, float tol, int out_w, int out_h, void *out_u8,
                           void *out_f32, hipStream_t stream);
 hipError_t launch_assemble(const void *gathered, void *frame, uint32_t bytes_per_pixel, uint32_t width, uint32_t height, uint32_t tiles_x,
@@ -136,6 +126,42 @@ struct Dist; // vrt_dist.hip
 namespace vrt {
 struct EditState;  // vrt_edit.hip
 struct EditStatus;
+
+// A range [lo, hi) of cells, brick slots or bytes written since the structures that follow them were last refreshed (lo >= hi: none)
+struct DirtyRange {
+    uint64_t lo = 0, hi = 0;
+    bool empty() const { return lo >= hi; }
+    void widen(uint64_t a, uint64_t b) { *this = empty() ? DirtyRange{a, b} : DirtyRange{a < lo ? a : lo, b > hi ? b : hi}; }
+    void clear() { lo = hi = 0; }
+};
+
+// The structures derived from the scene buffers, each kept only if a kernel the context selects reads it (nullptr otherwise; TraceParams
+// carries the same pointers to the kernels), and what has been written since they were built.  All of vrt_derived.hip's.
+struct Derived {
+    uint2 *status_blocks = nullptr;        // 4x4x4 block words + block filter (development variants)
+    int *cell_bounds = nullptr;            // bounding box of the occupied cells (TraceParams::cell_bounds; every context)
+    uint8_t *status_bytes = nullptr;       // one byte per grid cell (TraceParams::status_bytes)
+    uint8_t *cell_distance = nullptr;      // L1 distance of every cell to the nearest occupied cell (vrt_path_kernel<DIST>, development)
+    uint32_t *status_halfblocks = nullptr; // status bits by 4 x 4 x 2 cells per word (vrt_path_kernel on eligible grids)
+    uint8_t *cell_occupancy = nullptr;     // occupancy bits by cell (TraceParams::cell_occupancy; vrt_path_kernel, within a memory budget)
+    bool cell_occupancy_lockstep = false;  // ... read by the lockstep bounce kernel too (scenes that stay in the caches)
+    uint32_t *start_is_slot = nullptr;     // 1 = binding 6 holds slot * B^3 for every allocated brick (TraceParams::start_is_slot)
+    uint32_t *materials_plain = nullptr;   // 1 = no material record has the type MAT_NONE (TraceParams::materials_plain)
+    uint8_t *cell_material = nullptr;      // the material every solid voxel of a cell's brick shares, a byte per cell (TraceParams::cell_material; vrt_pool_kernel)
+    uint32_t *cell_box = nullptr;          // the box of the solid voxels of a cell's brick, a word per cell (TraceParams::cell_box; the one-sample kernel on 8^3 bricks)
+    bool status_dirty = true;        // binding 3 changed since its copies (blocks, bounds, bytes, half-blocks, distance) were built
+    bool start_dirty = true;         // binding 6 changed since it was checked
+    bool materials_dirty = true;     // binding 0 changed since it was checked
+    bool occupancy_dirty = true;     // bindings 3-5 changed since the by-cell occupancy was built ...
+    // ... in these ranges (ADVICE r03: the reference issues a single-brick delta every frame, VoxelRT.zig:107-172; the copy is then
+    // refreshed for the cells and brick slots it names, not gathered anew over the whole grid): cells whose status bit / brick index
+    // changed, brick slots whose occupancy bytes changed.  Before the first refresh: every cell
+    DirtyRange occ_cell{0, ~0ull}, occ_slot;
+    // cell_material and cell_box, built by one pass: cells (status / index), slots (occupancy / start index), entries (bytes of binding 7)
+    bool cell_material_dirty = true;
+    DirtyRange cm_cell{0, ~0ull}, cm_slot, cm_mat;
+    bool any_dirty() const { return status_dirty || occupancy_dirty || start_dirty || materials_dirty || cell_material_dirty; }
+};
 } // namespace vrt
 
 struct vrt_ctx {
@@ -183,41 +209,16 @@ struct vrt_ctx {
     Dist *dist = nullptr;                                        // multi-GPU frame pipeline (vrt_dist_*)
     uint32_t denoised_w = 0, denoised_h = 0;
     hipStream_t denoised_stream = nullptr;
-    void *d_status_blocks = nullptr; // derived: 4x4x4 block words + block filter (vrt_trace.hip)
-    int *d_cell_bounds = nullptr;    // derived: bounding box of the occupied cells (TraceParams::cell_bounds)
-    // The host's copy of that box (read back behind every rebuild, never waited for): when it is, or nearly is, the grid, bounce
-    // frames of a context whose kernel is the dilated-index path kernel are traced by its twin without steps-left counters.
+    vrt::Derived derived;      // the structures derived from the scene buffers (vrt_derived.hip)
+    // The host's copy of the box of the occupied cells, Derived::cell_bounds (read back behind every rebuild, never waited for): when it
+    // is, or nearly is, the grid, bounce frames of a context whose kernel is the dilated-index path kernel are traced by its twin without steps-left counters.
     int *h_cell_bounds = nullptr;
     hipEvent_t ev_bounds = nullptr;
     bool bounds_pending = false, box_is_grid = false;
     // frames with bounces once the box is known to be the grid: vrt_pool_kernel where it applies, else vrt_path_kernel<..., DIL 2>;
     // *_path: that DIL-2 twin kept beside a pool kernel, for the frames the pool kernel cannot take
     vrt::KernelFn kernel_grid_exit = nullptr, product_grid_exit = nullptr, kernel_grid_exit_path = nullptr, product_grid_exit_path = nullptr;
-    uint8_t *d_status_bytes = nullptr; // derived: one byte per grid cell (TraceParams::status_bytes)
-    uint8_t *d_cell_distance = nullptr;      // derived: L1 distance of every cell to the nearest occupied cell (vrt_path_kernel<DIST>)
-    uint32_t *d_status_halfblocks = nullptr; // derived: status bits by 4 x 4 x 2 cells per word (vrt_path_kernel on eligible grids)
-    bool cell_occupancy_lockstep = false;    // ... read by the lockstep bounce kernel too (scenes that stay in the caches)
-    uint8_t *d_cell_occupancy = nullptr;     // derived: occupancy bits by cell (TraceParams::cell_occupancy; vrt_path_kernel, within a memory budget)
-    uint32_t *d_start_is_slot = nullptr;     // derived: 1 = binding 6 holds slot * B^3 for every allocated brick (TraceParams::start_is_slot)
-    bool occupancy_dirty = true;             // bindings 3-5 changed since the by-cell copy was built ...
-    // ... in these ranges (ADVICE r03: the reference issues a single-brick delta every frame, VoxelRT.zig:107-172; the copy is then
-    // refreshed for the cells and brick slots it names, not gathered anew over the whole grid): cells whose status bit / brick index
-    // changed and brick slots whose occupancy bytes changed, both [lo, hi); lo >= hi: none
-    uint64_t occ_cell_lo = 0, occ_cell_hi = ~0ull, occ_slot_lo = 0, occ_slot_hi = 0;
-    // derived (round 5): the material every solid voxel of a cell's brick shares, a byte per cell (TraceParams::cell_material; contexts that
-    // select vrt_pool_kernel).  Refreshed like the by-cell occupancy, for what was written: cells [occ_cell_lo, hi) (status / index),
-    // slots [cm_slot_lo, hi) (occupancy / start index), material entries [cm_mat_lo, hi) (bytes of binding 7); lo >= hi: none
-    uint8_t *d_cell_material = nullptr;
-    // derived: the box of the solid voxels of a cell's brick, a word per cell (TraceParams::cell_box; contexts that select the one-sample
-    // kernel on 8^3 bricks).  Built by the same pass and for the same written ranges as d_cell_material
-    uint32_t *d_cell_box = nullptr;
-    bool cell_material_dirty = true;
-    uint64_t cm_cell_lo = 0, cm_cell_hi = ~0ull, cm_slot_lo = 0, cm_slot_hi = 0, cm_mat_lo = 0, cm_mat_hi = 0;
-    uint32_t *d_materials_plain = nullptr;   // derived: 1 = no material record has the type MAT_NONE (TraceParams::materials_plain)
-    bool materials_dirty = true;             // binding 0 changed since it was checked
-    bool start_dirty = true;                 // binding 6 changed since it was checked
     vrt::TileOwnership own{};        // weighted tile ownership (period 0: tile t belongs to rank t % shard_count)
-    bool status_dirty = true;        // brick_status changed since the derived copy was built
     bool grid_uploaded = false;      // binding 1 has been uploaded (ray queries need the grid's geometry)
     // ray queries (vrt_query.hip): the host path's device buffers
     vrt_ray_query *d_query_rays = nullptr;
@@ -356,12 +357,19 @@ void free_ctx(vrt_ctx *c);
 // the scene on another stream, and later frames on those streams must see them.
 int begin_scene_write(vrt_ctx *c);
 int end_scene_write(vrt_ctx *c);
-// which derived structures a write to scene buffer `id` invalidates (rebuilt before the next frame, pre_dispatch)
-void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t nbytes);
 // the unit counters and (contexts that select vrt_pool_kernel) the path records of one stream of persistent-kernel frames
 int lane_init(vrt_ctx *c, vrt::PersistentLane &lane);
 // host memory -> device memory through the pinned staging slots, on the primary stream, as a scene write (vrt_upload's copy)
 int staged_copy_h2d(vrt_ctx *c, void *dst, const void *src, uint64_t nbytes);
+
+// ---- vrt_derived.hip ----
+hipError_t derived_create(vrt_ctx *c, const vrt::KernelFn *kernels, int n); // vrt_create: the structures the kernels it selected read, allocated and filled ...
+void derived_bind(const vrt::Derived &d, vrt::TraceParams &p);               // ... and named to the kernels
+// which derived structures a write to scene buffer `id` invalidates (rebuilt before the next frame, pre_dispatch)
+void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t nbytes);
+// the grid-scale reciprocals of TraceParams and every structure derived from the scene buffers, brought up to date with the uploads so far
+// (stream-ordered on the primary stream): the part of pre_dispatch that frames, queries and edits share
+int refresh_derived(vrt_ctx *ctx);
 
 // ---- vrt_frame.hip ----
 void note_kernel(vrt_ctx *c, vrt::KernelFn fn); // remember which kernel rendered the most recent frame (vrt_kernel_name reports what ran)
@@ -375,9 +383,8 @@ int finish_frame(vrt_ctx *c);                   // wait for the frame in flight 
 int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_device *sun, vrt::PersistentLane *lane, hipStream_t lane_stream, vrt::KernelFn *fn,
                  vrt::KernelFn *product_fn, bool *with_samples, int trial = -1);
 bool lane_samples_ready(vrt_ctx *ctx, vrt::PersistentLane &lane, uint64_t units, hipStream_t lane_stream);
-// the grid-scale reciprocals of TraceParams and every structure derived from the scene buffers, brought up to date with the uploads so far
-// (stream-ordered on the primary stream): the part of pre_dispatch that frames and ray queries share
-int refresh_derived(vrt_ctx *ctx);
+// behind a rebuild of Derived::cell_bounds, inside refresh_derived's scene write: its copy to the host, which decides box_is_grid
+int read_back_cell_bounds(vrt_ctx *ctx);
 uint64_t sample_units(const vrt_ctx *ctx, int samples_per_pixel); // units of a frame of this context (0: not a frame of units)
 void lane_into_params(const vrt::PersistentLane &lane, bool with_samples, vrt::TraceParams &p);
 

@@ -377,7 +377,7 @@ static int dist_queue_frame(vrt_ctx *ctx, const vrt_camera_device *camera, const
     Dist *d = ctx->dist;
     // (a refresh of the derived structures is a scene write and launches what is queued: do that now, so that the launch slot — and with
     // it the lane — this frame's batch will use is known before the kernel is chosen)
-    if (d->npend && (ctx->status_dirty || ctx->occupancy_dirty || ctx->start_dirty || ctx->materials_dirty || ctx->cell_material_dirty)) {
+    if (d->npend && ctx->derived.any_dirty()) {
         const int rcf = dist_flush(ctx);
         if (rcf != VRT_OK) return rcf;
     }

@@ -1,9 +1,8 @@
-// vrt_frame.hip — one frame behind the C ABI: refresh of the structures derived from the scene buffers, the choice of the
-// traversal kernel, the cost-feedback tile schedule, the launch on one of the context's streams, its timing.
+// vrt_frame.hip — one frame behind the C ABI: the choice of the traversal kernel (behind refresh_derived, vrt_derived.hip), the
+// cost-feedback tile schedule, the launch on one of the context's streams, its timing.
 // Replaces ComputePipeline.dispatch (src/modules/voxel_rt/ComputePipeline.zig:417-463).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 #include "vrt_ctx.h"
@@ -88,71 +87,19 @@ static vrt::KernelFn grid_exit_choice(vrt_ctx *ctx, vrt::KernelFn exit_fn, vrt::
     return exit_path ? exit_path : keep;
 }
 
-int refresh_derived(vrt_ctx *ctx) {
-    const vrt_grid_state &g = ctx->params.grid;
-    {
-        auto pow2_with_normal_reciprocal = [](float v) {
-            uint32_t b;
-            std::memcpy(&b, &v, 4);
-            const uint32_t e = (b >> 23) & 0xFFu;
-            return (b & 0x7FFFFFu) == 0u && e >= 2u && e <= 252u;
-        };
-        const float gs = g.max_point_scale[3];
-        const float vs = gs * (1.0f / (float)ctx->cfg.brick_dimension); // as the kernel forms it (Pipeline.zig:313)
-        const bool ok = pow2_with_normal_reciprocal(gs) && pow2_with_normal_reciprocal(vs);
-        ctx->params.scale_pow2 = ok ? 1u : 0u;
-        ctx->params.inv_grid_scale = ok ? 1.0f / gs : 0.0f;
-        ctx->params.inv_voxel_scale = ok ? 1.0f / vs : 0.0f;
-    }
-    if (g.dim_x != 0 && (g.dim_x != ctx->cfg.dim_x || g.dim_y != ctx->cfg.dim_y || g.dim_z != ctx->cfg.dim_z))
-        return fail(ctx, VRT_E_INVALID_ARG, "uploaded grid state has other brick dimensions than the context was created with");
-    if (ctx->status_dirty) {
-        // refresh the derived block words / filter from the uploaded status bits (stream-ordered after the uploads)
-        int rcw = begin_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-        VRT_HIP(ctx, vrt::launch_build_status_blocks(ctx->params, ctx->cfg.dim_x, ctx->cfg.dim_y, ctx->cfg.dim_z, ctx->stream));
-        VRT_HIP(ctx, vrt::launch_build_cell_bounds(ctx->params, ctx->cfg.dim_x, ctx->cfg.dim_y, ctx->cfg.dim_z, ctx->stream));
-        if (ctx->kernel_grid_exit || ctx->product_grid_exit || ctx->bounce_auto) {
-            if (!ctx->h_cell_bounds) VRT_HIP(ctx, ctx->res.pinned(&ctx->h_cell_bounds, 6 * sizeof(int)));
-            if (!ctx->ev_bounds) VRT_HIP(ctx, ctx->res.event(&ctx->ev_bounds, hipEventDisableTiming));
-            if (ctx->bounds_pending) VRT_HIP(ctx, hipEventSynchronize(ctx->ev_bounds)); // (the copy before this one still owns the buffer)
-            VRT_HIP(ctx, hipMemcpyAsync(ctx->h_cell_bounds, ctx->d_cell_bounds, 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            VRT_HIP(ctx, hipEventRecord(ctx->ev_bounds, ctx->stream));
-            ctx->bounds_pending = true;
-            ctx->box_is_grid = false; // until the new box is known
-            ctx->auto_next = 0;       // (another scene: the bounce kernel's auto-tune starts again)
-            ctx->auto_decided = ctx->auto_use_pool = false;
-        }
-        VRT_HIP(ctx, vrt::launch_build_status_bytes(ctx->params, ctx->stream));
-        VRT_HIP(ctx, vrt::launch_build_status_halfblocks(ctx->params, ctx->cfg.dim_x, ctx->cfg.dim_y, ctx->cfg.dim_z, ctx->stream));
-        VRT_HIP(ctx, vrt::launch_build_cell_distance(ctx->params, ctx->cfg.dim_x, ctx->cfg.dim_y, ctx->cfg.dim_z, ctx->stream));
-        rcw = end_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-        ctx->status_dirty = false;
-    }
-    if ((ctx->occupancy_dirty && ctx->d_cell_occupancy) || (ctx->start_dirty && ctx->d_start_is_slot) || (ctx->materials_dirty && ctx->d_materials_plain)) {
-        int rcw = begin_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-        if (ctx->occupancy_dirty)
-            VRT_HIP(ctx, vrt::launch_build_cell_occupancy(ctx->params, ctx->cfg.brick_dimension, ctx->cfg.brick_alloc, ctx->occ_cell_lo, ctx->occ_cell_hi, ctx->occ_slot_lo,
-                                                          ctx->occ_slot_hi, ctx->stream));
-        if (ctx->start_dirty) VRT_HIP(ctx, vrt::launch_check_start_is_slot(ctx->params, ctx->cfg.brick_dimension, ctx->cfg.brick_alloc, ctx->stream));
-        if (ctx->materials_dirty) VRT_HIP(ctx, vrt::launch_check_materials_plain(ctx->params, std::max<uint32_t>(256u, (uint32_t)(ctx->dsize[VRT_BUF_MATERIALS] / sizeof(vrt_material))), ctx->stream));
-        rcw = end_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-    }
-    ctx->occupancy_dirty = ctx->start_dirty = ctx->materials_dirty = false;
-    ctx->occ_cell_lo = ctx->occ_cell_hi = ctx->occ_slot_lo = ctx->occ_slot_hi = 0;
-    if (ctx->cell_material_dirty && (ctx->d_cell_material || ctx->d_cell_box)) {
-        int rcw = begin_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-        VRT_HIP(ctx, vrt::launch_build_cell_material(ctx->params, ctx->cfg.brick_dimension, ctx->cfg.brick_alloc, ctx->cm_cell_lo, ctx->cm_cell_hi, ctx->cm_slot_lo, ctx->cm_slot_hi,
-                                                     ctx->cm_mat_lo, ctx->cm_mat_hi, ctx->stream));
-        rcw = end_scene_write(ctx);
-        if (rcw != VRT_OK) return rcw;
-    }
-    ctx->cell_material_dirty = false;
-    ctx->cm_cell_lo = ctx->cm_cell_hi = ctx->cm_slot_lo = ctx->cm_slot_hi = ctx->cm_mat_lo = ctx->cm_mat_hi = 0;
+// Behind every rebuild of the box of the occupied cells (refresh_derived, inside its scene write): contexts whose bounce kernel depends
+// on the box copy it to the host — pinned, behind an event, never waited for; pre_dispatch looks at it once it has arrived.
+int read_back_cell_bounds(vrt_ctx *ctx) {
+    if (!(ctx->kernel_grid_exit || ctx->product_grid_exit || ctx->bounce_auto)) return VRT_OK;
+    if (!ctx->h_cell_bounds) VRT_HIP(ctx, ctx->res.pinned(&ctx->h_cell_bounds, 6 * sizeof(int)));
+    if (!ctx->ev_bounds) VRT_HIP(ctx, ctx->res.event(&ctx->ev_bounds, hipEventDisableTiming));
+    if (ctx->bounds_pending) VRT_HIP(ctx, hipEventSynchronize(ctx->ev_bounds)); // (the copy before this one still owns the buffer)
+    VRT_HIP(ctx, hipMemcpyAsync(ctx->h_cell_bounds, ctx->derived.cell_bounds, 6 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VRT_HIP(ctx, hipEventRecord(ctx->ev_bounds, ctx->stream));
+    ctx->bounds_pending = true;
+    ctx->box_is_grid = false; // until the new box is known
+    ctx->auto_next = 0;       // (another scene: the bounce kernel's auto-tune starts again)
+    ctx->auto_decided = ctx->auto_use_pool = false;
     return VRT_OK;
 }
 
@@ -243,7 +190,7 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
                     }
                 }
             }
-        } else if (frames == 1 && !marks && camera && camera->max_bounce > 1 && ctx->box_is_grid && !ctx->status_dirty && !ctx->params.wave_timeline) {
+        } else if (frames == 1 && !marks && camera && camera->max_bounce > 1 && ctx->box_is_grid && !ctx->derived.status_dirty && !ctx->params.wave_timeline) {
             // (the four trials must trace the same work: a host that changes the samples per pixel or the bounce count between them
             // starts the trials again with the new pair — ADVICE r05)
             if (ctx->auto_next != 0u && (camera->samples_per_pixel != ctx->auto_spp || camera->max_bounce != ctx->auto_bounce)) ctx->auto_next = 0u;
@@ -397,51 +344,6 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
     ctx->in_flight = true;
     ctx->frame_seq++;
     ctx->last_slot = 0;
-    return VRT_OK;
-}
-
-// where derived structure `id` lies and its logical size (0, nullptr: this context keeps none)
-static uint64_t derived_span(const vrt_ctx *ctx, vrt_derived_id id, const void **ptr) {
-    const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
-    const uint64_t b = ctx->cfg.brick_dimension;
-    const void *p = nullptr;
-    uint64_t n = 0;
-    switch (id) {
-    case VRT_DERIVED_CELL_BOUNDS: p = ctx->d_cell_bounds, n = 6u * sizeof(int); break;
-    case VRT_DERIVED_STATUS_BYTES: p = ctx->d_status_bytes, n = ((cells + 31u) / 32u) * 32u; break;
-    case VRT_DERIVED_STATUS_HALFBLOCKS: p = ctx->d_status_halfblocks, n = (cells / 32u) * 4u; break;
-    case VRT_DERIVED_CELL_OCCUPANCY: p = ctx->d_cell_occupancy, n = cells * (b * b * b / 8u); break;
-    case VRT_DERIVED_CELL_MATERIAL: p = ctx->d_cell_material, n = cells; break;
-    case VRT_DERIVED_CELL_BOX: p = ctx->d_cell_box, n = cells * 4u; break;
-    case VRT_DERIVED_START_IS_SLOT: p = ctx->d_start_is_slot, n = 4u; break;
-    case VRT_DERIVED_MATERIALS_PLAIN: p = ctx->d_materials_plain, n = 4u; break;
-    default: break;
-    }
-    if (ptr) *ptr = p;
-    return p ? n : 0u;
-}
-
-uint64_t vrt_derived_size(const vrt_ctx *ctx, vrt_derived_id id) {
-    if (!ctx || (int)id < 0 || id >= VRT_DERIVED_COUNT) return 0;
-    return derived_span(ctx, id, nullptr);
-}
-
-int vrt_read_derived(vrt_ctx *ctx, vrt_derived_id id, uint64_t byte_offset, void *dst, uint64_t nbytes) {
-    if (!ctx) return VRT_E_INVALID_ARG;
-    if ((int)id < 0 || id >= VRT_DERIVED_COUNT) return fail(ctx, VRT_E_INVALID_ARG, "bad derived-structure id");
-    if (nbytes && !dst) return fail(ctx, VRT_E_INVALID_ARG, "dst is NULL");
-    const void *src = nullptr;
-    const uint64_t size = derived_span(ctx, id, &src);
-    if (src && (byte_offset > size || nbytes > size - byte_offset)) return fail(ctx, VRT_E_OUT_OF_RANGE, "read exceeds the derived structure");
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, "the derived structures are not read back on a context of the multi-GPU pipeline");
-    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
-    if (!src) return fail(ctx, VRT_E_STATE, "this context keeps no such derived structure (no kernel it selects reads it)");
-    if (nbytes == 0) return VRT_OK;
-    DeviceGuard dg(ctx->device);
-    const int rc = refresh_derived(ctx); // (on the primary stream, behind every upload and edit so far)
-    if (rc != VRT_OK) return rc;
-    VRT_HIP(ctx, hipMemcpyAsync(dst, static_cast<const uint8_t *>(src) + byte_offset, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-    VRT_HIP(ctx, wait_stream(ctx->stream));
     return VRT_OK;
 }
 

@@ -1,266 +1,11 @@
-// vrt_trace.hip — derived-structure builders, tile schedule, root-side un-swizzle, and the launchers / kernel selection
-// called from vrt_api.hip.  The traversal kernels themselves live in vrt_trace_kernels.h and are instantiated by vrt_inst_*.hip.
+// vrt_trace.hip — tile schedule, root-side un-swizzle, and the launchers / kernel selection called from vrt_api.hip and
+// vrt_frame.hip (the builders of the derived structures: vrt_derived.hip).  The traversal kernels themselves live in vrt_trace_kernels.h and are instantiated by vrt_inst_*.hip.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <climits>
 #include "vrt_internal.h"
 #include "vrt_kernels.h"
 
 namespace vrt {
-
-// Builds the derived status structures from the uploaded brick_status words (binding 3):
-// out[0 .. nblocks)            one uint2 per 4x4x4 block of cells
-// out[nblocks ..) as u32 words  filter: bit b set iff block b has any occupied cell
-// One thread per block; the filter words are produced by a wave ballot (32 blocks per word).
-#ifdef VRT_DEV_VARIANTS // (only development variants read the words: the Blocked status modes, vrt_path_kernel<FILTER> and DIL 3)
-__global__ __launch_bounds__(256) void vrt_build_status_blocks(const uint32_t *__restrict__ status, uint2 *__restrict__ out, uint32_t dim_x,
-                                                               uint32_t dim_y, uint32_t dim_z, uint32_t nbx, uint32_t nby, uint32_t nbz) {
-    const uint32_t nblocks = nbx * nby * nbz;
-    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-    uint2 word = make_uint2(0u, 0u);
-    if (b < nblocks) {
-        const uint32_t bx = b % nbx, bz = (b / nbx) % nbz, by = b / (nbx * nbz);
-        for (uint32_t yy = 0; yy < 4u; yy++)
-            for (uint32_t zz = 0; zz < 4u; zz++)
-                for (uint32_t xx = 0; xx < 4u; xx++) {
-                    const uint32_t x = bx * 4u + xx, y = by * 4u + yy, z = bz * 4u + zz;
-                    if (x < dim_x && y < dim_y && z < dim_z) {
-                        const uint32_t gi = x + dim_x * (z + dim_z * y);
-                        const uint32_t bit = (status[gi >> 5] >> (gi & 31u)) & 1u;
-                        const uint32_t pos = xx + 4u * zz + 16u * yy;
-                        if (pos < 32u) word.x |= bit << pos;
-                        else word.y |= bit << (pos - 32u);
-                    }
-                }
-        out[b] = word;
-    }
-    const unsigned long long nonempty = __ballot((word.x | word.y) != 0u);
-    uint32_t *filter = reinterpret_cast<uint32_t *>(out + nblocks);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t base_word = (blockIdx.x * 256u + (threadIdx.x & ~63u)) >> 5; // first filter word of this wave
-    const uint32_t nwords = (nblocks + 31u) >> 5;
-    if (lane == 0 && base_word < nwords) filter[base_word] = (uint32_t)(nonempty & 0xFFFFFFFFull);
-    if (lane == 32 && base_word + 1u < nwords) filter[base_word + 1u] = (uint32_t)(nonempty >> 32);
-}
-#endif
-
-// The status bits ordered by half-blocks of 4 x 4 x 2 cells (TraceParams::status_halfblocks, grid_walk_park_halfblocks_gfx950):
-// word (x>>2) + (dim_x/4) * ((z>>2) + (dim_z/4) * (y>>1)), bit (x&3) | (z&3) << 2 | (y&1) << 4.  One thread per word.
-__global__ __launch_bounds__(256) void vrt_build_status_halfblocks(const uint32_t *__restrict__ status, uint32_t *__restrict__ out, uint32_t dim_x,
-                                                                   uint32_t dim_y, uint32_t dim_z) {
-    const uint32_t nx = dim_x >> 2, nz = dim_z >> 2, ny = dim_y >> 1;
-    const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
-    if (wi >= nx * nz * ny) return;
-    const uint32_t bx = wi % nx, bz = (wi / nx) % nz, by = wi / (nx * nz);
-    uint32_t word = 0u;
-    for (uint32_t k = 0; k < 32u; k++) {
-        const uint32_t x = bx * 4u + (k & 3u), z = bz * 4u + ((k >> 2) & 3u), y = by * 2u + (k >> 4);
-        const uint32_t gi = x + dim_x * (z + dim_z * y);
-        word |= ((status[gi >> 5] >> (gi & 31u)) & 1u) << k;
-    }
-    out[wi] = word;
-}
-
-// The L1 distance field of the occupied cells (TraceParams::cell_distance; grid_walk_park_dist_gfx950): one byte per cell, 0 where
-// the status bit is set, else min(255, Manhattan distance in cells to the nearest set bit).  The L1 distance transform separates:
-// seed 0 / 255, then along each axis in turn a forward and a backward sweep d = min(d, neighbour + 1) — exact after x, z, y (the
-// cap commutes with min and + 1).  One thread per status word for the seed; one thread per line of cells for a sweep (the line of
-// thread t along axis a: the t-th combination of the other two coordinates; consecutive threads are consecutive in the fastest
-// remaining coordinate).
-#ifdef VRT_DEV_VARIANTS // (only vrt_path_kernel<DIST>, a development variant, reads the field)
-__global__ __launch_bounds__(256) void vrt_build_distance_seed(const uint32_t *__restrict__ status, uint8_t *__restrict__ out, uint32_t words, uint32_t cells) {
-    const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
-    if (wi >= words) return;
-    const uint32_t bits = status[wi];
-    for (uint32_t k = 0; k < 32u; k++) {
-        const uint32_t gi = wi * 32u + k;
-        if (gi < cells) out[gi] = ((bits >> k) & 1u) ? 0u : 255u;
-    }
-}
-__global__ __launch_bounds__(256) void vrt_build_distance_sweep(uint8_t *__restrict__ d, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, uint32_t axis) {
-    // cell index = x + dim_x * (z + dim_z * y)
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    uint32_t n, stride, first;
-    if (axis == 0u) { // lines along x: one per (z, y)
-        if (t >= dim_z * dim_y) return;
-        n = dim_x, stride = 1u, first = t * dim_x;
-    } else if (axis == 1u) { // lines along z: one per (x, y)
-        if (t >= dim_x * dim_y) return;
-        n = dim_z, stride = dim_x, first = (t % dim_x) + dim_x * dim_z * (t / dim_x);
-    } else { // lines along y: one per (x, z)
-        if (t >= dim_x * dim_z) return;
-        n = dim_y, stride = dim_x * dim_z, first = t;
-    }
-    uint32_t run = 255u;
-    for (uint32_t i = 0; i < n; i++) {
-        uint8_t *c = d + (size_t)first + (size_t)i * stride;
-        run = min(min(run + 1u, 255u), (uint32_t)*c);
-        *c = (uint8_t)run;
-    }
-    run = 255u;
-    for (uint32_t i = n; i-- > 0u;) {
-        uint8_t *c = d + (size_t)first + (size_t)i * stride;
-        run = min(min(run + 1u, 255u), (uint32_t)*c);
-        *c = (uint8_t)run;
-    }
-}
-#endif
-
-// One byte per grid cell (TraceParams::status_bytes): 1 where the cell's status bit is set.  One thread per status word.
-__global__ __launch_bounds__(256) void vrt_build_status_bytes(const uint32_t *__restrict__ status, uint8_t *__restrict__ out, uint32_t words, uint32_t /*cells*/) {
-    const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
-    if (wi >= words) return;
-    const uint32_t bits = status[wi];
-    uint32_t *dst = reinterpret_cast<uint32_t *>(out + (size_t)wi * 32u); // (the allocation holds 32 bytes per status word)
-    for (uint32_t k = 0; k < 8u; k++) {
-        const uint32_t nib = (bits >> (4u * k)) & 0xFu;
-        const uint32_t v = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
-        dst[k] = v;
-    }
-}
-
-// The occupancy bits of every occupied cell's brick, stored by cell (TraceParams::cell_occupancy): one thread per 8-byte word of
-// the copy; words8 = B^3 / 64 words per brick.  Cells whose status bit is clear are never read by the kernels and are left alone.
-// Refresh: the cells [scan_lo, scan_hi) are looked at; a cell's words are copied if it lies in [cell_lo, cell_hi) (its status bit or
-// brick index was written) or its brick's slot in [slot_lo, slot_hi) (that brick's occupancy bytes were written).
-__global__ __launch_bounds__(256) void vrt_build_cell_occupancy(const uint32_t *__restrict__ status, const uint32_t *__restrict__ brick_index,
-                                                                const uint2 *__restrict__ occupancy, uint2 *__restrict__ out, uint64_t scan_lo, uint64_t scan_hi,
-                                                                uint32_t words8, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
-                                                                uint64_t slot_hi) {
-    const uint64_t w = scan_lo * words8 + (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint64_t cell = w / words8;
-    if (cell >= scan_hi) return;
-    if (!((status[cell >> 5] >> (cell & 31u)) & 1u)) return;
-    const uint32_t slot = brick_index[cell];
-    if (slot >= brick_alloc) return; // (malformed scene: the shader would read outside binding 5)
-    if (!((cell >= cell_lo && cell < cell_hi) || (slot >= slot_lo && slot < slot_hi))) return;
-    out[w] = occupancy[(uint64_t)slot * words8 + (w % words8)];
-}
-
-
-// TraceParams::cell_material: a wave looks at 64 consecutive cells; for every occupied one whose inputs were written — the cell itself
-// (status bit / brick index in [cell_lo, cell_hi)), its brick's slot (occupancy bytes / start index in [slot_lo, slot_hi)) or its
-// brick's material entries (bytes [mat_lo, mat_hi) of binding 7) — the lanes share the brick's voxels (B^3 / 64 each), find the first
-// solid voxel's material and whether every other solid voxel has it too.  0xFF: mixed, no solid voxel, a malformed brick, or the id 255.
-// The same pass builds TraceParams::cell_box (`box`, when not null; `out` may then be null): the box of the brick's solid voxels, from the
-// coordinates each lane's voxels have — the whole brick where there is none or the brick is malformed.  (Its inputs are a subset of the
-// material byte's, so the material's written ranges cover it; one builder, not two: the product binary keeps its kernel count.)
-template <int B>
-__global__ __launch_bounds__(256) void vrt_build_cell_material(const uint32_t *__restrict__ status, const uint32_t *__restrict__ brick_index,
-                                                               const uint8_t *__restrict__ occupancy, const uint32_t *__restrict__ start_index,
-                                                               const uint8_t *__restrict__ material_index, uint8_t *__restrict__ out,
-                                                               uint32_t *__restrict__ box, uint32_t cells,
-                                                               uint32_t status_words, uint64_t brick_alloc, uint64_t material_bytes, uint64_t cell_lo,
-                                                               uint64_t cell_hi, uint64_t slot_lo, uint64_t slot_hi, uint64_t mat_lo, uint64_t mat_hi) {
-    constexpr uint32_t kBits = B * B * B, kPerLane = kBits / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t base = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;
-    if (base >= cells) return;
-    const uint32_t w0 = (uint32_t)(base >> 5);
-    unsigned long long bits = status[w0] | (w0 + 1u < status_words ? (unsigned long long)status[w0 + 1u] << 32 : 0ull);
-    while (bits) { // (uniform over the wave)
-        const uint32_t b = (uint32_t)__builtin_ctzll(bits);
-        bits &= bits - 1ull;
-        const uint64_t cell = base + b;
-        if (cell >= cells) break;
-        const uint32_t slot = brick_index[cell];
-        if (slot >= brick_alloc) { // (malformed scene: the shader would read outside bindings 5 / 6)
-            if (box && lane == 0u && cell >= cell_lo && cell < cell_hi) box[cell] = full_cell_box(B);
-            continue;
-        }
-        const uint64_t start = start_index[slot] & 0x7FFFFFFFu; // comp:422
-        const bool written = (cell >= cell_lo && cell < cell_hi) || (slot >= slot_lo && slot < slot_hi) || (start < mat_hi && start + kBits > mat_lo);
-        if (!written) continue;
-        if (box) {
-            // per lane: a bit per coordinate value its solid voxels have (voxel v = x + B (z + B y), comp:412); OR-ed over the wave by ballots
-            uint32_t xs, ys, zs;
-            if constexpr (kPerLane == 8u) { // lane = z + 8 y, its byte holds x = 0..7
-                const uint32_t occ = occupancy[(uint64_t)slot * (kBits / 8u) + lane];
-                xs = occ, ys = occ ? 1u << (lane >> 3) : 0u, zs = occ ? 1u << (lane & 7u) : 0u;
-            } else { // lane = v
-                const bool s = ((occupancy[(uint64_t)slot * (kBits / 8u) + (lane >> 3)] >> (lane & 7u)) & 1u) != 0u;
-                xs = s ? 1u << (lane & 3u) : 0u, ys = s ? 1u << (lane >> 4) : 0u, zs = s ? 1u << ((lane >> 2) & 3u) : 0u;
-            }
-            uint32_t mx = 0u, my = 0u, mz = 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < (uint32_t)B; k++) {
-                mx |= __builtin_amdgcn_ballot_w64(((xs >> k) & 1u) != 0u) ? 1u << k : 0u;
-                my |= __builtin_amdgcn_ballot_w64(((ys >> k) & 1u) != 0u) ? 1u << k : 0u;
-                mz |= __builtin_amdgcn_ballot_w64(((zs >> k) & 1u) != 0u) ? 1u << k : 0u;
-            }
-            constexpr uint32_t n = B == 8 ? 3u : 2u;
-            auto lo = [](uint32_t m) { return (uint32_t)__builtin_ctz(m); };
-            auto hi = [](uint32_t m) { return 31u - (uint32_t)__builtin_clz(m); };
-            if (lane == 0u)
-                box[cell] = mx == 0u ? full_cell_box(B)
-                                     : (lo(mx) | lo(my) << n | lo(mz) << 2u * n | hi(mx) << 3u * n | hi(my) << 4u * n | hi(mz) << 5u * n);
-        }
-        if (!out) continue;
-        uint32_t first = 0xFFu;
-        bool solid = false, same = true;
-        if (start + kBits <= material_bytes) {
-            if constexpr (kPerLane == 8u) {
-                const uint32_t occ = occupancy[(uint64_t)slot * (kBits / 8u) + lane]; // voxels 8 lane .. 8 lane + 7 (Grid.zig:180-182)
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) {
-                    if (!((occ >> k) & 1u)) continue;
-                    const uint32_t id = material_index[start + 8u * lane + k]; // comp:425
-                    if (!solid) first = id, solid = true;
-                    else same = same && id == first;
-                }
-            } else {
-                solid = ((occupancy[(uint64_t)slot * (kBits / 8u) + (lane >> 3)] >> (lane & 7u)) & 1u) != 0u;
-                if (solid) first = material_index[start + lane];
-            }
-        }
-        const unsigned long long any = __builtin_amdgcn_ballot_w64(solid);
-        uint32_t id = 0xFFu;
-        if (any != 0ull) {
-            const uint32_t leader = (uint32_t)__builtin_ctzll(any);
-            const uint32_t m = (uint32_t)__shfl((int)first, (int)leader, 64);
-            if (__builtin_amdgcn_ballot_w64(solid && (!same || first != m)) == 0ull) id = m;
-        }
-        if (lane == 0u) out[cell] = (uint8_t)id;
-    }
-}
-
-// *flag = 1 iff every brick's start index (binding 6) is either unset (0xFFFFFFFF) or slot * bits in its low 31 bits
-// (TraceParams::start_is_slot).  The flag is set to 1 before the launch; violators clear it.
-__global__ __launch_bounds__(256) void vrt_check_start_is_slot(const uint32_t *__restrict__ start, uint32_t *__restrict__ flag, uint64_t brick_alloc,
-                                                               uint32_t bits) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= brick_alloc) return;
-    const uint32_t v = start[i];
-    if (v != 0xFFFFFFFFu && (uint64_t)(v & 0x7FFFFFFFu) != i * bits) *flag = 0u;
-}
-
-// *flag = 1 iff no material record has the type MAT_NONE (TraceParams::materials_plain).  Set to 1 before the launch; violators clear it.
-__global__ __launch_bounds__(256) void vrt_check_materials_plain(const vrt_material *__restrict__ materials, uint32_t *__restrict__ flag, uint32_t count) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < count && materials[i].type == 3u /* MAT_NONE */) *flag = 0u;
-}
-
-// Bounding box of the occupied grid cells (TraceParams::cell_bounds), from the status bits of binding 3: one thread per
-// status word, six atomic maxima over {-x, -y, -z, x, y, z}; bounds[] starts as 0x80808080 (hipMemsetAsync 0x80).
-__global__ __launch_bounds__(256) void vrt_build_cell_bounds(const uint32_t *__restrict__ status, int *__restrict__ bounds, uint32_t words,
-                                                             uint32_t cells, uint32_t dim_x, uint32_t dim_z) {
-    const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
-    if (wi >= words) return;
-    uint32_t bits = status[wi];
-    if (wi == words - 1u && (cells & 31u)) bits &= (1u << (cells & 31u)) - 1u; // bits beyond the last cell mean nothing
-    if (bits == 0u) return;
-    int m[6] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN, INT_MIN, INT_MIN};
-    while (bits) {
-        const uint32_t b = (uint32_t)__builtin_ctz(bits);
-        bits &= bits - 1u;
-        const uint32_t i = wi * 32u + b; // x + dim_x * (z + dim_z * y), comp:318
-        const int x = (int)(i % dim_x), z = (int)((i / dim_x) % dim_z), y = (int)(i / (dim_x * dim_z));
-        m[0] = max(m[0], -x), m[1] = max(m[1], -y), m[2] = max(m[2], -z);
-        m[3] = max(m[3], x), m[4] = max(m[4], y), m[5] = max(m[5], z);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) atomicMax(&bounds[k], m[k]);
-}
 
 // Cost-feedback schedule: order[] = owned tile ids in kScheduleBuckets classes of cost (wave-cycles of the most
 // recent frame, relative to the maximum), heaviest class first; INSIDE a class the tiles keep the default
@@ -750,113 +495,6 @@ hipError_t launch_schedule(const uint32_t *cost, uint32_t *snap, const uint32_t 
     VRT_LAUNCH(vrt_schedule_kernel, dim3(1), dim3(1024), 0, stream, cost, snap, prev_order, order, n, extra_max, extra < extra_max ? extra : extra_max,
                        wave_slots);
     return hipGetLastError();
-}
-
-hipError_t launch_build_status_halfblocks(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
-    if (!p.status_halfblocks) return hipSuccess;
-    const uint32_t words = (dim_x >> 2) * (dim_z >> 2) * (dim_y >> 1);
-    VRT_LAUNCH(vrt_build_status_halfblocks, dim3((words + 255u) / 256u), dim3(256), 0, stream, p.brick_status,
-                       const_cast<uint32_t *>(p.status_halfblocks), dim_x, dim_y, dim_z);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_cell_distance(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
-    if (!p.cell_distance) return hipSuccess;
-#ifndef VRT_DEV_VARIANTS
-    (void)dim_x, (void)dim_y, (void)dim_z, (void)stream;
-    return hipErrorNotSupported; // (no kernel of the product build reads the field: vrt_create never allocates it there)
-#else
-    uint8_t *d = const_cast<uint8_t *>(p.cell_distance);
-    VRT_LAUNCH(vrt_build_distance_seed, dim3((p.status_words + 255u) / 256u), dim3(256), 0, stream, p.brick_status, d, p.status_words, p.status_cells);
-    const uint32_t lines[3] = {dim_z * dim_y, dim_x * dim_y, dim_x * dim_z};
-    for (uint32_t axis = 0; axis < 3u; axis++)
-        VRT_LAUNCH(vrt_build_distance_sweep, dim3((lines[axis] + 255u) / 256u), dim3(256), 0, stream, d, dim_x, dim_y, dim_z, axis);
-    return hipGetLastError();
-#endif
-}
-
-hipError_t launch_build_cell_occupancy(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
-                                       uint64_t slot_hi, hipStream_t stream) {
-    if (!p.cell_occupancy) return hipSuccess;
-    const uint32_t words8 = brick_dimension * brick_dimension * brick_dimension / 64u;
-    const uint64_t cells = p.status_cells;
-    cell_hi = cell_hi < cells ? cell_hi : cells;
-    // written brick slots may belong to any cell: every cell is looked at (a read of its status bit and index), the named ones copied;
-    // written cells only: those cells
-    const bool any_slot = slot_lo < slot_hi;
-    const uint64_t scan_lo = any_slot ? 0u : (cell_lo < cell_hi ? cell_lo : 0u), scan_hi = any_slot ? cells : (cell_lo < cell_hi ? cell_hi : 0u);
-    if (scan_lo >= scan_hi) return hipSuccess;
-    const uint64_t words = (scan_hi - scan_lo) * words8;
-    VRT_LAUNCH(vrt_build_cell_occupancy, dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, stream, p.brick_status, p.brick_index,
-                       reinterpret_cast<const uint2 *>(p.brick_occupancy), reinterpret_cast<uint2 *>(const_cast<uint8_t *>(p.cell_occupancy)), scan_lo, scan_hi,
-                       words8, brick_alloc, cell_lo, cell_hi, slot_lo, slot_hi);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_cell_material(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, uint64_t cell_lo, uint64_t cell_hi, uint64_t slot_lo,
-                                      uint64_t slot_hi, uint64_t mat_lo, uint64_t mat_hi, hipStream_t stream) {
-    if (!p.cell_material && !p.cell_box) return hipSuccess;
-    const uint32_t cells = p.status_cells;
-    if (cells == 0u || (cell_lo >= cell_hi && slot_lo >= slot_hi && mat_lo >= mat_hi)) return hipSuccess;
-    const uint64_t bits = (uint64_t)brick_dimension * brick_dimension * brick_dimension;
-    const dim3 grid((cells + 255u) / 256u);
-    uint8_t *out = const_cast<uint8_t *>(p.cell_material);
-    if (brick_dimension == 8u)
-        VRT_LAUNCH(vrt_build_cell_material<8>, grid, dim3(256), 0, stream, p.brick_status, p.brick_index, p.brick_occupancy, p.brick_start_index, p.material_index, out,
-                           const_cast<uint32_t *>(p.cell_box), cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
-    else
-        VRT_LAUNCH(vrt_build_cell_material<4>, grid, dim3(256), 0, stream, p.brick_status, p.brick_index, p.brick_occupancy, p.brick_start_index, p.material_index, out,
-                           const_cast<uint32_t *>(p.cell_box), cells, p.status_words, brick_alloc, brick_alloc * bits, cell_lo, cell_hi, slot_lo, slot_hi, mat_lo, mat_hi);
-    return hipGetLastError();
-}
-
-hipError_t launch_check_start_is_slot(const TraceParams &p, uint32_t brick_dimension, uint64_t brick_alloc, hipStream_t stream) {
-    if (!p.start_is_slot) return hipSuccess;
-    uint32_t *flag = const_cast<uint32_t *>(p.start_is_slot);
-    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), 1, 1, stream);
-    if (e != hipSuccess) return e;
-    VRT_LAUNCH(vrt_check_start_is_slot, dim3((uint32_t)((brick_alloc + 255u) / 256u)), dim3(256), 0, stream, p.brick_start_index, flag, brick_alloc,
-                       brick_dimension * brick_dimension * brick_dimension);
-    return hipGetLastError();
-}
-
-hipError_t launch_check_materials_plain(const TraceParams &p, uint32_t count, hipStream_t stream) {
-    if (!p.materials_plain) return hipSuccess;
-    uint32_t *flag = const_cast<uint32_t *>(p.materials_plain);
-    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), 1, 1, stream);
-    if (e != hipSuccess) return e;
-    if (count) VRT_LAUNCH(vrt_check_materials_plain, dim3((count + 255u) / 256u), dim3(256), 0, stream, p.materials, flag, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_cell_bounds(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
-    if (!p.cell_bounds) return hipSuccess;
-    int *bounds = const_cast<int *>(p.cell_bounds);
-    hipError_t e = hipMemsetAsync(bounds, 0x80, 6 * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    VRT_LAUNCH(vrt_build_cell_bounds, dim3((p.status_words + 255u) / 256u), dim3(256), 0, stream, p.brick_status, bounds, p.status_words,
-                       dim_x * dim_y * dim_z, dim_x, dim_z);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_status_bytes(const TraceParams &p, hipStream_t stream) {
-    if (!p.status_bytes) return hipSuccess;
-    VRT_LAUNCH(vrt_build_status_bytes, dim3((p.status_words + 255u) / 256u), dim3(256), 0, stream, p.brick_status,
-                       const_cast<uint8_t *>(p.status_bytes), p.status_words, p.status_cells);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_status_blocks(const TraceParams &p, uint32_t dim_x, uint32_t dim_y, uint32_t dim_z, hipStream_t stream) {
-    if (!p.status_blocks) return hipSuccess;
-#ifndef VRT_DEV_VARIANTS
-    (void)dim_x, (void)dim_y, (void)dim_z, (void)stream;
-    return hipErrorNotSupported; // (no kernel of the product build reads the words: vrt_create never allocates them there)
-#else
-    const uint32_t nblocks = p.nbx * p.nby * p.nbz;
-    VRT_LAUNCH(vrt_build_status_blocks, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream, p.brick_status,
-                       const_cast<uint2 *>(p.status_blocks), dim_x, dim_y, dim_z, p.nbx, p.nby, p.nbz);
-    return hipGetLastError();
-#endif
 }
 
 hipError_t launch_assemble_rgb(const void *gathered, void *frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_count,
