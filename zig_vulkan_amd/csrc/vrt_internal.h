@@ -1,6 +1,7 @@
 // vrt_internal.h — types shared by the C-ABI implementation and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/vrt_hip.h"
 
@@ -34,6 +35,39 @@ struct TileOwnership {
     uint8_t prefix[64];   // number of earlier slots of the period held by the same rank
     uint8_t count[8];     // slots per period of each rank
 };
+
+// What the one-sample kernels read of TraceParams, gathered by the PHASE of vrt_trace_kernel that reads it: tile and schedule selection,
+// grid_hit's set-up (behind TraceParams::grid), the brick round's pointers.  TraceParams carries each block once more behind its own
+// fields (launch_trace fills them from those fields at every launch), and the one-sample kernels fetch a block by one batch of wide
+// scalar loads behind one wait (vrt_trace_kernels.h, kernarg_*): a round trip to the scalar cache costs a wave ~42 clocks whether it
+// brings one dword or sixteen (tools/ubench/smem_probe.hip), and left to itself the compiler fetches the fields one by one where
+// they are used.  The fields keep their places for every other kernel family, whose register allocation sits at the edge of its budget
+// (tests/test_kernel_resources.py) and moves with the order of the kernel-argument loads.
+struct TileArgs {
+    uint32_t tile_order, wave_groups, split_all, owned_tiles, sched_extra, own_period;
+    const uint32_t *tile_schedule;
+    unsigned long long *wave_timeline;
+    uint32_t own_count, shard_rank, shard_count, tiles_x, width, height;
+};
+struct GridExtra {
+    uint32_t scale_pow2;
+    float inv_grid_scale, inv_voxel_scale;
+    uint32_t skip_to_box;
+    const int *cell_bounds;
+    uint32_t status_cells, status_words;
+    const uint32_t *start_is_slot;
+    uint32_t occupancy_words, count_box;
+};
+struct BrickArgs {
+    const uint32_t *cell_box;
+    const uint8_t *status_bytes;
+    const vrt_material *materials;
+    const uint32_t *brick_status, *brick_index;
+    const uint8_t *brick_occupancy;
+    const uint32_t *brick_start_index;
+    const uint8_t *material_index;
+};
+static_assert(sizeof(TileArgs) == 64 && sizeof(GridExtra) == 48 && sizeof(BrickArgs) == 64, "16, 12 and 16 dwords: s_load_dwordx16, x8 + x4, x16");
 
 // Kernel argument block.  Passed by value: lives in the kernarg segment and is
 // read through the scalar cache, like the reference's UBO + push constants.
@@ -151,7 +185,12 @@ struct TraceParams {
     uint32_t tile_order;                 // workgroup -> tile mapping: 1 row bands per XCD, 2 column bands per XCD, 3 reverse raster, 4 strided,
                                          // 5 cost-feedback schedule, 6 raster.  (kernel_variant: 0 = the library chooses between 3 and the
                                          // schedule re-sorted every 32 frames, which is 7 there; 5 there re-sorts before every frame)
+    // the one-sample kernels' blocks (see TileArgs above): copies of the fields above, made by launch_trace (fill_arg_blocks)
+    alignas(16) TileArgs tile_args;
+    GridExtra grid_extra;
+    BrickArgs brick_args;
 };
+static_assert(offsetof(TraceParams, grid) == 0 && offsetof(TraceParams, tile_args) % 16 == 0, "the wide scalar loads' offsets");
 
 constexpr int kMaxBatchFrames = 8;
 constexpr int kTileW = 16;

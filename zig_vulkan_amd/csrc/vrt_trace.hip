@@ -429,8 +429,19 @@ const char *kernel_name_of(KernelFn fn) {
     return e ? e->name : "?";
 }
 
-hipError_t launch_trace(KernelFn fn, const TraceParams &p, size_t lds_bytes, hipStream_t stream, uint32_t frames) {
-    if (p.owned_tiles == 0 || frames == 0) return hipSuccess;
+// TraceParams' blocks for the one-sample kernels (vrt_internal.h, TileArgs): copies of the fields, made where every launch passes
+static void fill_arg_blocks(TraceParams &q) {
+    q.tile_args = TileArgs{q.tile_order, q.wave_groups, q.split_all, q.owned_tiles, q.sched_extra, q.own_period, q.tile_schedule, q.wave_timeline,
+                           q.own_count, q.shard_rank, q.shard_count, q.tiles_x, q.width, q.height};
+    q.grid_extra = GridExtra{q.scale_pow2, q.inv_grid_scale, q.inv_voxel_scale, q.skip_to_box, q.cell_bounds, q.status_cells, q.status_words, q.start_is_slot,
+                             q.occupancy_words, q.count_box};
+    q.brick_args = BrickArgs{q.cell_box, q.status_bytes, q.materials, q.brick_status, q.brick_index, q.brick_occupancy, q.brick_start_index, q.material_index};
+}
+
+hipError_t launch_trace(KernelFn fn, const TraceParams &params, size_t lds_bytes, hipStream_t stream, uint32_t frames) {
+    if (params.owned_tiles == 0 || frames == 0) return hipSuccess;
+    TraceParams p = params;
+    fill_arg_blocks(p);
     if (const KernelEntry *pe = kernel_entry_of(fn); pe && pe->path == 2) {
         // a pool of rays per wave (vrt_pool_kernel.h): as many workgroups as the GPU holds, or as the frame has pixels for
         if (!p.work_counter || !p.pool_paths || !p.pool_samples || frames != 1u) return hipErrorInvalidValue;
@@ -478,6 +489,7 @@ hipError_t launch_trace(KernelFn fn, const TraceParams &p, size_t lds_bytes, hip
                                                        p.block_threads != 512u && !p.split_all && !p.packed_rgb && !profiled) {
         TraceParams q = p;
         q.wave_groups = 1u;
+        fill_arg_blocks(q);
         VRT_LAUNCH(fn, dim3((q.owned_tiles + (q.tile_order == 5u ? q.sched_units : 0u)) * 4u, frames), dim3(64), lds_bytes, stream, q);
         return hipGetLastError();
     }

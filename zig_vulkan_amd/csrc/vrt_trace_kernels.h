@@ -785,9 +785,9 @@ struct RaySetup {
 };
 
 // comp:522-536 with comp:278 (slab test against the grid box)
-VRT_DI bool grid_slab(const TraceParams &p, const Ray &r, float t_min, float t_max, RaySetup &s) {
-    const f3 g_min = mk3(p.grid.min_point_base_t[0], p.grid.min_point_base_t[1], p.grid.min_point_base_t[2]);
-    const f3 g_max = mk3(p.grid.max_point_scale[0], p.grid.max_point_scale[1], p.grid.max_point_scale[2]);
+VRT_DI bool grid_slab(const vrt_grid_state &grid, const Ray &r, float t_min, float t_max, RaySetup &s) {
+    const f3 g_min = mk3(grid.min_point_base_t[0], grid.min_point_base_t[1], grid.min_point_base_t[2]);
+    const f3 g_max = mk3(grid.max_point_scale[0], grid.max_point_scale[1], grid.max_point_scale[2]);
     const f3 inv = mk3(safe_inverse(r.direction.x), safe_inverse(r.direction.y), safe_inverse(r.direction.z));
     const f3 t_lower = (g_min - r.origin) * inv;
     const f3 t_upper = (g_max - r.origin) * inv;
@@ -811,6 +811,8 @@ VRT_DI bool grid_slab(const TraceParams &p, const Ray &r, float t_min, float t_m
     s.sz = (int)sign1(r.direction.z);
     return s.grid_t_min <= s.grid_t_max;
 }
+
+VRT_DI bool grid_slab(const TraceParams &p, const Ray &r, float t_min, float t_max, RaySetup &s) { return grid_slab(p.grid, r, t_min, t_max, s); }
 
 VRT_DI f3 axis_normal(const RaySetup &s, int axis) {
     // normal_axis, comp:304-308: (step < 0) ? 1 : -1 on the crossed axis; axis 3 = slab-entry normal
@@ -983,21 +985,141 @@ VRT_DI bool brick_reject(const f3 &fposition, const f3 &inv_dir, uint32_t box) {
 // REJECT (the one-sample kernel on 8^3 bricks, vrt::reads_cell_box): `box` is the cell's TraceParams::cell_box, and lanes whose walk
 // brick_reject proves empty leave before the occupancy word is requested; a wave whose lanes all leave skips the walk and the material
 // prefetch.  The walk of every other lane is the shader's.
-template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false>
-VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min, Hit &hit,
-                              int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u) {
+// The scalar side of a brick round.  A wave walks about a dozen bricks per ray, and what a round needs that is the same for the whole
+// launch — two pointers and a device flag — it used to fetch in every round: with no scalar register to spare the compiler sank the
+// kernel-argument loads to their uses (one round trip to the scalar cache each: tools/ubench/smem_probe.hip), kept "pointer is not
+// null" as 64-bit lane masks, parked those in lanes of a vector register and read *start_is_slot by a vector load per brick entry.
+// grid_hit now fills BrickConsts once in front of its walk; a round takes the values through opaque_uniform (an empty asm: no
+// instruction, but nothing derived from them can be hoisted out of the round and kept live across the walk loops as a lane mask).
+struct BrickConsts {
+    BrickArgs a;                   // the round's pointers (cell_box nullptr: the context holds none)
+    uint32_t occupancy_words;      // TraceParams::occupancy_words
+    uint32_t start_is_slot;        // *TraceParams::start_is_slot (0: no flag, or the flag says no)
+    uint32_t scale_pow2;           // TraceParams::scale_pow2, as a scalar the round tests by s_cmp (not as a lane mask: two registers)
+    float inv_voxel_scale;         // TraceParams::inv_voxel_scale
+};
+// A wave-uniform value the optimiser may not move out of a loop (empty asm pinned to scalar registers).
+template <typename T>
+VRT_DI T opaque_uniform(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// A pointer that came out of a batch is a bare 64-bit value to the compiler, which would address it as a flat pointer (a 64-bit
+// vector address per lane, both counters waited for); these say what the kernel-argument pointers are: global memory.
+template <typename T>
+VRT_DI const __attribute__((address_space(1))) T *global_ptr(const T *ptr) {
+    return (const __attribute__((address_space(1))) T *)ptr;
+}
+// one dword through the scalar data cache (the flag words the builders of the derived structures leave behind an earlier kernel)
+VRT_DI uint32_t scalar_load_u32(const uint32_t *ptr) {
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(ptr));
+    return v;
+}
+// ---- kernel arguments in batches (the one-sample kernels, whose only argument is TraceParams: KARGS) ----------------------------
+// A block of TraceParams (vrt_internal.h: tile_args, grid + grid_extra, brick_args, the frame's camera and sun) from the kernarg
+// segment by wide scalar loads behind ONE wait, where the statement stands: the optimiser can neither sink the loads to the uses,
+// one dword and one wait each, nor fetch a value a second time.
+typedef __attribute__((ext_vector_type(8))) uint32_t u32x8;
+typedef __attribute__((ext_vector_type(16))) uint32_t u32x16;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+VRT_DI unsigned long long kernarg_address() { return (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr(); }
+VRT_DI TileArgs kernarg_tile_args() {
+    u32x16 v;
+    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(kernarg_address()), "n"(offsetof(TraceParams, tile_args)));
+    return __builtin_bit_cast(TileArgs, v);
+}
+// the camera of frame `frame` of the launch (24 dwords, for ray generation) and its sun (8 dwords: fetched behind the primary walk, where
+// the shadow ray and the shading read it — carried across the walk its eight values would only be parked and brought back)
+VRT_DI vrt_camera_device kernarg_camera(uint32_t frame) {
+    struct Parts { u32x16 a; u32x8 b; } v;
+    const unsigned long long at = kernarg_address() + offsetof(TraceParams, pcs) + (unsigned long long)frame * sizeof(PushConstants);
+    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v.a), "=&s"(v.b) : "s"(at));
+    struct Padded { vrt_camera_device cam; uint32_t pad[8]; };
+    static_assert(sizeof(Parts) == sizeof(Padded) && offsetof(Parts, b) == 64, "x16 | x8, padded to the alignment of the first");
+    return __builtin_bit_cast(Padded, v).cam;
+}
+VRT_DI vrt_sun_device kernarg_sun(uint32_t frame) {
+    u32x8 v;
+    const unsigned long long at = kernarg_address() + offsetof(TraceParams, pcs) + (unsigned long long)frame * sizeof(PushConstants) + offsetof(PushConstants, sun);
+    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(at));
+    return __builtin_bit_cast(vrt_sun_device, v);
+}
+// grid_hit's set-up operands: TraceParams::grid and the block behind it
+struct GridArgs {
+    vrt_grid_state grid;
+    uint32_t scale_pow2;
+    float inv_grid_scale, inv_voxel_scale;
+    uint32_t skip_to_box;
+    const int *cell_bounds;
+    uint32_t status_cells, status_words;
+    const uint32_t *start_is_slot;
+    uint32_t occupancy_words, count_box;
+};
+static_assert(sizeof(GridArgs) == sizeof(vrt_grid_state) + sizeof(GridExtra) && offsetof(GridArgs, cell_bounds) - 64 == offsetof(GridExtra, cell_bounds) &&
+                  offsetof(GridArgs, start_is_slot) - 64 == offsetof(GridExtra, start_is_slot) && offsetof(GridArgs, count_box) - 64 == offsetof(GridExtra, count_box),
+              "GridArgs = vrt_grid_state + GridExtra, field for field");
+VRT_DI GridArgs kernarg_grid_args() {
+    struct Parts { u32x16 grid; u32x8 a; u32x4 b; } v;
+    asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %3, %4\n\ts_load_dwordx4 %2, %3, %5\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v.grid), "=&s"(v.a), "=&s"(v.b)
+                 : "s"(kernarg_address()), "n"(offsetof(TraceParams, grid_extra)), "n"(offsetof(TraceParams, grid_extra) + 32));
+    static_assert(sizeof(Parts) == sizeof(GridArgs) + 16 && offsetof(Parts, a) == 64 && offsetof(Parts, b) == 96, "x16 | x8 | x4, padded to the alignment of the first");
+    struct Padded { GridArgs g; uint32_t pad[4]; };
+    return __builtin_bit_cast(Padded, v).g;
+}
+// the box of the occupied cells (six ints behind TraceParams::cell_bounds) and the flag word behind start_is_slot, through the scalar
+// unit behind one wait; a null pointer reads the kernarg segment instead (any readable address) and its words are not used
+struct DerivedWords {
+    int bounds[6];
+    uint32_t start_is_slot;
+};
+VRT_DI DerivedWords scalar_derived_words(const GridArgs &ga) {
+    u32x4 lo;
+    u32x2 hi;
+    uint32_t flag;
+    const unsigned long long ka = kernarg_address();
+    const unsigned long long b = ga.cell_bounds ? (unsigned long long)ga.cell_bounds : ka, f = ga.start_is_slot ? (unsigned long long)ga.start_is_slot : ka;
+    asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dwordx2 %1, %3, 0x10\n\ts_load_dword %2, %4, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(lo), "=&s"(hi), "=&s"(flag)
+                 : "s"(b), "s"(f));
+    return DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, ga.start_is_slot ? flag : 0u};
+}
+VRT_DI BrickConsts kernarg_brick_consts(const GridArgs &ga, uint32_t start_is_slot) {
+    u32x16 v;
+    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(kernarg_address()), "n"(offsetof(TraceParams, brick_args)));
+    return BrickConsts{__builtin_bit_cast(BrickArgs, v), ga.occupancy_words, start_is_slot, ga.scale_pow2, ga.inv_voxel_scale};
+}
+// steps_left with the sign tests of `step` formed HERE, by two compares the optimiser cannot merge with the ray set-up's: merged, their
+// six lane masks stay live from the set-up across both walk loops — twelve scalar registers the kernel does not have, so they were
+// parked in a vector register and read back lane by lane (two v_readlane and their wait states per mask) in every brick round.
+VRT_DI int steps_left_fresh(int step, int pos, int dim, int zero_budget) {
+    unsigned long long gt, lt;
+    asm volatile("v_cmp_lt_i32_e64 %0, 0, %1" : "=s"(gt) : "v"(step));
+    asm volatile("v_cmp_gt_i32_e64 %0, 0, %1" : "=s"(lt) : "v"(step));
+    return __builtin_amdgcn_inverse_ballot_w64(gt) ? (int)((uint32_t)(dim - 1) - (uint32_t)pos) : (__builtin_amdgcn_inverse_ballot_w64(lt) ? pos : zero_budget);
+}
+
+// CONSTS (the one-sample kernels, grid_hit<KARGS>): the round's uniform operands come from `bc`; otherwise the round reads `p` as it
+// always did — the other kernel families sit at the edge of their register budgets, and their code is left as it is.
+template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false, bool CONSTS = false>
+VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min,
+                              Hit &hit, int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u) {
+    constexpr bool kConsts = CONSTS;
+    static_assert(!(CONSTS && BY_CELL), "the by-cell copy is the bounce kernel's");
     const float brick_voxel_scale = 1.0f / (float)B; // spec const 5, Pipeline.zig:313
     const float voxel_scale = g_scale * brick_voxel_scale;
-    const f3 fposition = p.scale_pow2 ? (ray_at(r, hit.t) - brick_min) * p.inv_voxel_scale : (ray_at(r, hit.t) - brick_min) / splat3(voxel_scale);
+    const bool pow2 = kConsts ? opaque_uniform(bc.scale_pow2) != 0u : p.scale_pow2 != 0u;
+    const f3 fposition = pow2 ? (ray_at(r, hit.t) - brick_min) * (kConsts ? bc.inv_voxel_scale : p.inv_voxel_scale) : (ray_at(r, hit.t) - brick_min) / splat3(voxel_scale);
     Walk w;
     w.side_dist = initial_side_dist(mk3((float)s.sx, (float)s.sy, (float)s.sz), fposition, s.ray_delta());
     const int px = f2i_clamp(__builtin_floorf(fposition.x));
     const int py = f2i_clamp(__builtin_floorf(fposition.y));
     const int pz = f2i_clamp(__builtin_floorf(fposition.z));
     constexpr int kZeroBudget = 3 * B + 8;
-    w.rx = steps_left(s.sx, px, B, kZeroBudget);
-    w.ry = steps_left(s.sy, py, B, kZeroBudget);
-    w.rz = steps_left(s.sz, pz, B, kZeroBudget);
+    w.rx = kConsts ? steps_left_fresh(s.sx, px, B, kZeroBudget) : steps_left(s.sx, px, B, kZeroBudget);
+    w.ry = kConsts ? steps_left_fresh(s.sy, py, B, kZeroBudget) : steps_left(s.sy, py, B, kZeroBudget);
+    w.rz = kConsts ? steps_left_fresh(s.sz, pz, B, kZeroBudget) : steps_left(s.sz, pz, B, kZeroBudget);
     w.t_value = 0;
     const float local_t_max = s.grid_t_max - hit.t;
     // global bit index of the voxel in brick_occupancy: brick * B^3 + voxel index (comp:412-415)
@@ -1011,21 +1133,26 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup
         if (__builtin_amdgcn_ballot_w64(more) == 0ull) return false;
     }
 
-    const uint8_t *const occupancy = by_cell ? p.cell_occupancy : p.brick_occupancy;
+    BrickArgs plain;
+    if constexpr (!kConsts) plain.brick_occupancy = p.brick_occupancy, plain.brick_start_index = p.brick_start_index, plain.material_index = p.material_index, plain.materials = p.materials;
+    const BrickArgs &a = kConsts ? bc.a : plain;
+    const uint8_t *const occupancy = by_cell ? p.cell_occupancy : a.brick_occupancy;
     const unsigned long long occ_addr = (unsigned long long)occupancy;
     u32x4 rsrc;
     rsrc.x = (uint32_t)occ_addr;
     rsrc.y = (uint32_t)(occ_addr >> 32) | (4u << 16);
-    rsrc.z = by_cell ? p.status_cells * (uint32_t)(B * B * B / 32) : p.occupancy_words;
+    rsrc.z = by_cell ? p.status_cells * (uint32_t)(B * B * B / 32) : (kConsts ? bc.occupancy_words : p.occupancy_words);
     rsrc.w = 0x00020000u;
-    uint32_t word = reinterpret_cast<const uint32_t *>(occupancy)[more ? (bit_index >> 5) : 0u];
+    uint32_t word = global_ptr(reinterpret_cast<const uint32_t *>(occupancy))[more ? (bit_index >> 5) : 0u];
     // comp:422.  EAGER: requested before the walk, so that a solid voxel's material test starts one dependent load later
     // (scenes that stay in the caches).  Otherwise requested at the first solid voxel: on a scene larger than the caches
     // every request is a 128-byte line from HBM, and four of five brick walks of the path-trace configuration end without
     // a solid voxel (K = 3.2 bricks entered, H = 0.7 hits per ray).
     uint32_t brick_material_index = 0u;
-    const bool start_is_slot = p.start_is_slot != nullptr && __builtin_amdgcn_readfirstlane((int)*p.start_is_slot) != 0; // (TraceParams; wave-uniform)
-    if constexpr (EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (p.brick_start_index[brick_index] & 0x7FFFFFFFu);
+    bool start_is_slot; // (wave-uniform; kConsts: read once in front of the walk, BrickConsts)
+    if constexpr (kConsts) start_is_slot = opaque_uniform(bc.start_is_slot) != 0u;
+    else start_is_slot = p.start_is_slot != nullptr && __builtin_amdgcn_readfirstlane((int)*p.start_is_slot) != 0;
+    if constexpr (EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (global_ptr(a.brick_start_index)[brick_index] & 0x7FFFFFFFu);
     GridWalkRegs g;
     g.alive = __builtin_amdgcn_ballot_w64(more);
     g.out_x = 0ull;
@@ -1042,9 +1169,9 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const Ray &r, const RaySetup
         if (__builtin_amdgcn_inverse_ballot_w64(g.occ)) {
             VRT_PROF_BEGIN(tp4);
             const uint32_t voxel_index = solid_bit - base;
-            if constexpr (!EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (p.brick_start_index[brick_index] & 0x7FFFFFFFu);
-            const uint32_t mi = p.material_index[brick_material_index + voxel_index];
-            const vrt_material *m = p.materials + mi;
+            if constexpr (!EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (global_ptr(a.brick_start_index)[brick_index] & 0x7FFFFFFFu);
+            const uint32_t mi = global_ptr(a.material_index)[brick_material_index + voxel_index];
+            const auto *m = global_ptr(kConsts ? opaque_uniform(a.materials) : a.materials) + mi;
             const uint32_t mtype = m->type;
             const float mdata = m->type_data;
             const bool ignore_brick = (mtype == r.ignore_type_material) && (r.internal_reflection == mdata); // comp:427
@@ -1324,11 +1451,6 @@ VRT_DI bool skip_to_box(Walk &w, const RaySetup &s, int span_x, int span_y, int 
 #include "vrt_trace_kernels_dev.h"
 #undef VRT_DEV_SECTION
 #endif
-// A wave-uniform float the optimiser may not move out of a loop (empty asm pinned to an SGPR).
-VRT_DI float opaque_uniform(float v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
 VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0]), opaque_uniform(v[1]), opaque_uniform(v[2])); }
 // comp:271-376.  t_min = 1e-5, t_max = +inf at every call site (comp:218,247).
 // BATCH (used for frames with bounces, whose secondary rays are incoherent): a lane that reaches an
@@ -1343,28 +1465,42 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 // VOXEL (ray queries, vrt_query.hip; the hand-written walks only): on a hit, voxel[0..2] = the voxel's position in the grid's voxel
 // coordinates of the walk (y as the shader counts it, cell * B + position in the brick) — integers from the walk, not derived from hit.point
 // REJECT: brick entries first tested against the cell's box of solid voxels (brick_walk_gfx950<..., REJECT>; vrt::reads_cell_box)
-template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false>
+// KARGS (the one-sample kernels; TraceParams is the kernel's only argument): the set-up's and the brick rounds' operands come from
+// the kernarg segment in three batches — the grid block in front of the slab test, the box of the occupied cells and the
+// start_is_slot flag through the scalar unit behind it, the brick rounds' pointers in front of the walk — instead of one load
+// and one wait per dword wherever the compiler sank it.  Without KARGS the same values are plain reads of `p`.
+template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false>
 VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr) {
     static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
                   "voxel coordinates come from the hand-written walk without batching");
+    constexpr bool kHandWalk = (MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT;
+    static_assert(!KARGS || (kHandWalk && !BATCH && MODE != kStatusLinearLds), "the batched arguments serve the one-sample kernels' walks");
+    // (without KARGS every VRT_GA(x) is the plain read p.x, where it stands)
+    [[maybe_unused]] GridArgs ga;
+    if constexpr (KARGS) ga = kernarg_grid_args();
+#define VRT_GA(field) (KARGS ? ga.field : p.field)
     const float t_min = 0.00001f;
     const float t_max = __builtin_inff();
     VRT_COUNT(rays);
     VRT_PROF_BEGIN(tp3);
     RaySetup s;
     VRT_PROF_BEGIN(tp6);
-    const bool slab_hit = grid_slab(p, r, t_min, t_max, s);
+    const bool slab_hit = grid_slab(VRT_GA(grid), r, t_min, t_max, s);
     VRT_PROF_END(6, tp6);
     if (!slab_hit) return false;
 
-    const f3 g_min = mk3(p.grid.min_point_base_t[0], p.grid.min_point_base_t[1], p.grid.min_point_base_t[2]);
-    const float g_scale = p.grid.max_point_scale[3];
-    const int dx = (int)p.grid.dim_x, dy = (int)p.grid.dim_y, dz = (int)p.grid.dim_z;
+    const f3 g_min = mk3(VRT_GA(grid.min_point_base_t)[0], VRT_GA(grid.min_point_base_t)[1], VRT_GA(grid.min_point_base_t)[2]);
+    const float g_scale = VRT_GA(grid.max_point_scale)[3];
+    const int dx = (int)VRT_GA(grid.dim_x), dy = (int)VRT_GA(grid.dim_y), dz = (int)VRT_GA(grid.dim_z);
+    // (KARGS: the six words of the box and the flag word, one round trip to the scalar cache for both; otherwise the box by
+    // vector loads here and the flag in front of the walk)
+    [[maybe_unused]] DerivedWords dw{};
+    if constexpr (KARGS) dw = scalar_derived_words(ga);
 
     // (opaque: the product of a uniform is formed where it is used, from its scalar register — hoisted out of the sample loop it was the one
     // vector register the several-samples kernel spilled at seven waves per SIMD, round 6)
     float global_t_value = s.grid_t_min + 0.0001f * (SCALAR_ENTRY ? opaque_uniform(g_scale) : g_scale); // comp:287
-    const f3 fposition = p.scale_pow2 ? (ray_at(r, global_t_value) - g_min) * p.inv_grid_scale : (ray_at(r, global_t_value) - g_min) / splat3(g_scale);
+    const f3 fposition = VRT_GA(scale_pow2) ? (ray_at(r, global_t_value) - g_min) * VRT_GA(inv_grid_scale) : (ray_at(r, global_t_value) - g_min) / splat3(g_scale);
     Walk w;
     w.side_dist = initial_side_dist(mk3((float)s.sx, (float)s.sy, (float)s.sz), fposition, s.ray_delta());
     const int px = f2i_clamp(__builtin_floorf(fposition.x));
@@ -1377,10 +1513,15 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
     // walks to the grid's face like the shader, so that its counters stay the reference algorithm's — unless asked
     // (count_box, vrt_config.enable_counters = 2) to count what the product kernel itself walks and requests.
     int lox = 0, loy = 0, loz = 0, hix = dx - 1, hiy = dy - 1, hiz = dz - 1;
-    if (!COUNT || p.count_box) {
-        if (p.cell_bounds) {
-            lox = -p.cell_bounds[0], loy = -p.cell_bounds[1], loz = -p.cell_bounds[2];
-            hix = p.cell_bounds[3], hiy = p.cell_bounds[4], hiz = p.cell_bounds[5];
+    if (!COUNT || VRT_GA(count_box)) {
+        if (VRT_GA(cell_bounds)) {
+            if constexpr (KARGS) {
+                lox = -dw.bounds[0], loy = -dw.bounds[1], loz = -dw.bounds[2];
+                hix = dw.bounds[3], hiy = dw.bounds[4], hiz = dw.bounds[5];
+            } else {
+                lox = -VRT_GA(cell_bounds)[0], loy = -VRT_GA(cell_bounds)[1], loz = -VRT_GA(cell_bounds)[2];
+                hix = VRT_GA(cell_bounds)[3], hiy = VRT_GA(cell_bounds)[4], hiz = VRT_GA(cell_bounds)[5];
+            }
         }
     }
     w.rx = steps_left_box(s.sx, px, lox, hix, zero_budget);
@@ -1411,7 +1552,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
     // was entered by a step through `axis` at crossed distance skip_t, not through the slab test
     [[maybe_unused]] bool skipped = false;
     [[maybe_unused]] float skip_t = 0.0f;
-    if ((!COUNT || p.count_box) && p.cell_bounds && p.skip_to_box) {
+    if ((!COUNT || VRT_GA(count_box)) && VRT_GA(cell_bounds) && VRT_GA(skip_to_box)) {
         VRT_PROF_BEGIN(tp5);
         // (extents in unsigned arithmetic: with no cell occupied the bounds are the 0x80808080 sentinel, whose signed difference overflows;
         // `more` is false for every lane then and the skip does nothing)
@@ -1420,6 +1561,10 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         w.t_value = skip_t;
         VRT_PROF_END(5, tp5);
     }
+
+    // (the brick rounds' uniform operands, fetched once; only the hand-written walks' rounds read them)
+    [[maybe_unused]] BrickConsts bc{};
+    if constexpr (KARGS) bc = kernarg_brick_consts(ga, dw.start_is_slot);
 
     auto cell_occupied = [&]() -> bool {
         VRT_COUNT(grid_steps);
@@ -1478,16 +1623,19 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         const f3 brick_min = fma3(mk3((float)cx, (float)cy, (float)cz), splat3(g_scale), g_min);  // comp:331
         global_t_value = t_cross * g_scale + s.grid_t_min + 0.01f * g_scale;                     // comp:347 (deferred) + comp:332
         hit.t = global_t_value;
-        const uint32_t brick_index = p.brick_index[cell]; // comp:337
+        const uint32_t brick_index = global_ptr(KARGS ? bc.a.brick_index : p.brick_index)[cell]; // comp:337
         // (keyed by cell: requested beside brick_index, not behind it; a context without the array never rejects)
         [[maybe_unused]] uint32_t box = 0u;
-        if constexpr (REJECT) box = p.cell_box ? p.cell_box[cell] : vrt::full_cell_box(B);
+        if constexpr (REJECT) {
+            const uint32_t *const boxes = KARGS ? opaque_uniform(bc.a.cell_box) : p.cell_box;
+            box = boxes ? global_ptr(boxes)[cell] : vrt::full_cell_box(B);
+        }
         VRT_COUNT(bricks_entered);
         VRT_COUNT_WAVE(wave_brick_walks);
         bool found;
         if constexpr ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT) {
             [[maybe_unused]] uint32_t voxel_in_brick = 0u;
-            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT>(p, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
+            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT, KARGS>(p, bc, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
             if constexpr (VOXEL) {
                 if (found) { // voxel index x + B (z + B y) in the brick (comp:412)
                     voxel[0] = cx * B + (int)(voxel_in_brick % (uint32_t)B);
@@ -1612,19 +1760,19 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         // The shipped default: grid_walk_gfx950 runs trips until some lane stands on an occupied cell (or all
         // lanes have left); the bricks are walked here, with the state from BEFORE the lane's last step rebuilt
         // from the post-step state and the crossed-axis lane masks, and the walk is resumed.
-        const unsigned long long status_addr = (MODE == kStatusBytes) ? (unsigned long long)p.status_bytes : (unsigned long long)p.brick_status;
+        const unsigned long long status_addr = (MODE == kStatusBytes) ? (unsigned long long)(KARGS ? bc.a.status_bytes : p.status_bytes) : (unsigned long long)(KARGS ? bc.a.brick_status : p.brick_status);
         u32x4 rsrc;
         rsrc.x = (uint32_t)status_addr;
         // words: stride 4, one record per status word.  bytes: a raw buffer (stride 0), num_records = bytes = cells
         rsrc.y = (uint32_t)(status_addr >> 32) | ((MODE == kStatusBytes) ? 0u : (4u << 16));
-        rsrc.z = (MODE == kStatusBytes) ? p.status_cells : p.status_words;
+        rsrc.z = (MODE == kStatusBytes) ? VRT_GA(status_cells) : VRT_GA(status_words);
         rsrc.w = 0x00020000u;
         // LDS variant: byte-address mask of the power-of-two LDS allocation holding the bitmap (trace_lds_bytes)
-        [[maybe_unused]] const uint32_t lds_mask = (0xFFFFFFFFu >> __builtin_clz(p.status_words * 4u - 1u)) & ~3u;
+        [[maybe_unused]] const uint32_t lds_mask = (0xFFFFFFFFu >> __builtin_clz(VRT_GA(status_words) * 4u - 1u)) & ~3u;
         uint32_t word;
         if constexpr (MODE == kStatusLinearLds) word = lds_word0(more ? (grid_index >> 5) : 0u);
-        else if constexpr (MODE == kStatusBytes) word = p.status_bytes[more ? grid_index : 0u];
-        else word = p.brick_status[more ? (grid_index >> 5) : 0u];
+        else if constexpr (MODE == kStatusBytes) word = global_ptr(KARGS ? bc.a.status_bytes : p.status_bytes)[more ? grid_index : 0u];
+        else word = global_ptr(KARGS ? bc.a.brick_status : p.brick_status)[more ? (grid_index >> 5) : 0u];
         GridWalkRegs g;
         g.alive = __builtin_amdgcn_ballot_w64(more);
         g.out_x = __builtin_amdgcn_ballot_w64(skipped && axis == 0);
@@ -1664,6 +1812,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         return stop == -1;
     }
 }
+#undef VRT_GA
 
 // ---- scatter functions (comp:539-596) -------------------------------------
 VRT_DI bool scatter_lambertian(const Hit &hit, Ray &scattered) {
@@ -1705,25 +1854,34 @@ VRT_DI bool scatter_dielectric(float ir, const Ray &r_in, const Hit &hit, Ray &s
 // comp:203-265 when push_constant.max_bounce <= 1 (Camera.Config.max_bounce = 0: "only primary
 // ray", Camera.zig:74).  The bounce loop then runs at most once, so the scatter functions — whose only
 // products are the next ray and the continue flag — have no observable effect and are not evaluated.
-template <int B, bool COUNT, int MODE, bool SCALAR_ENTRY = false, bool REJECT = false>
+template <int B, bool COUNT, int MODE, bool SCALAR_ENTRY = false, bool REJECT = false, bool KARGS = false>
 VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const uint32_t *lds_filter, const Ray &ray, Cnt<COUNT> &c) {
-    const bool sun_enabled = pc.sun.enabled > 0;
-    const f3 sun_color = mk3(pc.sun.color[0], pc.sun.color[1], pc.sun.color[2]);
     f3 color = mk3(0, 0, 0);
     int loop_count = 0;
     Hit hit;
-    if (pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT>(p, lds_filter, ray, hit, c)) {
+    // (KARGS: pc.sun is not filled; the sun arrives behind the primary walk, in one batch)
+    [[maybe_unused]] vrt_sun_device sun_batch;
+    bool sun_enabled = false;
+    f3 sun_color = mk3(0, 0, 0);
+    if constexpr (!KARGS) sun_enabled = pc.sun.enabled > 0, sun_color = mk3(pc.sun.color[0], pc.sun.color[1], pc.sun.color[2]);
+    const bool primary_hit = pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, ray, hit, c);
+    if constexpr (KARGS) {
+        sun_batch = kernarg_sun(blockIdx.y);
+        sun_enabled = sun_batch.enabled > 0, sun_color = mk3(sun_batch.color[0], sun_batch.color[1], sun_batch.color[2]);
+    }
+    const vrt_sun_device &sun = KARGS ? sun_batch : pc.sun;
+    if (primary_hit) {
         // (the material record is read AFTER the shadow ray: only its index stays live across the second walk — three registers
         // fewer at the kernel's point of highest pressure; the record sits in the scalar / L1 cache)
         const uint32_t material = hit.index;
         bool lit = true;
         if (sun_enabled) {
-            const f3 sun_position = mk3(pc.sun.position[0], pc.sun.position[1], pc.sun.position[2]);
-            const f3 rv = rand_vec3_range(ray.direction.x + ray.direction.z, ray.direction.y + ray.direction.z, -pc.sun.radius,
-                                          pc.sun.radius);
+            const f3 sun_position = mk3(sun.position[0], sun.position[1], sun.position[2]);
+            const f3 rv = rand_vec3_range(ray.direction.x + ray.direction.z, ray.direction.y + ray.direction.z, -sun.radius,
+                                          sun.radius);
             const Ray shadow_ray = create_ray(hit.point, (sun_position + rv) - hit.point);
             Hit shadow_hit;
-            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT>(p, lds_filter, shadow_ray, shadow_hit, c);
+            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, shadow_ray, shadow_hit, c);
         }
         const vrt_material *m = p.materials + material;
         const uint32_t mtype = m->type;
@@ -1832,6 +1990,13 @@ VRT_DI uint32_t fresh_lane() {
 template <int B, bool COUNT, int MODE, int MIN_WAVES, int SHADE, int BLOCK = 256>
 __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const TraceParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_filter[];
+    // the one-sample product kernels take their arguments in batches, a block of TraceParams per phase behind one wait (grid_hit<KARGS>)
+    constexpr bool KARGS = SHADE == 2 && !COUNT && BLOCK == 256 && (MODE == kStatusLinearAlways || MODE == kStatusBytes);
+    // tile and schedule selection: one block, fetched here (what the store needs of it is fetched again behind the walks: plain `p`)
+    // (without KARGS every VRT_TA(x) is the plain read p.x, where it stands)
+    [[maybe_unused]] TileArgs ta;
+    if constexpr (KARGS) ta = kernarg_tile_args();
+#define VRT_TA(field) (KARGS ? ta.field : p.field)
     if constexpr (MODE == kStatusLinearLds) {
         // stage the brick-status bitmap (binding 3) in LDS: 16 bytes per lane per trip
         const uint32_t nvec = (p.status_words + 3u) >> 2;
@@ -1854,14 +2019,14 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
     // p.split_all = s (small frames, reverse raster only): 2^s workgroups per tile, each renders 8 >> s rows of every 8x8 block on
     // 64 >> s lanes per wave — a frame with fewer waves than the GPU has SIMDs lasts as long as its slowest wave, and a wave walks the
     // bricks its lanes meet one after the other: fewer lanes, a shorter chain
-    const uint32_t unit = p.wave_groups ? (blockIdx.x >> 2) : (BLOCK == 512 ? blockIdx.x * 2u + (threadIdx.x >> 8) : (blockIdx.x >> p.split_all));
+    const uint32_t unit = VRT_TA(wave_groups) ? (blockIdx.x >> 2) : (BLOCK == 512 ? blockIdx.x * 2u + (threadIdx.x >> 8) : (blockIdx.x >> VRT_TA(split_all)));
     // (SHADE 1: the wave's number in a scalar register — with fresh_lane() below nothing then keeps threadIdx.x alive)
-    const uint32_t wave = p.wave_groups ? (blockIdx.x & 3u)
+    const uint32_t wave = VRT_TA(wave_groups) ? (blockIdx.x & 3u)
                                         : ((SHADE <= 1 && !COUNT) ? ((uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 3u) : ((threadIdx.x >> 6) & 3u));
-    if (BLOCK == 512 && unit >= p.owned_tiles) return; // odd tile count: the last workgroup's second half is idle
+    if (BLOCK == 512 && unit >= VRT_TA(owned_tiles)) return; // odd tile count: the last workgroup's second half is idle
     uint32_t owned;
     uint32_t split = 0u, half = 0u; // split: this workgroup renders one half of the tile (rows 4*half .. 4*half+3 of each 8x8 block)
-    if (p.tile_order == 5u) {
+    if (VRT_TA(tile_order) == 5u) {
         // cost-feedback schedule: tiles sorted by the time they took last frame, heaviest first, so the
         // kernel's tail is made of cheap tiles (longest-processing-time-first list scheduling).  Launch
         // order also spreads consecutive tiles over XCDs (block b runs on XCD b % 8).
@@ -1870,37 +2035,42 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
         // splits the tiles whose slowest wave would otherwise outlast the rest of the frame (the lanes of such a wave
         // walk their bricks one after the other; half the lanes, fewer separate walks: 88 -> 70 us for the slowest
         // tile of view V1).  The list has p.sched_extra spare entries for the second halves; unused ones are ~0.
-        const uint32_t entry = p.tile_schedule[(unit & 7u) * ((p.owned_tiles + p.sched_extra + 7u) >> 3) + (unit >> 3)];
+        const uint32_t *const slot = VRT_TA(tile_schedule) + ((unit & 7u) * ((VRT_TA(owned_tiles) + VRT_TA(sched_extra) + 7u) >> 3) + (unit >> 3));
+        const uint32_t entry = KARGS ? scalar_load_u32(slot) : *slot; // (uniform over the workgroup: through the scalar unit either way)
         if (entry == 0xFFFFFFFFu) return; // a spare entry (uniform over the workgroup)
         owned = entry & 0x3FFFFFFFu;
         split = entry >> 31;
         half = (entry >> 30) & 1u;
-    } else if (p.tile_order == 6u) {
+    } else if (VRT_TA(tile_order) == 6u) {
         // raster order; consecutive tiles go to consecutive XCDs: every XCD samples the whole image
         // (a contiguous band per XCD measured 22-28 % slower on the headline frame: sky bands idle)
         owned = unit;
-    } else if (p.tile_order == 3u) {
+    } else if (VRT_TA(tile_order) == 3u) {
         // reverse raster, consecutive tiles on consecutive XCDs: every XCD samples the whole image, and
         // the rows that usually hold the ground (long rays) start first so that sky tiles fill the tail
-        owned = p.owned_tiles - 1u - unit;
-        split = p.split_all;
-        half = blockIdx.x & ((1u << p.split_all) - 1u);
-    } else if (p.tile_order == 4u) {
+        owned = VRT_TA(owned_tiles) - 1u - unit;
+        split = VRT_TA(split_all);
+        half = blockIdx.x & ((1u << VRT_TA(split_all)) - 1u);
+    } else if (VRT_TA(tile_order) == 4u) {
         // strided permutation: consecutive launches sample the whole image (stride coprime to the count)
-        owned = (uint32_t)(((unsigned long long)unit * p.tile_stride) % p.owned_tiles);
-    } else if (p.tile_order == 2u) {
+        owned = (uint32_t)(((unsigned long long)unit * p.tile_stride) % VRT_TA(owned_tiles));
+    } else if (VRT_TA(tile_order) == 2u) {
         // XCD k gets a band of tile columns: slice index runs column-major over the tile grid
-        const uint32_t cm = xcd_slice_index(unit, p.owned_tiles);
+        const uint32_t cm = xcd_slice_index(unit, VRT_TA(owned_tiles));
         const uint32_t col = cm / p.tiles_y, row = cm % p.tiles_y;
-        owned = row * p.tiles_x + col;
+        owned = row * VRT_TA(tiles_x) + col;
     } else {
-        owned = xcd_slice_index(unit, p.owned_tiles);
+        owned = xcd_slice_index(unit, VRT_TA(owned_tiles));
     }
-    const uint32_t tile = p.own_period ? (owned / p.own_count) * p.own_period + p.own_slots[owned % p.own_count] : owned * p.shard_count + p.shard_rank;
-    const uint32_t tile_x = tile % p.tiles_x, tile_y = tile / p.tiles_x;
+    const uint32_t tile = VRT_TA(own_period) ? (owned / VRT_TA(own_count)) * VRT_TA(own_period) + p.own_slots[owned % VRT_TA(own_count)] : owned * VRT_TA(shard_count) + VRT_TA(shard_rank);
+    const uint32_t tile_x = tile % VRT_TA(tiles_x), tile_y = tile / VRT_TA(tiles_x);
     // lane -> pixel: wave w of the tile covers the 8x8 quadrant (w&1, w>>1)
     const uint32_t lane = (SHADE <= 1 && !COUNT) ? fresh_lane() : (threadIdx.x & 63u);
-    const PushConstants &pc = p.pcs[blockIdx.y]; // frame blockIdx.y of this launch (kernarg segment, scalar loads)
+    // frame blockIdx.y of this launch (kernarg segment, scalar loads; KARGS: the camera's 24 dwords in one batch for ray generation —
+    // the sun is fetched by ray_color_single behind the primary walk)
+    PushConstants pc_batch;
+    if constexpr (KARGS) pc_batch.cam = kernarg_camera(blockIdx.y);
+    const PushConstants &pc = KARGS ? pc_batch : p.pcs[blockIdx.y];
     // A half-tile workgroup of a frame with TWO samples per pixel gives its idle lanes the second sample (round 4): lanes 0-31 trace
     // sample 0 of the wave's 32 pixels, lanes 32-63 sample 1 of the same pixels, and lane l adds lane l + 32's colour to its own —
     // (0 + s0) + s1, the sample loop's own sum (comp:173) — before the tone-map.  The slowest waves of a bounce frame (the frame lasts
@@ -1925,10 +2095,10 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
     __syncthreads();
 #endif
     VRT_PROF_BEGIN(tp7);
-    const unsigned long long t_begin = (p.tile_order == 5u) ? __builtin_readcyclecounter() : 0ull;
-    const unsigned long long wall_begin = p.wave_timeline ? wall_clock64() : 0ull;
+    const unsigned long long t_begin = (VRT_TA(tile_order) == 5u) ? __builtin_readcyclecounter() : 0ull;
+    const unsigned long long wall_begin = VRT_TA(wave_timeline) ? wall_clock64() : 0ull;
     Cnt<COUNT> c;
-    const bool inside = (px < p.width) && (py < p.height) && lane < (dual ? 2u * pixels : pixels); // comp:155-159
+    const bool inside = (px < VRT_TA(width)) && (py < VRT_TA(height)) && lane < (dual ? 2u * pixels : pixels); // comp:155-159
     uint32_t rgba = 0u; // this lane's pixel (0 outside the image), also needed after the branch by the RGB shard store
     if (inside) {
         f3 color = mk3(0, 0, 0);
@@ -1944,7 +2114,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
             const float u = (x0 + 0.0f) / (float)(pc.cam.image_width - 1u);
             const float v = (y0 + 0.0f) / (float)(pc.cam.image_height - 1u);
             const f3 ray_dir = fma3(horizontal, splat3(u), llc) + fma3(splat3(v), vertical, -origin);
-            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE, false, vrt::reads_cell_box(0, B, COUNT, MODE, SHADE)>(p, pc, lds_filter, create_ray(origin, ray_dir), c);
+            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE, false, vrt::reads_cell_box(0, B, COUNT, MODE, SHADE), KARGS>(p, pc, lds_filter, create_ray(origin, ray_dir), c);
         } else {
             const int sample_begin = dual ? (int)(lane >= pixels ? 1u : 0u) : 0, sample_end = dual ? sample_begin + 1 : spp;
             for (int sample_i = sample_begin; sample_i < sample_end; sample_i++) {
@@ -2058,5 +2228,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
         }
     }
 }
+
+#undef VRT_TA
 
 } // namespace vrt
