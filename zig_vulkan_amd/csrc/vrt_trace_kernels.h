@@ -972,6 +972,50 @@ VRT_DI bool brick_reject(const f3 &fposition, const f3 &inv_dir, uint32_t box) {
     return tf < tn;
 }
 
+// Box miss (the one-sample kernels' primary rays): true when the brick-level walk of the ray (comp:271-376) can visit no cell of the
+// box of the OCCUPIED cells — GridHit then finds nothing whatever it does, and the whole set-up (slab test, entry position, counters,
+// skip_to_box) is work the pixel does not need.  `bounds` are the device's cell_bounds words (-lo x, y, z, hi x, y, z).  A slab test of
+// the ray (t >= 0, from its ORIGIN, in world units) against the box DILATED BY ONE CELL on every side plus kBoxMissEps; empty
+// interval: miss.  brick_reject's argument one level up: the walk's three side-distance sequences are repeated additions of |1/dir|,
+// at most dim_x + dim_y + dim_z + 8 of them, and skip_to_box performs the walk's own additions; so every crossing the walk takes lies
+// within a few ulps of the exact line's crossing of the same plane, only crossings of different axes that nearly coincide can be
+// taken in the other order, and each axis's count is then off by at most one: a cell the binary32 walk visits is at L-infinity
+// distance <= 1 from a cell the exact line passes through.  The epsilon (1/64 cell) covers what lies between the exact line through
+// the origin and the one the walk starts from — the entry position ray_at(grid_t_min + 0.0001 scale), its subtraction and division,
+// and this test's own roundings (the dilated faces: a product and a sum; the differences; the products with 1/dir) — as long as every
+// coordinate involved is small: with the origin, the faces and their differences within kBoxMissReach cells in magnitude, one rounding
+// is at most 2^-13 cell, and two dozen of them stay below a fifth of the epsilon.  Beyond that reach the test says "no miss" (a camera
+// or a grid far from the world's origin, and the sentinel box of a scene with no occupied cell: faces near +-2^31 cells; its
+// negated lower bounds 0x7F7F7F80 do not overflow).
+// (inv_dir is safeInverse, the very values grid_slab forms: 1e12 for a zero component, never NaN; such a ray misses iff its origin
+// lies outside that axis's dilated range — both products then have one sign and 1e9 cells in magnitude.  A DENORMAL component's inverse
+// overflows to inf, and there the walk itself leaves the line: a start exactly on a cell boundary makes that axis's side distance
+// 0 * inf = NaN, which loses every comparison of the min-axis step, so the walk marches along that axis alone.  A ray with an infinite
+// inverse is therefore never called a miss.  A NaN product — a zero difference times a huge inverse cannot be one, only NaN operands —
+// is dropped by v_min_f32 / v_max_f32; tests/test_box_miss.py states both so.)  The transient values die here, before the walk.
+constexpr float kBoxMissEps = 1.0f / 64.0f;
+constexpr float kBoxMissReach = 2048.0f;
+VRT_DI bool box_miss(const f3 &origin, const f3 &inv_dir, const int (&bounds)[6], const f3 &g_min, float g_scale) {
+    float reach = 0.0f;
+    auto slab = [&](int k, float o, float inv, float g, float &near, float &far) {
+        const float lo = ((float)(-bounds[k]) - (1.0f + kBoxMissEps)) * g_scale + g;
+        const float hi = ((float)bounds[k + 3] + (2.0f + kBoxMissEps)) * g_scale + g; // (the far face of cell hi is hi + 1)
+        const float a0 = lo - o, a1 = hi - o;
+        const float t0 = a0 * inv, t1 = a1 * inv;
+        near = __builtin_fminf(t0, t1);
+        far = __builtin_fmaxf(t0, t1);
+        reach = __builtin_fmaxf(reach, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a0), __builtin_fabsf(a1)), __builtin_fabsf(o)));
+    };
+    float nx, fx, ny, fy, nz, fz;
+    slab(0, origin.x, inv_dir.x, g_min.x, nx, fx);
+    slab(1, origin.y, inv_dir.y, g_min.y, ny, fy);
+    slab(2, origin.z, inv_dir.z, g_min.z, nz, fz);
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), 0.0f);
+    const float tf = __builtin_fminf(__builtin_fminf(fx, fy), fz);
+    const float inv_max = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(inv_dir.x), __builtin_fabsf(inv_dir.y)), __builtin_fabsf(inv_dir.z));
+    return tf < tn && reach <= kBoxMissReach * g_scale && inv_max < __builtin_inff();
+}
+
 // comp:378-471 on the hand-written voxel loop (voxel_walk_gfx950): same operations per lane as brick_walk.
 // The loop returns when some lane has left a solid voxel behind; the material test (comp:422-427) and the hit
 // record are done here, and lanes whose voxel is to be ignored walk on.  `axis_in`: the face through which the
@@ -1024,17 +1068,60 @@ typedef __attribute__((ext_vector_type(8))) uint32_t u32x8;
 typedef __attribute__((ext_vector_type(16))) uint32_t u32x16;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 VRT_DI unsigned long long kernarg_address() { return (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr(); }
-VRT_DI TileArgs kernarg_tile_args() {
+// (with the tile block, in the same round trip: where the derived words of the scene lie — GridExtra's two pointers and the skip_to_box
+// switch — so that the words themselves can be requested with the camera, box_miss below)
+struct DerivedPtrs {
+    const int *cell_bounds;
+    const uint32_t *start_is_slot;
+    uint32_t skip_to_box;
+};
+VRT_DI TileArgs kernarg_tile_args(DerivedPtrs &dp) {
     u32x16 v;
-    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(kernarg_address()), "n"(offsetof(TraceParams, tile_args)));
+    u32x2 b, f;
+    asm volatile("s_load_dwordx16 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\ts_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v), "=&s"(b), "=&s"(f), "=&s"(dp.skip_to_box)
+                 : "s"(kernarg_address()), "n"(offsetof(TraceParams, tile_args)), "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, cell_bounds)),
+                   "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, start_is_slot)), "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, skip_to_box)));
+    dp.cell_bounds = (const int *)__builtin_bit_cast(unsigned long long, b);
+    dp.start_is_slot = (const uint32_t *)__builtin_bit_cast(unsigned long long, f);
     return __builtin_bit_cast(TileArgs, v);
 }
-// the camera of frame `frame` of the launch (24 dwords, for ray generation) and its sun (8 dwords: fetched behind the primary walk, where
-// the shadow ray and the shading read it — carried across the walk its eight values would only be parked and brought back)
-VRT_DI vrt_camera_device kernarg_camera(uint32_t frame) {
+// the camera of frame `frame` of the launch (24 dwords, for ray generation: kernarg_camera_box) and its sun (8 dwords: fetched behind the
+// primary walk, where the shadow ray and the shading read it — carried across the walk its eight values would only be parked and brought back)
+
+// the box of the occupied cells and the flag word (DerivedWords), read from the DEVICE's words — which the builders of the derived
+// structures keep current behind every upload and every edit on the GPU; a host copy could be stale — with the grid's origin and cell
+// size: what box_miss needs, and what the primary grid_hit then takes instead of fetching the words itself
+struct DerivedWords {
+    int bounds[6];
+    uint32_t start_is_slot;
+};
+struct EarlyBox {
+    DerivedWords dw;
+    float g_min[3], g_scale;
+    bool test; // the context keeps the box and skips to it (the conditions of skip_to_box)
+};
+// the camera and, behind the same wait, EarlyBox: the words' round trip is the camera's (a null pointer reads the kernarg segment
+// instead, any readable address, and its words are not used)
+VRT_DI vrt_camera_device kernarg_camera_box(uint32_t frame, const DerivedPtrs &dp, EarlyBox &eb) {
     struct Parts { u32x16 a; u32x8 b; } v;
-    const unsigned long long at = kernarg_address() + offsetof(TraceParams, pcs) + (unsigned long long)frame * sizeof(PushConstants);
-    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v.a), "=&s"(v.b) : "s"(at));
+    u32x4 lo, gm;
+    u32x2 hi;
+    uint32_t flag, sc;
+    const unsigned long long ka = kernarg_address();
+    const unsigned long long at = ka + offsetof(TraceParams, pcs) + (unsigned long long)frame * sizeof(PushConstants);
+    const unsigned long long b = dp.cell_bounds ? (unsigned long long)dp.cell_bounds : ka, f = dp.start_is_slot ? (unsigned long long)dp.start_is_slot : ka;
+    asm volatile("s_load_dwordx16 %0, %7, 0x0\n\ts_load_dwordx8 %1, %7, 0x40\n\ts_load_dwordx4 %2, %8, 0x0\n\ts_load_dwordx2 %3, %8, 0x10\n\t"
+                 "s_load_dword %4, %9, 0x0\n\ts_load_dwordx4 %5, %10, %11\n\ts_load_dword %6, %10, %12\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v.a), "=&s"(v.b), "=&s"(lo), "=&s"(hi), "=&s"(flag), "=&s"(gm), "=&s"(sc)
+                 : "s"(at), "s"(b), "s"(f), "s"(ka), "n"(offsetof(TraceParams, grid) + offsetof(vrt_grid_state, min_point_base_t)),
+                   "n"(offsetof(TraceParams, grid) + offsetof(vrt_grid_state, max_point_scale) + 12));
+    eb.dw = DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, dp.start_is_slot ? flag : 0u};
+    // (the elements as values first: a bit cast straight from `gm.y` reads element 0)
+    const uint32_t gx = gm.x, gy = gm.y, gz = gm.z;
+    eb.g_min[0] = __builtin_bit_cast(float, gx), eb.g_min[1] = __builtin_bit_cast(float, gy), eb.g_min[2] = __builtin_bit_cast(float, gz);
+    eb.g_scale = __builtin_bit_cast(float, sc);
+    eb.test = dp.cell_bounds != nullptr && dp.skip_to_box != 0u;
     struct Padded { vrt_camera_device cam; uint32_t pad[8]; };
     static_assert(sizeof(Parts) == sizeof(Padded) && offsetof(Parts, b) == 64, "x16 | x8, padded to the alignment of the first");
     return __builtin_bit_cast(Padded, v).cam;
@@ -1070,10 +1157,6 @@ VRT_DI GridArgs kernarg_grid_args() {
 }
 // the box of the occupied cells (six ints behind TraceParams::cell_bounds) and the flag word behind start_is_slot, through the scalar
 // unit behind one wait; a null pointer reads the kernarg segment instead (any readable address) and its words are not used
-struct DerivedWords {
-    int bounds[6];
-    uint32_t start_is_slot;
-};
 VRT_DI DerivedWords scalar_derived_words(const GridArgs &ga) {
     u32x4 lo;
     u32x2 hi;
@@ -1470,7 +1553,8 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 // start_is_slot flag through the scalar unit behind it, the brick rounds' pointers in front of the walk — instead of one load
 // and one wait per dword wherever the compiler sank it.  Without KARGS the same values are plain reads of `p`.
 template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false>
-VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr) {
+VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr,
+                     const DerivedWords *early = nullptr, bool sits_out = false) {
     static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
                   "voxel coordinates come from the hand-written walk without batching");
     constexpr bool kHandWalk = (MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT;
@@ -1487,15 +1571,16 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
     VRT_PROF_BEGIN(tp6);
     const bool slab_hit = grid_slab(VRT_GA(grid), r, t_min, t_max, s);
     VRT_PROF_END(6, tp6);
-    if (!slab_hit) return false;
+    // (sits_out: a lane of a primary wave whose ray box_miss proved clear of the occupied cells leaves with the lanes that miss the grid)
+    if (!slab_hit || sits_out) return false;
 
     const f3 g_min = mk3(VRT_GA(grid.min_point_base_t)[0], VRT_GA(grid.min_point_base_t)[1], VRT_GA(grid.min_point_base_t)[2]);
     const float g_scale = VRT_GA(grid.max_point_scale)[3];
     const int dx = (int)VRT_GA(grid.dim_x), dy = (int)VRT_GA(grid.dim_y), dz = (int)VRT_GA(grid.dim_z);
-    // (KARGS: the six words of the box and the flag word, one round trip to the scalar cache for both; otherwise the box by
-    // vector loads here and the flag in front of the walk)
+    // (KARGS: the six words of the box and the flag word, one round trip to the scalar cache for both — or none: the primary ray's
+    // came with the camera, `early`; otherwise the box by vector loads here and the flag in front of the walk)
     [[maybe_unused]] DerivedWords dw{};
-    if constexpr (KARGS) dw = scalar_derived_words(ga);
+    if constexpr (KARGS) dw = early ? *early : scalar_derived_words(ga);
 
     // (opaque: the product of a uniform is formed where it is used, from its scalar register — hoisted out of the sample loop it was the one
     // vector register the several-samples kernel spilled at seven waves per SIMD, round 6)
@@ -1779,6 +1864,10 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         g.out_y = __builtin_amdgcn_ballot_w64(skipped && axis == 1);
         g.t_out = skip_t;
         bool first = true; // wave-uniform
+        // (KARGS: `first && !skipped` as ONE lane mask, cleared behind the first trip — the two apart are two register pairs held
+        // across the walk, and the kernel has none to spare: tests/test_scalar_side.py)
+        [[maybe_unused]] unsigned long long by_slab = 0ull;
+        if constexpr (KARGS) by_slab = __builtin_amdgcn_ballot_w64(!skipped);
         VRT_PROF_END(3, tp3);
         while (g.alive != 0ull) {
             uint32_t cell; // the cell each lane stood on before its last step
@@ -1790,7 +1879,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
             if (g.occ == 0ull) break; // every lane has left the grid
             if (__builtin_amdgcn_inverse_ballot_w64(g.occ)) {
                 // axis 3: the first cell of the walk was entered through the slab test, not by a step
-                int a = (first && g.stub == 0u && !skipped) ? 3
+                int a = (KARGS ? (__builtin_amdgcn_inverse_ballot_w64(by_slab) && g.stub == 0u) : (first && g.stub == 0u && !skipped)) ? 3
                                                 : (__builtin_amdgcn_inverse_ballot_w64(g.in_x) ? 0 : (__builtin_amdgcn_inverse_ballot_w64(g.in_y) ? 1 : 2));
                 const bool out_x = __builtin_amdgcn_inverse_ballot_w64(g.out_x), out_y = __builtin_amdgcn_inverse_ballot_w64(g.out_y);
                 VRT_PROF_BEGIN(tp1);
@@ -1800,6 +1889,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
             // (as asm: the compiler would do this on the vector unit and could not hand the result back to an SGPR operand)
             asm("s_andn2_b64 %0, %0, %1" : "+s"(g.alive) : "s"(__builtin_amdgcn_ballot_w64(stop != 0)) : "scc");
             first = false;
+            if constexpr (KARGS) by_slab = 0ull;
         }
         finish_hit();
         return stop == -1;
@@ -1854,8 +1944,13 @@ VRT_DI bool scatter_dielectric(float ir, const Ray &r_in, const Hit &hit, Ray &s
 // comp:203-265 when push_constant.max_bounce <= 1 (Camera.Config.max_bounce = 0: "only primary
 // ray", Camera.zig:74).  The bounce loop then runs at most once, so the scatter functions — whose only
 // products are the next ray and the continue flag — have no observable effect and are not evaluated.
+// KARGS: `eb` is the box of the occupied cells as the device holds it, fetched with the camera.  A primary ray that box_miss proves
+// clear of the box runs no grid_hit — in a wave of such rays (most waves of the sky) no lane does: no grid batch, no slab test, no
+// brick constants, no skip rounds, straight to the sun and the background; in a mixed wave those lanes sit out.  Shadow rays start on
+// the terrain, inside the box: not tested.
 template <int B, bool COUNT, int MODE, bool SCALAR_ENTRY = false, bool REJECT = false, bool KARGS = false>
-VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const uint32_t *lds_filter, const Ray &ray, Cnt<COUNT> &c) {
+VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const uint32_t *lds_filter, const Ray &ray, Cnt<COUNT> &c,
+                           const EarlyBox *eb = nullptr) {
     f3 color = mk3(0, 0, 0);
     int loop_count = 0;
     Hit hit;
@@ -1864,7 +1959,18 @@ VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const 
     bool sun_enabled = false;
     f3 sun_color = mk3(0, 0, 0);
     if constexpr (!KARGS) sun_enabled = pc.sun.enabled > 0, sun_color = mk3(pc.sun.color[0], pc.sun.color[1], pc.sun.color[2]);
-    const bool primary_hit = pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, ray, hit, c);
+    bool primary_hit;
+    if constexpr (KARGS) {
+        // (1 / dir as grid_slab forms it: one set of divisions serves both)
+        const f3 inv = mk3(safe_inverse(ray.direction.x), safe_inverse(ray.direction.y), safe_inverse(ray.direction.z));
+        const bool miss = eb->test && box_miss(ray.origin, inv, eb->dw.bounds, mk3(eb->g_min[0], eb->g_min[1], eb->g_min[2]), eb->g_scale);
+        primary_hit = false;
+        if (pc.cam.max_bounce > 0 && __builtin_amdgcn_ballot_w64(!miss) != 0ull) {
+            primary_hit = grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, ray, hit, c, nullptr, &eb->dw, miss);
+        }
+    } else {
+        primary_hit = pc.cam.max_bounce > 0 && grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, ray, hit, c);
+    }
     if constexpr (KARGS) {
         sun_batch = kernarg_sun(blockIdx.y);
         sun_enabled = sun_batch.enabled > 0, sun_color = mk3(sun_batch.color[0], sun_batch.color[1], sun_batch.color[2]);
@@ -1995,7 +2101,8 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
     // tile and schedule selection: one block, fetched here (what the store needs of it is fetched again behind the walks: plain `p`)
     // (without KARGS every VRT_TA(x) is the plain read p.x, where it stands)
     [[maybe_unused]] TileArgs ta;
-    if constexpr (KARGS) ta = kernarg_tile_args();
+    [[maybe_unused]] DerivedPtrs dp;
+    if constexpr (KARGS) ta = kernarg_tile_args(dp);
 #define VRT_TA(field) (KARGS ? ta.field : p.field)
     if constexpr (MODE == kStatusLinearLds) {
         // stage the brick-status bitmap (binding 3) in LDS: 16 bytes per lane per trip
@@ -2067,9 +2174,11 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
     // lane -> pixel: wave w of the tile covers the 8x8 quadrant (w&1, w>>1)
     const uint32_t lane = (SHADE <= 1 && !COUNT) ? fresh_lane() : (threadIdx.x & 63u);
     // frame blockIdx.y of this launch (kernarg segment, scalar loads; KARGS: the camera's 24 dwords in one batch for ray generation —
-    // the sun is fetched by ray_color_single behind the primary walk)
+    // the sun is fetched by ray_color_single behind the primary walk;
+    // with the camera: the box of the occupied cells for box_miss, requested here and used behind ray generation)
     PushConstants pc_batch;
-    if constexpr (KARGS) pc_batch.cam = kernarg_camera(blockIdx.y);
+    [[maybe_unused]] EarlyBox eb;
+    if constexpr (KARGS) pc_batch.cam = kernarg_camera_box(blockIdx.y, dp, eb);
     const PushConstants &pc = KARGS ? pc_batch : p.pcs[blockIdx.y];
     // A half-tile workgroup of a frame with TWO samples per pixel gives its idle lanes the second sample (round 4): lanes 0-31 trace
     // sample 0 of the wave's 32 pixels, lanes 32-63 sample 1 of the same pixels, and lane l adds lane l + 32's colour to its own —
@@ -2114,7 +2223,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void vrt_trace_kernel(const Trace
             const float u = (x0 + 0.0f) / (float)(pc.cam.image_width - 1u);
             const float v = (y0 + 0.0f) / (float)(pc.cam.image_height - 1u);
             const f3 ray_dir = fma3(horizontal, splat3(u), llc) + fma3(splat3(v), vertical, -origin);
-            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE, false, vrt::reads_cell_box(0, B, COUNT, MODE, SHADE), KARGS>(p, pc, lds_filter, create_ray(origin, ray_dir), c);
+            color = mk3(0, 0, 0) + ray_color_single<B, COUNT, MODE, false, vrt::reads_cell_box(0, B, COUNT, MODE, SHADE), KARGS>(p, pc, lds_filter, create_ray(origin, ray_dir), c, KARGS ? &eb : nullptr);
         } else {
             const int sample_begin = dual ? (int)(lane >= pixels ? 1u : 0u) : 0, sample_end = dual ? sample_begin + 1 : spp;
             for (int sample_i = sample_begin; sample_i < sample_end; sample_i++) {
