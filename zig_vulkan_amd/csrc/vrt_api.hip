@@ -330,52 +330,9 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         VRT_CREATE_HIP(hipMemsetAsync(c->d_counters, 0, sizeof(vrt::DeviceCounters), c->stream));
     }
     const uint32_t nbx = (cfg->dim_x + 3u) / 4u, nby = (cfg->dim_y + 3u) / 4u, nbz = (cfg->dim_z + 3u) / 4u;
-    {
-        // tile schedule starts as reverse raster (bottom rows first); the feedback kernel refines it
-        const uint32_t n = sh.owned_tiles ? sh.owned_tiles : 1u;
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
-        c->wave_slots = 24u * (uint32_t)cus; // 4 SIMDs x 6 waves of the trace kernel per CU
-        // default order: frames that run one at a time take the amortised cost-feedback schedule (7) unless all their workgroups
-        // are resident at once (6 per CU: no launch order to speak of) or the frame is many times that (4K: 21 rounds of resident
-        // workgroups, the tail is a small part of it and the schedule measured +1 %); the schedule may split tiles (spare entries)
-        uint32_t order = (cfg->kernel_variant >> 16) & 0xFu;
-        c->order_auto = (order == 0u);
-        if (order == 0u) order = (n > 6u * (uint32_t)cus && n <= 64u * (uint32_t)cus) ? 7u : 3u;
-        c->tile_order = order;
-        const bool plain_tiles = (vrt::resolve_variant(cfg->kernel_variant) & 0xFFu) != vrt::kVariantLinearLds512;
-        // spare entries: one per tile (the list's layout); a sort may use min(1024, n / 8) of them — or all, with a lower bar, for
-        // frames of two samples per pixel (measured on the reference app's run, same box, V0 / V1 / V2: 0.336 / 0.340 / 0.364 ms with
-        // n / 8 and a bar of 1.25 x the frame's wave-cycles over 24 slots per CU; 0.294 / 0.306 / 0.330 with every tile eligible
-        // and 40 slots per CU — 28 / 32 / 36 / 44: 0.329 / 0.306 / 0.293 / 0.295 on V0; every tile split 0.339 / 0.345 / 0.370; a cap
-        // below what the bar asks for makes the order flip between sorts: n / 4 0.395 / 0.367 / 0.396)
-        c->sched_extra = (order == 7u && plain_tiles) ? n : 0u;
-        c->sched_cap[0] = std::min(std::min(1024u, n / 8u), c->sched_extra);
-        c->sched_cap[1] = c->sched_extra;
-        c->sched_slots[0] = c->wave_slots;
-        // (with the halves in cost classes of their own — vrt_schedule_kernel, round 4 — a lower bar pays: 28 / 40 / 52 / 64 / 96 slots
-        // per CU 0.300 / 0.260 / 0.259 / 0.259 / 0.259 ms on V0, 0.323 / 0.285 / 0.262 / 0.255 / 0.257 on V1, 0.350 / 0.312 / 0.286 / 0.284 / 0.282 on V2)
-        c->sched_slots[1] = 64u * (uint32_t)cus;
-        VRT_CREATE_HIP(c->res.device(&c->d_tile_cost, n * 32u)); // [half][tile][wave]
-        const uint32_t ns = 8u * ((n + c->sched_extra + 7u) / 8u); // an order buffer is stored XCD-major: 8 rows of ceil((n + extra) / 8)
-        c->sched_stride = ns;
-        VRT_CREATE_HIP(c->res.device(&c->d_tile_schedule, (2u * (size_t)ns + 2u * (size_t)n) * 4u)); // order A, order B, snapshot + split state
-        VRT_CREATE_HIP(hipMemsetAsync(c->d_tile_cost, 0, n * 32u, c->stream));
-        VRT_CREATE_HIP(hipMemsetAsync(c->d_tile_schedule + 2u * (size_t)ns, 0, 2u * (size_t)n * 4u, c->stream));
-        uint32_t *init = static_cast<uint32_t *>(std::malloc((size_t)ns * 4u));
-        if (!init) {
-            free_ctx(c);
-            return fail(nullptr, VRT_E_OOM, "host allocation failed");
-        }
-        std::memset(init, 0xFF, (size_t)ns * 4u); // spare entries: idle workgroups
-        for (uint32_t i = 0; i < n; i++) init[(i & 7u) * (ns / 8u) + (i >> 3)] = n - 1u - i;
-        const hipError_t e = hipMemcpy(c->d_tile_schedule, init, ns * 4u, hipMemcpyHostToDevice);
-        std::free(init);
-        VRT_CREATE_HIP(e);
-        // first launch of the schedule kernel now (code-object load, about 2 ms, stays out of the frames): with no cost
-        // measured yet it copies the initial order into the second buffer
-        if (n > 1u) VRT_CREATE_HIP(vrt::launch_schedule(c->d_tile_cost, c->d_tile_schedule + 2u * (size_t)ns, c->d_tile_schedule, c->d_tile_schedule + ns, n, c->sched_extra, c->sched_cap[0], c->sched_slots[0], c->stream));
-    }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
+    VRT_CREATE_HIP(schedule_create(c, (uint32_t)cus)); // (its first sort here: the code-object load stays out of the frames)
     for (int i = 0; i < kStagingSlots; i++) {
         VRT_CREATE_HIP(c->res.pinned(&c->staging[i], kStagingSlotBytes));
         VRT_CREATE_HIP(c->res.event(&c->staging_ev[i], hipEventDisableTiming));
@@ -524,8 +481,6 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
                                        c->kernel_grid_exit, c->product_grid_exit, c->kernel_grid_exit_path, c->product_grid_exit_path, c->bounce_auto};
         VRT_CREATE_HIP(derived_create(c, fns, 12));
     }
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
     {
         const vrt::KernelEntry *e1 = c->kernel_grid_exit ? vrt::kernel_entry_of(c->kernel_grid_exit) : nullptr;
         const vrt::KernelEntry *e2 = c->product_grid_exit ? vrt::kernel_entry_of(c->product_grid_exit) : nullptr;
@@ -604,31 +559,16 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     // (the u31 start-index check above), so it always reaches
     p.occupancy_words = (uint32_t)(c->dsize[VRT_BUF_BRICK_OCCUPANCY] / 4u);
     derived_bind(c->derived, p);
+    schedule_bind(c->sched, p);
     p.status_cells = (uint32_t)cells;
-    // (order_auto: frames that alternate between the two streams of a frames_in_flight = 2 context take reverse raster (3)
-    // instead, see do_dispatch and DESIGN.md §4)
-    p.tile_order = c->tile_order;
-    p.sched_extra = c->sched_extra;
-    p.sched_units = c->sched_cap[0];
-    if (p.tile_order == 7u) {
-        // the cost-feedback schedule, re-sorted every 32 frames instead of every frame: the kernel sees order 5
-        p.tile_order = 5u;
-        c->sched_period = (cfg->kernel_variant >> 28) ? (1u << (cfg->kernel_variant >> 28)) : 32u; // tuning knob: log2 of the period
-        VRT_CREATE_HIP(c->res.event(&c->ev_sched, hipEventDisableTiming));
-        VRT_CREATE_HIP(c->res.event(&c->ev_b_sched, hipEventDisableTiming));
-    }
-    p.tile_cost = c->d_tile_cost;
-    p.tile_schedule = c->d_tile_schedule;
     p.wave_groups = (cfg->kernel_variant >> 20) & 0x1u;
     p.wave_groups_bounce = (cfg->tuning_flags & VRT_TUNE_NO_BOUNCE_WAVE_GROUPS) ? 0u : 1u;
     {
         // small frames (configs[0], 256 tiles = one wave per SIMD, lasts as long as its slowest wave's chain): when the
         // frame's waves do not fill the SIMDs twice, every tile goes to two workgroups of 32-lane waves
-        int cus2 = 0;
-        if (hipDeviceGetAttribute(&cus2, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus2 <= 0) cus2 = 256;
-        const uint32_t waves = sh.owned_tiles * 4u, simds = 4u * (uint32_t)cus2;
+        const uint32_t waves = sh.owned_tiles * 4u, simds = 4u * (uint32_t)cus;
         // (a shard of a multi-GPU frame is a small frame as well: a rank of eight owns 1 020 tiles of the headline's 8 160)
-        const bool eligible = c->order_auto && c->tile_order == 3u && !p.wave_groups && !(cfg->tuning_flags & VRT_TUNE_NO_SMALL_FRAME_SPLIT) &&
+        const bool eligible = c->sched.order_auto && c->sched.tile_order == 3u && !p.wave_groups && !(cfg->tuning_flags & VRT_TUNE_NO_SMALL_FRAME_SPLIT) &&
                               (vrt::resolve_variant(cfg->kernel_variant) & 0xFFu) != vrt::kVariantLinearLds512;
         c->split_ok = eligible;
         c->simds = simds;
@@ -637,7 +577,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         // fixed part of a wave's chain — the status bits in LDS change nothing, tools/experiments/small_frame_ab.py)
         p.split_all = (eligible && waves <= 2u * simds) ? 1u : 0u;
 #ifdef VRT_EXP_SPLIT_ALL
-        if (c->tile_order == 3u) p.split_all = VRT_EXP_SPLIT_ALL;
+        if (c->sched.tile_order == 3u) p.split_all = VRT_EXP_SPLIT_ALL;
 #endif
     }
     p.brick_batch = (cfg->kernel_variant >> 24) & 0xFu ? ((cfg->kernel_variant >> 24) & 0xFu) * 4u : 8u; // tuning knob: units of 4 lanes

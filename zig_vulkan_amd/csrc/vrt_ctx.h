@@ -1,7 +1,8 @@
 // vrt_ctx.h — the context behind the C ABI of include/vrt_hip.h, shared by the units that implement it:
 //   vrt_api.hip      creation / destruction, the seven uploads (pinned staging ring), read-back, counters
 //   vrt_derived.hip  the structures derived from the scene buffers (vrt::Derived): their builder kernels, allocation, invalidation, refresh, read-back
-//   vrt_frame.hip    one frame: kernel choice, tile schedule, launch, timing
+//   vrt_schedule.hip the cost-feedback tile schedule (vrt::TileSchedule): its sort kernel, creation, the re-sorts of a frame, the second stream's order against them
+//   vrt_frame.hip    one frame: kernel choice, the bounce kernel's trials (vrt::BounceTrials), launch, timing
 //   vrt_dist.hip     the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip     the present / denoise pass
 //   vrt_query.hip    batched ray queries, the first-hit buffer pass and the volume queries — voxel look-ups, box counts (their kernels and host side)
@@ -30,8 +31,6 @@ uint32_t resolve_variant(uint32_t variant);
 size_t trace_lds_bytes(const TraceParams &p, uint32_t variant);
 hipError_t launch_trace(KernelFn fn, const TraceParams &p, size_t lds_bytes, hipStream_t stream, uint32_t frames = 1);
 bool is_path_kernel(KernelFn fn);
-hipError_t launch_schedule(const uint32_t *cost, uint32_t *snap, const uint32_t *prev_order, uint32_t *order, uint32_t n, uint32_t extra_max, uint32_t extra, uint32_t wave_slots,
-                           hipStream_t stream);
 hipError_t launch_assemble_rgb(const void *gathered, void *frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_count,
                                uint32_t tiles_per_rank, const TileOwnership &own, hipStream_t stream, uint32_t frames, uint32_t frame_src_stride_bytes);
 hipError_t launch_denoise(const void *img, int W, int H, int samples, float bias, float mult, float tol, int out_w, int out_h, void *out_u8,
@@ -162,6 +161,30 @@ struct Derived {
     DirtyRange cm_cell{0, ~0ull}, cm_slot, cm_mat;
     bool any_dirty() const { return status_dirty || occupancy_dirty || start_dirty || materials_dirty || cell_material_dirty; }
 };
+
+// The cost-feedback tile schedule (tile_order 5, and 7: its amortised form).  All of vrt_schedule.hip's, where its head comment explains the fields.
+struct TileSchedule {
+    uint32_t *d_tile_cost = nullptr, *d_tile_schedule = nullptr;
+    uint32_t period = 0, since = 0, cur = 0; // (order 7) frames between two sorts, frames since the last one, the order buffer frames read
+    bool order_auto = false; // kernel_variant left the tile order to the library
+    uint32_t tile_order = 0, extra = 0, stride = 0; // the context's order; spare entries, all entries of an order buffer
+    uint32_t cap[2] = {0, 0}, slots[2] = {0, 0}, mode = 0;
+    uint64_t seq = 0, b_seen = 0; // sorts so far, and how many of them the second stream has been ordered after
+    hipEvent_t ev_sched = nullptr, ev_b_sched = nullptr;
+    bool b_recorded = false;
+};
+// What the schedule says about one frame (schedule_frame): its kernel reads the schedule; the rule that serves it is not the one the current
+// order was sorted under; it takes reverse raster where it alternates between two streams; the rule
+struct ScheduleFrame { bool scheduled, changes, raster; uint32_t rule; };
+
+// The four timed frames by which a context chooses its bounce kernel (vrt_ctx::bounce_auto); the functions beside do_dispatch, vrt_frame.hip
+struct BounceTrials {
+    uint32_t next = 0;                // trial frames launched so far (0 .. 4)
+    int32_t spp = 0, bounce = 0;      // what trial 0 traced: the other three must trace the same, or the trials start again
+    bool decided = false, use_pool = false;
+    hipEvent_t ev[4][2] = {};
+    float ms[2] = {0.0f, 0.0f};       // what the trials measured: lockstep, pool (vrt_bounce_autotune_ms)
+};
 } // namespace vrt
 
 struct vrt_ctx {
@@ -185,20 +208,9 @@ struct vrt_ctx {
     float *target32f = nullptr;
     uint64_t target_pixels = 0; // pixels in the (possibly sharded, padded) target
     vrt::DeviceCounters *d_counters = nullptr;
-    uint32_t *d_tile_cost = nullptr, *d_tile_schedule = nullptr; // cost-feedback tile schedule (two order buffers + snapshot)
-    // amortised cost-feedback schedule (tile_order 7): re-sorted every sched_period frames into the other buffer
-    uint32_t sched_period = 0, sched_since = 0, sched_cur = 0;
-    bool order_auto = false; // kernel_variant left the tile order to the library
+    vrt::TileSchedule sched;   // the cost-feedback tile schedule (vrt_schedule.hip)
     uint32_t bounce_variant = 0; // kernel_variant with the occupancy choice of the bounce kernel filled in
     uint32_t single_variant = 0; // kernel_variant with the library's choice of mode for frames without bounces filled in
-    uint32_t tile_order = 0, sched_extra = 0, sched_stride = 0, wave_slots = 0;
-    // the cost schedule's two rules (index 1: frames whose split tiles trace their second sample on the idle lanes — two samples per
-    // pixel — where a split costs nothing but the second workgroup's fixed part): how many tiles an order may split, and the wave
-    // slots the "time the frame needs anyway" is computed for; sched_mode: the rule the current order was sorted under
-    uint32_t sched_cap[2] = {0, 0}, sched_slots[2] = {0, 0}, sched_mode = 0;
-    uint64_t sched_seq = 0, b_seen_sched = 0;
-    hipEvent_t ev_sched = nullptr, ev_b_sched = nullptr;
-    bool b_sched_recorded = false;
     // Output of the present / denoise pass, one image per frame slot: with two frames in flight consecutive passes run on the two frame
     // streams with nothing ordering them, so each writes its own slot's image (a slot's passes follow one another on one stream) and
     // denoised_slot names the image of the most recent pass — what vrt_read_denoised_* and vrt_device_denoised_rgba8 hand out.
@@ -271,11 +283,7 @@ struct vrt_ctx {
     // the library TIMES them — four frames on the primary stream, lockstep / pool / lockstep / pool, HIP events around each — and keeps
     // the faster (pool only if it wins by 15 %); a status upload starts the trials again.  Frames are the same bytes either way.
     vrt::KernelFn bounce_auto = nullptr;
-    uint32_t auto_next = 0;                // trial frames launched so far (0 .. 4)
-    int32_t auto_spp = 0, auto_bounce = 0; // what trial 0 traced: the other three must trace the same, or the trials start again
-    bool auto_decided = false, auto_use_pool = false;
-    hipEvent_t auto_ev[4][2] = {};
-    float auto_ms[2] = {0.0f, 0.0f};       // what the trials measured: lockstep, pool (vrt_bounce_autotune_ms)
+    vrt::BounceTrials trials;
     vrt::PersistentLane lane[2];           // what the persistent kernels need per stream: [0] the primary stream, [1] stream_b
     size_t pool_stream_dwords = 0;         // size of one lane's pool_paths (0: this context selects no vrt_pool_kernel)
     uint32_t path_lds_bytes = 0;           // LDS block filter of vrt_path_kernel (0: grid not eligible)
@@ -370,6 +378,17 @@ void mark_dirty(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, uint64_t n
 // the grid-scale reciprocals of TraceParams and every structure derived from the scene buffers, brought up to date with the uploads so far
 // (stream-ordered on the primary stream): the part of pre_dispatch that frames, queries and edits share
 int refresh_derived(vrt_ctx *ctx);
+
+// ---- vrt_schedule.hip ---- (the hooks of a frame return what their HIP calls returned)
+hipError_t schedule_create(vrt_ctx *c, uint32_t cus);                // vrt_create: order, buffers, initial order and first sort, on the primary stream ...
+void schedule_bind(const vrt::TileSchedule &s, vrt::TraceParams &p); // ... and named to the kernels
+bool schedule_two_streams(const vrt_ctx *ctx);                       // frames may alternate between the streams (not while every frame re-sorts in place)
+vrt::ScheduleFrame schedule_frame(const vrt_ctx *ctx, const vrt_camera_device *camera, bool scheduled);
+hipError_t schedule_before_b(vrt_ctx *ctx), schedule_after_b(vrt_ctx *ctx); // around a frame on the second stream: its order against the sorts; counts the frame
+hipError_t schedule_sort_in_place(vrt_ctx *ctx, const vrt::ScheduleFrame &f); // order 5: before every frame
+hipError_t schedule_change_rule(vrt_ctx *ctx, const vrt::ScheduleFrame &f);   // f.changes: the next frame sorts under f.rule
+hipError_t schedule_before_frame(vrt_ctx *ctx, const vrt::ScheduleFrame &f);  // each frame of the primary stream: the amortised sort when due; counts the frame
+uint32_t schedule_groups(const vrt_ctx *ctx, bool any_rule); // tiles + spare workgroups: the most any rule launches, or what the last launch held
 
 // ---- vrt_frame.hip ----
 void note_kernel(vrt_ctx *c, vrt::KernelFn fn); // remember which kernel rendered the most recent frame (vrt_kernel_name reports what ran)

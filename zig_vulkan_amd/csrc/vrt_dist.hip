@@ -455,7 +455,7 @@ int dist_flush(vrt_ctx *ctx) {
     // 1. this rank's tiles of the n frames, packed tile-major, frame after frame, straight into the buffer RCCL sends
     //    (rank 0: into region 0 of `gathered`)
     vrt::TraceParams pk = ctx->params;
-    if (ctx->order_auto) pk.tile_order = 3u; // (no cost feedback across the slots of the pipeline yet)
+    if (ctx->sched.order_auto) pk.tile_order = 3u; // (no cost feedback across the slots of the pipeline yet)
     pk.target_rgba8 = sl.shard;
     pk.target_rgba32f = nullptr;
     pk.packed_tiles = 1u;

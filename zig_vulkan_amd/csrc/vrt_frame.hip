@@ -1,5 +1,5 @@
-// vrt_frame.hip — one frame behind the C ABI: the choice of the traversal kernel (behind refresh_derived, vrt_derived.hip), the
-// cost-feedback tile schedule, the launch on one of the context's streams, its timing.
+// vrt_frame.hip — one frame behind the C ABI: the choice of the traversal kernel (behind refresh_derived, vrt_derived.hip), the trials
+// of the bounce kernel's auto-tune, the launch on one of the context's streams (its tile schedule: vrt_schedule.hip), its timing.
 // Replaces ComputePipeline.dispatch (src/modules/voxel_rt/ComputePipeline.zig:417-463).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -87,6 +87,72 @@ static vrt::KernelFn grid_exit_choice(vrt_ctx *ctx, vrt::KernelFn exit_fn, vrt::
     return exit_path ? exit_path : keep;
 }
 
+// ---- the trials of the bounce kernel's auto-tune (vrt::BounceTrials, vrt_ctx::bounce_auto): no other code touches the struct ----
+
+static void trials_restart(vrt_ctx *ctx) { ctx->trials.next = 0, ctx->trials.decided = ctx->trials.use_pool = false; }
+// (this context's frames do not fit the pool kernel: decided without a contest — the trial under way is an ordinary frame, trials_confirm)
+static void trials_no_contest(vrt_ctx *ctx) { ctx->trials.decided = true, ctx->trials.use_pool = false; }
+static int trials_confirm(const vrt_ctx *ctx, int trial) { return ctx->trials.decided ? -1 : trial; }
+// Whether the pool kernel takes a bounce frame: trial `trial` of the four (lockstep / pool / lockstep / pool), or (-1) a frame outside
+// the trials, which follows the verdict.  trials_upcoming: what the next plain dispatch would be.
+static bool trials_pool_frame(const vrt_ctx *ctx, const vrt_camera_device *camera, int trial) {
+    return camera->max_bounce > 1 && ctx->bounce_auto && !ctx->dist && (trial >= 0 ? (trial & 1) != 0 : ctx->trials.decided && ctx->trials.use_pool);
+}
+[[maybe_unused]] static int trials_upcoming(const vrt_ctx *ctx) { return ctx->trials.decided ? -1 : (int)ctx->trials.next; }
+
+// All four trials are out: read their events once they have completed, and decide
+static void trials_read_verdict(vrt_ctx *ctx) {
+    vrt::BounceTrials &t = ctx->trials;
+    bool done = true;
+    for (int k = 0; k < 4 && done; k++) done = hipEventQuery(t.ev[k][1]) == hipSuccess;
+    if (!done) return;
+    float ms[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4 && done; k++) done = hipEventElapsedTime(&ms[k], t.ev[k][0], t.ev[k][1]) == hipSuccess;
+    t.ms[0] = std::min(ms[0], ms[2]), t.ms[1] = std::min(ms[1], ms[3]);
+    t.use_pool = done && t.ms[1] < 0.85f * t.ms[0];
+    t.decided = true;
+    if (t.use_pool || vrt::is_path_kernel(ctx->kernel)) return;
+    // the lockstep kernel stays: the sample buffers the pool trials made serve no frame of this context
+    for (vrt::PersistentLane &lane : ctx->lane) {
+        if (!lane.samples) continue;
+        ctx->res.drop(lane.samples); // (the trials' events have completed: nothing in flight reads it)
+        lane.samples = nullptr;
+        lane.sample_elems = 0;
+    }
+}
+
+// Head of a dispatch: which trial it is (0 .. 3), or -1.  plain: one frame, not timed by the caller.
+static int trials_turn(vrt_ctx *ctx, const vrt_camera_device *camera, bool plain) {
+    vrt::BounceTrials &t = ctx->trials;
+    if (!ctx->bounce_auto || t.decided) return -1;
+    if (t.next == 4u) {
+        trials_read_verdict(ctx);
+        return -1;
+    }
+    if (!(plain && camera && camera->max_bounce > 1 && ctx->box_is_grid && !ctx->derived.status_dirty && !ctx->params.wave_timeline)) return -1;
+    // (the four trials must trace the same work: a host that changes the samples per pixel or the bounce count between them
+    // starts the trials again with the new pair — ADVICE r05)
+    if (t.next != 0u && (camera->samples_per_pixel != t.spp || camera->max_bounce != t.bounce)) t.next = 0u;
+    if (t.next == 0u) t.spp = camera->samples_per_pixel, t.bounce = camera->max_bounce;
+    return (int)t.next;
+}
+static void trials_info(const vrt_ctx *ctx, double out[4]) { // vrt_bounce_autotune_info: state (0 off, 1 trials, 2 lockstep, 3 pool), trials out, ms
+    const vrt::BounceTrials &t = ctx->trials;
+    out[0] = !ctx->bounce_auto || ctx->dist ? 0.0 : (!t.decided ? 1.0 : (t.use_pool ? 3.0 : 2.0));
+    out[1] = (double)t.next, out[2] = (double)t.ms[0], out[3] = (double)t.ms[1];
+}
+
+// The events around trial `trial` (-1: nothing) on the primary stream; end: the trial is out
+static hipError_t trials_mark(vrt_ctx *ctx, int trial, int end) {
+    if (trial < 0) return hipSuccess;
+    vrt::BounceTrials &t = ctx->trials;
+    for (int e = 0; e < 2 && !end; e++)
+        if (hipError_t err = t.ev[trial][e] ? hipSuccess : ctx->res.event(&t.ev[trial][e]); err != hipSuccess) return err;
+    const hipError_t err = hipEventRecord(t.ev[trial][end], ctx->stream);
+    if (end && err == hipSuccess) t.next = (uint32_t)trial + 1u;
+    return err;
+}
+
 // Behind every rebuild of the box of the occupied cells (refresh_derived, inside its scene write): contexts whose bounce kernel depends
 // on the box copy it to the host — pinned, behind an event, never waited for; pre_dispatch looks at it once it has arrived.
 int read_back_cell_bounds(vrt_ctx *ctx) {
@@ -98,8 +164,7 @@ int read_back_cell_bounds(vrt_ctx *ctx) {
     VRT_HIP(ctx, hipEventRecord(ctx->ev_bounds, ctx->stream));
     ctx->bounds_pending = true;
     ctx->box_is_grid = false; // until the new box is known
-    ctx->auto_next = 0;       // (another scene: the bounce kernel's auto-tune starts again)
-    ctx->auto_decided = ctx->auto_use_pool = false;
+    trials_restart(ctx); // (another scene: the bounce kernel's auto-tune starts again)
     return VRT_OK;
 }
 
@@ -135,10 +200,10 @@ int pre_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_de
     if (camera->max_bounce > 1 && ctx->box_is_grid && !ctx->d_counters && ctx->kernel_grid_exit)
         *fn = grid_exit_choice(ctx, ctx->kernel_grid_exit, ctx->kernel_grid_exit_path, *fn, camera, lane, lane_stream);
     // the auto-tuned bounce kernel (bounce_auto): the pool kernel on its trial frames and once the trials have said so
-    if (camera->max_bounce > 1 && ctx->box_is_grid && ctx->bounce_auto && !ctx->dist && ((trial >= 0 && (trial & 1)) || (trial < 0 && ctx->auto_decided && ctx->auto_use_pool))) {
+    if (ctx->box_is_grid && trials_pool_frame(ctx, camera, trial)) {
         const vrt::KernelFn pool = grid_exit_choice(ctx, ctx->bounce_auto, nullptr, nullptr, camera, lane, lane_stream);
         if (pool) *fn = pool;
-        else if (trial >= 0) ctx->auto_decided = true, ctx->auto_use_pool = false; // (this context's frames do not fit the pool kernel: no contest)
+        else if (trial >= 0) trials_no_contest(ctx);
     }
     // With counters enabled the counting build of the kernel (compiler-generated loops, per-lane counters) runs
     // first and fills the counters; the frame that is read back is then rendered by the product kernel itself,
@@ -166,59 +231,23 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
     if (frames == 0) return ctx ? fail(ctx, VRT_E_INVALID_ARG, "zero frames") : VRT_E_INVALID_ARG;
     if (ctx && ctx->dist) return fail(ctx, VRT_E_STATE, "this context runs the multi-GPU pipeline: use vrt_dist_frame");
     DeviceGuard dg(ctx ? ctx->device : 0);
+    // the bounce kernel's auto-tune (vrt_ctx::bounce_auto): is this frame a trial?
+    int trial = ctx ? trials_turn(ctx, camera, frames == 1 && !marks) : -1;
+    if (trial >= 0) primary_only = true; // (a trial runs alone on the primary stream: its time is the kernel's, not the overlap's)
     // (the stream a frame of the persistent kernels would run on — they never wait for a re-sort of the tile schedule — and with it
     // the lane whose buffers the frame uses)
-    // the bounce kernel's auto-tune (vrt_ctx::bounce_auto): read the trials' events once all four have been launched; is this frame a trial?
-    int trial = -1;
-    if (ctx && ctx->bounce_auto && !ctx->auto_decided) {
-        if (ctx->auto_next == 4u) {
-            bool done = true;
-            for (int k = 0; k < 4 && done; k++) done = hipEventQuery(ctx->auto_ev[k][1]) == hipSuccess;
-            if (done) {
-                float ms[4] = {0, 0, 0, 0};
-                for (int k = 0; k < 4 && done; k++) done = hipEventElapsedTime(&ms[k], ctx->auto_ev[k][0], ctx->auto_ev[k][1]) == hipSuccess;
-                ctx->auto_ms[0] = std::min(ms[0], ms[2]), ctx->auto_ms[1] = std::min(ms[1], ms[3]);
-                ctx->auto_use_pool = done && ctx->auto_ms[1] < 0.85f * ctx->auto_ms[0];
-                ctx->auto_decided = true;
-                if (!ctx->auto_use_pool && !vrt::is_path_kernel(ctx->kernel)) {
-                    // the lockstep kernel stays: the sample buffers the pool trials made serve no frame of this context
-                    for (int l = 0; l < 2; l++) {
-                        if (!ctx->lane[l].samples) continue;
-                        ctx->res.drop(ctx->lane[l].samples); // (the trials' events have completed: nothing in flight reads it)
-                        ctx->lane[l].samples = nullptr;
-                        ctx->lane[l].sample_elems = 0;
-                    }
-                }
-            }
-        } else if (frames == 1 && !marks && camera && camera->max_bounce > 1 && ctx->box_is_grid && !ctx->derived.status_dirty && !ctx->params.wave_timeline) {
-            // (the four trials must trace the same work: a host that changes the samples per pixel or the bounce count between them
-            // starts the trials again with the new pair — ADVICE r05)
-            if (ctx->auto_next != 0u && (camera->samples_per_pixel != ctx->auto_spp || camera->max_bounce != ctx->auto_bounce)) ctx->auto_next = 0u;
-            if (ctx->auto_next == 0u) ctx->auto_spp = camera->samples_per_pixel, ctx->auto_bounce = camera->max_bounce;
-            trial = (int)ctx->auto_next;
-            primary_only = true; // (a trial runs alone on the primary stream: its time is the kernel's, not the overlap's)
-        }
-    }
-    const bool b_turn = ctx && ctx->stream_b && frames == 1 && !primary_only && (ctx->frame_seq & 1u) && (ctx->params.tile_order != 5u || ctx->sched_period);
+    const bool b_turn = ctx && ctx->stream_b && frames == 1 && !primary_only && (ctx->frame_seq & 1u) && schedule_two_streams(ctx);
     vrt::PersistentLane *lane = ctx ? &ctx->lane[b_turn ? 1 : 0] : nullptr;
     vrt::KernelFn fn = nullptr, product_fn = nullptr;
     bool with_samples = false;
     const int rcp = pre_dispatch(ctx, camera, sun, lane, ctx ? (b_turn ? ctx->stream_b : ctx->stream) : nullptr, &fn, &product_fn, &with_samples, trial);
     if (rcp != VRT_OK) return rcp;
-    if (trial >= 0 && ctx->auto_decided) trial = -1; // (the pool kernel cannot take this context's frames: decided without a contest)
+    trial = trials_confirm(ctx, trial);
     lane_into_params(ctx->lane[0], with_samples && !b_turn, ctx->params);
     note_kernel(ctx, product_fn ? product_fn : fn);
     // (the persistent-lane kernel takes its pixels from a counter: it neither reads the tile schedule nor reports tile costs)
-    const bool scheduled = !vrt::is_path_kernel(product_fn ? product_fn : fn);
-
-    // (tile_order 5 re-sorts the tile schedule in place before every frame on the primary stream: a frame running on
-    // the second stream would read it while it is being rewritten, so that order runs one frame at a time.  The
-    // amortised form, tile_order 7, sorts into the other of two buffers and may use both streams.)
-    // which of the cost schedule's two rules serves this frame (vrt_trace_kernel's `dual`: two samples per pixel, whole RGBA pixels); a
-    // change re-sorts at once, on the primary stream
-    const uint32_t sched_mode = (ctx->sched_period && scheduled && camera->samples_per_pixel == 2 && !ctx->params.packed_rgb) ? 1u : 0u;
-    const bool sched_changes = ctx->sched_period && scheduled && sched_mode != ctx->sched_mode;
-    const bool slot_b = b_turn && !sched_changes;
+    const vrt::ScheduleFrame sf = schedule_frame(ctx, camera, !vrt::is_path_kernel(product_fn ? product_fn : fn));
+    const bool slot_b = b_turn && !sf.changes; // (a change of the schedule's rule re-sorts at once, on the primary stream)
     if (slot_b) {
         // second frame slot: its own stream and target; ordered after every scene write so far
         if (ctx->post_pending[1]) { // (... and after the present pass that still reads this slot's target, round 6)
@@ -229,28 +258,16 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
             VRT_HIP(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->ev_upload, 0));
             ctx->b_seen_upload = ctx->upload_seq;
         }
-        if (ctx->b_seen_sched != ctx->sched_seq) {
-            // the schedule buffer this frame reads was sorted on the primary stream
-            VRT_HIP(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->ev_sched, 0));
-        }
+        VRT_HIP(ctx, schedule_before_b(ctx));
         vrt::TraceParams pb = ctx->params;
-        // (frames of two samples per pixel keep the cost schedule on both streams: their split tiles trace the second sample on the idle
-        // lanes, which is worth more than reverse raster's neighbourhood — the app's run, two frames in flight, V0 / V1 / V2: 0.205 /
-        // 0.214 / 0.237 ms per frame against 0.267 / 0.262 / 0.286, tools/experiments/fif_order_ab.py)
-        if (ctx->order_auto && sched_mode == 0u) pb.tile_order = 3u;
+        if (sf.raster) pb.tile_order = 3u;
         pb.target_rgba8 = ctx->target8_b;
         pb.target_rgba32f = ctx->target32f_b;
         lane_into_params(ctx->lane[1], with_samples, pb); // its frames run beside the primary stream's
         VRT_HIP(ctx, vrt::launch_trace(fn, pb, ctx->lds_bytes, ctx->stream_b));
         if (product_fn) VRT_HIP(ctx, vrt::launch_trace(product_fn, pb, ctx->lds_bytes, ctx->stream_b));
         VRT_HIP(ctx, hipEventRecord(ctx->ev_b_done, ctx->stream_b));
-        if (ctx->b_seen_sched != ctx->sched_seq) {
-            // everything this stream read from the OTHER schedule buffer is finished once this event is
-            VRT_HIP(ctx, hipEventRecord(ctx->ev_b_sched, ctx->stream_b));
-            ctx->b_sched_recorded = true;
-            ctx->b_seen_sched = ctx->sched_seq;
-        }
-        ctx->sched_since++;
+        VRT_HIP(ctx, schedule_after_b(ctx));
         ctx->b_pending = true;
         ctx->frame_seq++;
         ctx->last_slot = 1;
@@ -266,13 +283,8 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
         ctx->post_pending[0] = false;
     }
     VRT_HIP(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    const uint32_t nt = ctx->shard.owned_tiles;
-    const uint32_t ns = ctx->sched_stride; // stride of a schedule buffer
-    if (ctx->params.tile_order == 5u && nt > 1u && !ctx->sched_period && scheduled) {
-        // re-sort the tile list by last frame's measured cost (inside the timed region: it is per-frame work)
-        VRT_HIP(ctx, vrt::launch_schedule(ctx->d_tile_cost, ctx->d_tile_schedule + 2u * (size_t)ns, ctx->d_tile_schedule, ctx->d_tile_schedule, nt, ctx->sched_extra, 0u, ctx->wave_slots, ctx->stream));
-    }
-    if (ctx->order_auto && ctx->stream_b && frames == 1 && !primary_only && sched_mode == 0u && !sched_changes) {
+    VRT_HIP(ctx, schedule_sort_in_place(ctx, sf));
+    if (sf.raster && ctx->stream_b && frames == 1 && !primary_only) {
         // the even frames of two frames in flight: the other stream fills this frame's tail, and reverse raster keeps
         // neighbouring tiles together (measured 4 % faster than the cost order in that mode)
         vrt::TraceParams pa = ctx->params;
@@ -296,49 +308,15 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
         if (ctx->target32f) VRT_HIP(ctx, hipMemsetAsync(ctx->target32f, 0xCD, ctx->target_pixels * 16u, ctx->stream));
         fn = product_fn;
     }
-    if (sched_changes) {
-        // The re-sort below writes the schedule buffer no frame is SUPPOSED to read any more — ev_b_sched covers the second stream's
-        // reads of it only from the first stream-b frame behind the previous sort on.  A change of rule may follow a sort at once
-        // (samples per pixel 2 -> 1 -> 2 on consecutive frames): then a frame still running on the second stream may read the very
-        // buffer this sort rewrites.  Let the primary stream wait for the second stream's last frame.
-        if (ctx->stream_b && ctx->b_pending) {
-            VRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_b_done, 0));
-            ctx->b_pending = false;
-        }
-        ctx->sched_mode = sched_mode;
-        ctx->params.sched_units = ctx->sched_cap[sched_mode];
-        ctx->sched_since = ctx->sched_period;
-    }
-    if (trial >= 0) {
-        for (int e = 0; e < 2; e++)
-            if (!ctx->auto_ev[trial][e]) VRT_HIP(ctx, ctx->res.event(&ctx->auto_ev[trial][e]));
-        VRT_HIP(ctx, hipEventRecord(ctx->auto_ev[trial][0], ctx->stream));
-    }
+    VRT_HIP(ctx, schedule_change_rule(ctx, sf));
+    VRT_HIP(ctx, trials_mark(ctx, trial, 0));
     for (uint32_t f = 0; f < frames; f++) {
         if (marks) VRT_HIP(ctx, hipEventRecord(marks[f], ctx->stream)); // per-frame timing (vrt_dispatch_timed)
-        if (ctx->sched_period && nt > 1u && ctx->sched_since >= ctx->sched_period && scheduled) {
-            // Amortised re-sort, in the frames' own stream (inside the timed region as well): the measured costs (running mean)
-            // order the tiles into the buffer no frame reads; frames launched from here on read that one.  A sort costs about
-            // 35 us of the stream's time (the kernel plus the two kernel boundaries).  Measured alternatives: on a second
-            // stream with event waits 80 us per sort; on a second stream with the host polling for its completion nothing, but
-            // then the order lags behind frames that are queued ahead (vrt_dispatch_repeat) by a whole call.
-            if (ctx->b_sched_recorded) VRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_b_sched, 0)); // (signalled a period ago)
-            uint32_t *cur = ctx->d_tile_schedule + (size_t)ctx->sched_cur * ns, *alt = ctx->d_tile_schedule + (size_t)(ctx->sched_cur ^ 1u) * ns;
-            VRT_HIP(ctx, vrt::launch_schedule(ctx->d_tile_cost, ctx->d_tile_schedule + 2u * (size_t)ns, cur, alt, nt, ctx->sched_extra, ctx->sched_cap[ctx->sched_mode], ctx->sched_slots[ctx->sched_mode], ctx->stream));
-            VRT_HIP(ctx, hipEventRecord(ctx->ev_sched, ctx->stream));
-            ctx->sched_cur ^= 1u;
-            ctx->params.tile_schedule = alt;
-            ctx->sched_seq++;
-            ctx->sched_since = 0;
-        }
+        VRT_HIP(ctx, schedule_before_frame(ctx, sf));
         VRT_HIP(ctx, vrt::launch_trace(fn, ctx->params, ctx->lds_bytes, ctx->stream));
-        ctx->sched_since++;
     }
     if (marks) VRT_HIP(ctx, hipEventRecord(marks[frames], ctx->stream));
-    if (trial >= 0) {
-        VRT_HIP(ctx, hipEventRecord(ctx->auto_ev[trial][1], ctx->stream));
-        ctx->auto_next = (uint32_t)trial + 1u;
-    }
+    VRT_HIP(ctx, trials_mark(ctx, trial, 1));
     VRT_HIP(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed_frames = frames;
     ctx->in_flight = true;
@@ -349,10 +327,7 @@ static int do_dispatch(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_
 
 int vrt_bounce_autotune_info(vrt_ctx *ctx, double out[4]) {
     if (!ctx || !out) return VRT_E_INVALID_ARG;
-    out[0] = !ctx->bounce_auto || ctx->dist ? 0.0 : (!ctx->auto_decided ? 1.0 : (ctx->auto_use_pool ? 3.0 : 2.0));
-    out[1] = (double)ctx->auto_next;
-    out[2] = (double)ctx->auto_ms[0];
-    out[3] = (double)ctx->auto_ms[1];
+    trials_info(ctx, out);
     return VRT_OK;
 }
 
@@ -461,7 +436,7 @@ int vrt_trace_wave_timeline(vrt_ctx *ctx, const vrt_camera_device *camera, const
     // it the number of spare workgroups it launches — any number up to the list's spare entries: the device buffer holds a row for
     // every wave ANY rule can launch, and the rows reported are counted after the dispatch (sized before it, a rule
     // change made the kernel write past the buffer).
-    const uint64_t waves_max = ((uint64_t)ctx->shard.owned_tiles + (ctx->params.tile_order == 5u ? ctx->sched_extra : 0u)) * 4u;
+    const uint64_t waves_max = (uint64_t)schedule_groups(ctx, true) * 4u;
     if (capacity_pairs < waves_max) return fail(ctx, VRT_E_OUT_OF_RANGE, "timeline buffer too small: 4 x (owned tiles + the schedule's spare entries) pairs");
     DeviceGuard dg(ctx->device);
     const size_t bytes = std::max<size_t>(waves_max * 16u, 32u * sizeof(unsigned long long)); // (the profile build of vrt_path_kernel writes 20 words)
@@ -471,7 +446,7 @@ int vrt_trace_wave_timeline(vrt_ctx *ctx, const vrt_camera_device *camera, const
         const vrt::KernelFn would = (camera && camera->max_bounce > 1) ? (ctx->d_counters ? ctx->product[0] : ctx->kernel) : nullptr;
         if (would && vrt::is_path_kernel(would)) return fail(ctx, VRT_E_STATE, "vrt_trace_wave_timeline: frames with bounces run vrt_path_kernel on this context (no per-tile waves)");
         // (... and so does a context whose auto-tune chose vrt_pool_kernel, or whose next frame would be a pool trial)
-        if (camera && camera->max_bounce > 1 && ctx->bounce_auto && !ctx->dist && ((ctx->auto_decided && ctx->auto_use_pool) || (!ctx->auto_decided && (ctx->auto_next & 1u))))
+        if (camera && trials_pool_frame(ctx, camera, trials_upcoming(ctx)))
             return fail(ctx, VRT_E_STATE, "vrt_trace_wave_timeline: this context's bounce frames run (or are about to try) vrt_pool_kernel (no per-tile waves); VRT_TUNE_NO_BOUNCE_AUTOTUNE keeps the lockstep kernel");
     }
 #endif
@@ -485,7 +460,7 @@ int vrt_trace_wave_timeline(vrt_ctx *ctx, const vrt_camera_device *camera, const
     if (rc == VRT_OK) rc = do_dispatch(ctx, camera, sun, 1, true);
     ctx->params.split_all = split_all;
     ctx->params.wave_timeline = nullptr;
-    const uint64_t waves = ((uint64_t)ctx->shard.owned_tiles + (ctx->params.tile_order == 5u ? ctx->params.sched_units : 0u)) * 4u; // (what that launch held)
+    const uint64_t waves = (uint64_t)schedule_groups(ctx, false) * 4u; // (what that launch held)
     if (rc == VRT_OK && (hipMemcpyAsync(out, d, waves * 16u, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
         rc = fail(ctx, VRT_E_HIP, "timeline read-back failed");
     (void)hipFree(d);

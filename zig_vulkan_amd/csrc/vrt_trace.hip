@@ -1,185 +1,11 @@
-// vrt_trace.hip — tile schedule, root-side un-swizzle, and the launchers / kernel selection called from vrt_api.hip and
-// vrt_frame.hip (the builders of the derived structures: vrt_derived.hip).  The traversal kernels themselves live in vrt_trace_kernels.h and are instantiated by vrt_inst_*.hip.
+// vrt_trace.hip — root-side un-swizzle, and the launchers / kernel selection called from vrt_api.hip and
+// vrt_frame.hip (the builders of the derived structures: vrt_derived.hip; the tile schedule: vrt_schedule.hip).  The traversal kernels themselves live in vrt_trace_kernels.h and are instantiated by vrt_inst_*.hip.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "vrt_internal.h"
 #include "vrt_kernels.h"
 
 namespace vrt {
-
-// Cost-feedback schedule: order[] = owned tile ids in kScheduleBuckets classes of cost (wave-cycles of the most
-// recent frame, relative to the maximum), heaviest class first; INSIDE a class the tiles keep the default
-// reverse-raster order, so that consecutive workgroups still render neighbouring tiles (a full sort by cost
-// measured 6-7 % slower on views without outliers: neighbouring tiles share the lines of the bitmaps they walk).
-// With extra > 0 the tiles whose slowest wave would outlast the rest of the frame (longer than 1.25 x the frame's
-// wave-cycles spread over all wave slots) are SPLIT: two entries, each renders half of the tile with 32 lanes per
-// wave, in a class of their own at the front; at most `extra` tiles, unused spare entries are ~0.  snap[n .. 2n)
-// remembers which tiles are split (their measured waves are scaled back up by 1.28 before the test, the measured
-// gain of splitting, so that a split tile does not flip back and forth).
-// One workgroup.  cost[] ([half][tile][wave], overwritten by every frame) is condensed into snap[] first: frames
-// on another stream may still be writing cost[], and every pass below must see the same values or order[] would
-// not be a permutation.  The order affects timing only, never pixels.
-// Round 4: the halves of split tiles are no longer ONE class in reverse-raster order but kSplitBuckets classes by the tile's slowest
-// wave, slowest first — on the reference app's own run nearly every tile that holds terrain is split (3 000 half-tile workgroups for
-// 1 024 workgroup slots), and with them unordered the second generation of workgroups held waves as long as the first's longest:
-// they started at 100 us and ended at 300 (tools/experiments/timeline_tail.py).
-constexpr uint32_t kScheduleBuckets = 8u;
-constexpr uint32_t kSplitBuckets = 8u;
-constexpr uint32_t kAllBuckets = kScheduleBuckets + kSplitBuckets;
-__global__ __launch_bounds__(1024) void vrt_schedule_kernel(const uint32_t *__restrict__ cost, uint32_t *__restrict__ snap,
-                                                            const uint32_t *prev_order, uint32_t *order, uint32_t n, uint32_t extra_max,
-                                                            uint32_t extra, uint32_t wave_slots) {
-    __shared__ uint32_t s_max, s_nsplit, s_longest;
-    __shared__ unsigned long long s_total;
-    __shared__ uint32_t wave_total[kAllBuckets][16];
-    __shared__ uint32_t class_total[kAllBuckets];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    uint32_t *state = snap + n;
-    // order[] is stored XCD-major: entry k at (k % 8) * row + k / 8.  extra_max: the spare entries the buffer holds (its layout);
-    // extra <= extra_max: how many tiles this sort may split (the frames launch n + extra workgroups)
-    const uint32_t row = (n + extra_max + 7u) >> 3;
-    if (tid == 0) {
-        s_max = 0u;
-        s_nsplit = 0u;
-        s_longest = 0u;
-        s_total = 0ull;
-    }
-    __syncthreads();
-    uint32_t m = 0u, ml = 0u;
-    unsigned long long total = 0ull;
-    const uint4 *cost4 = reinterpret_cast<const uint4 *>(cost);
-#pragma unroll 4
-    for (uint32_t i = tid; i < n; i += 1024u) {
-        const uint4 w = cost4[i]; // the four waves of the tile, most recent frame
-        uint32_t v = w.x + w.y + w.z + w.w;
-        uint32_t longest = max(max(w.x, w.y), max(w.z, w.w));
-        const uint32_t was_split = extra ? (state[i] & 1u) : 0u;
-        if (was_split) {
-            const uint4 w2 = cost4[n + i]; // the waves of the second half
-            v += w2.x + w2.y + w2.z + w2.w;
-            longest = max(longest, max(max(w2.x, w2.y), max(w2.z, w2.w)));
-            longest += (longest >> 2) + (longest >> 5); // what the wave would take unsplit
-        }
-        // (the classes come from the mean of this measurement and the running value: a tile's cycles depend on what
-        // runs beside it, i.e. on the order itself, and an order made from one frame's costs alone keeps changing)
-        const uint32_t prev = snap[i];
-        if (prev) v = (uint32_t)(((unsigned long long)prev + v) >> 1);
-        snap[i] = v;
-        state[i] = (min(longest, 0x7FFFFFFFu) << 1) | was_split;
-        m = max(m, v);
-        ml = max(ml, longest);
-        total += v;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        m = max(m, (uint32_t)__shfl_down(m, off, 64));
-        ml = max(ml, (uint32_t)__shfl_down(ml, off, 64));
-        total += __shfl_down(total, off, 64);
-    }
-    if (lane == 0u) {
-        atomicMax(&s_max, m);
-        atomicMax(&s_longest, ml);
-        atomicAdd(&s_total, total);
-    }
-    __syncthreads(); // (also orders the snap[] / state[] writes before the reads of other threads below)
-    const uint32_t mx = s_max;
-    if (mx == 0u) { // no measurement yet: keep the current order
-        if (order != prev_order)
-            for (uint32_t i = tid; i < 8u * row; i += 1024u) order[i] = prev_order[i];
-        for (uint32_t i = tid; i < n; i += 1024u) state[i] &= 1u;
-        return;
-    }
-    // A frame whose slowest wave is well below (0.6 x) the time the frame needs anyway (its wave-cycles spread over all
-    // wave slots) keeps the plain reverse-raster order: there the launch order cannot shorten anything.  Otherwise: cost
-    // classes, and which tiles to split.
-    const unsigned long long par = s_total / (wave_slots ? wave_slots : 1u);
-    const bool reorder = (unsigned long long)s_longest * 5ull > par * 3ull;
-    const unsigned long long threshold = par + (par >> 2);
-    const uint32_t top_bar = (uint32_t)(0.85f * (float)s_longest); // (0.7: the headline's V1 +3 %; none: V1 / V2 +2 %)
-#pragma unroll 4
-    for (uint32_t i = tid; i < n; i += 1024u) {
-        // (... and the frame's very longest waves whatever the bar says: a frame whose slowest wave is all of it — the headline's V1 / V2 —
-        // ends with that wave)
-        uint32_t want = (reorder && extra && ((unsigned long long)(state[i] >> 1) > threshold || (state[i] >> 1) > top_bar)) ? 1u : 0u;
-        if (want && atomicAdd(&s_nsplit, 1u) >= extra) want = 0u; // no spare entry left
-        state[i] = (state[i] & ~1u) | want; // (bits 1-31: the tile's slowest wave, for the class of a split tile below)
-    }
-    __syncthreads();
-    const uint32_t nsplit = min(s_nsplit, extra);
-    const float scale = reorder ? (float)kScheduleBuckets / (float)mx : 0.0f; // (0: one class, i.e. reverse raster)
-    // ONE scale for all workgroups when tiles are split: the expected time of the workgroup's slowest wave — the tile's slowest wave,
-    // over 1.28 for a half (what splitting gains) — so that a whole tile with a long wave is not launched behind every half
-    const float split_scale = (float)kAllBuckets / (float)max(1u, s_longest);
-    auto class_of = [&](uint32_t tile, uint32_t st) {
-        if (nsplit != 0u) return min(kAllBuckets - 1u, (uint32_t)((float)(st >> 1) * ((st & 1u) ? 0.78125f : 1.0f) * split_scale));
-        return min(kScheduleBuckets - 1u, (uint32_t)((float)snap[tile] * scale));
-    };
-    // thread t owns positions [lo, hi) of the default order (position j = tile n-1-j)
-    const uint32_t chunk = (n + 1023u) / 1024u;
-    const uint32_t lo = min(n, tid * chunk), hi = min(n, lo + chunk);
-    uint32_t cnt[kAllBuckets]; // classes kScheduleBuckets ...: the halves of split tiles
-#pragma unroll
-    for (uint32_t b = 0; b < kAllBuckets; b++) cnt[b] = 0u;
-#pragma unroll 4
-    for (uint32_t j = lo; j < hi; j++) {
-        const uint32_t tile = n - 1u - j;
-        const uint32_t st = state[tile], sp = st & 1u;
-        const uint32_t b = class_of(tile, st);
-#pragma unroll
-        for (uint32_t k = 0; k < kAllBuckets; k++) cnt[k] += (k == b) ? (1u + sp) : 0u;
-    }
-    // exclusive scan of every class over the threads, heaviest class first: inside the wave by shuffles, over the 16 waves
-    // by one thread per class
-    uint32_t pos[kAllBuckets];
-#pragma unroll
-    for (uint32_t b = 0; b < kAllBuckets; b++) {
-        uint32_t incl = cnt[b];
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
-            if (lane >= (uint32_t)off) incl += up;
-        }
-        pos[b] = incl - cnt[b]; // exclusive, inside the wave
-        if (lane == 63u) wave_total[b][wv] = incl;
-    }
-    __syncthreads();
-    if (tid < kAllBuckets) {
-        uint32_t acc = 0u;
-        for (uint32_t k = 0; k < 16u; k++) {
-            const uint32_t t = wave_total[tid][k];
-            wave_total[tid][k] = acc; // -> exclusive over the waves
-            acc += t;
-        }
-        class_total[tid] = acc;
-    }
-    __syncthreads();
-    {
-        uint32_t base = 0u;
-#pragma unroll
-        for (int b = (int)kAllBuckets - 1; b >= 0; b--) {
-            pos[b] += base + wave_total[b][wv];
-            base += class_total[b];
-        }
-    }
-    for (uint32_t j = lo; j < hi; j++) {
-        const uint32_t tile = n - 1u - j;
-        const uint32_t st = state[tile], sp = st & 1u;
-        const uint32_t b = class_of(tile, st);
-        uint32_t at = 0u;
-#pragma unroll
-        for (uint32_t k = 0; k < kAllBuckets; k++) {
-            if (k == b) {
-                at = pos[k];
-                pos[k] += 1u + sp;
-            }
-        }
-        if (sp) {
-            order[(at & 7u) * row + (at >> 3)] = tile | 0x80000000u;
-            order[((at + 1u) & 7u) * row + ((at + 1u) >> 3)] = tile | 0xC0000000u;
-        } else {
-            order[(at & 7u) * row + (at >> 3)] = tile;
-        }
-    }
-    for (uint32_t at = n + nsplit + tid; at < 8u * row; at += 1024u) order[(at & 7u) * row + (at >> 3)] = 0xFFFFFFFFu; // idle workgroups
-}
 
 // Root-side un-swizzle of gathered shards (rank-major, tile-major) into a
 // row-major frame.  One thread per pixel.
@@ -499,13 +325,6 @@ hipError_t launch_trace(KernelFn fn, const TraceParams &params, size_t lds_bytes
     else if (p.wave_groups) VRT_LAUNCH(fn, dim3((p.owned_tiles + (p.tile_order == 5u ? p.sched_units : 0u)) * 4u, frames), dim3(64), lds_bytes, stream, p);
     else if (p.tile_order == 3u && p.split_all) VRT_LAUNCH(fn, dim3(p.owned_tiles << p.split_all, frames), dim3(256), lds_bytes, stream, p);
     else VRT_LAUNCH(fn, dim3(p.owned_tiles + (p.tile_order == 5u ? p.sched_units : 0u), frames), dim3(256), lds_bytes, stream, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_schedule(const uint32_t *cost, uint32_t *snap, const uint32_t *prev_order, uint32_t *order, uint32_t n, uint32_t extra_max,
-                           uint32_t extra, uint32_t wave_slots, hipStream_t stream) {
-    VRT_LAUNCH(vrt_schedule_kernel, dim3(1), dim3(1024), 0, stream, cost, snap, prev_order, order, n, extra_max, extra < extra_max ? extra : extra_max,
-                       wave_slots);
     return hipGetLastError();
 }
 
