@@ -102,6 +102,14 @@ pub const DerivedId = enum(c_int) {
     materials_plain = 7,
 };
 
+/// vrt_read_schedule's `part` (vrt_schedule_info / vrt_read_schedule / vrt_schedule_sort: a test and diagnosis aid; the layouts are
+/// the library's own and may change)
+pub const schedule_order_current: u32 = 0;
+pub const schedule_order_other: u32 = 1;
+pub const schedule_snapshot: u32 = 2;
+pub const schedule_split_state: u32 = 3;
+pub const schedule_cost: u32 = 4;
+
 // ---- data contract structs: field for field include/vrt_hip.h (checked by tests/test_abi.py) ----
 pub const GridState = extern struct { // State.Device, State.zig:60-79
     voxel_dim_x: u32,
@@ -356,6 +364,9 @@ pub extern fn vrt_region_end(ctx: ?*Ctx, ms: [*c]f64) c_int;
 pub extern fn vrt_get_counters(ctx: ?*Ctx, out: [*c]Counters) c_int;
 pub extern fn vrt_get_wave_counters(ctx: ?*Ctx, out: *[3]u64) c_int;
 pub extern fn vrt_trace_wave_timeline(ctx: ?*Ctx, camera: [*c]const CameraDevice, sun: [*c]const SunDevice, out: [*c]u64, capacity_pairs: u64, n_pairs: [*c]u64) c_int;
+pub extern fn vrt_schedule_info(ctx: ?*const Ctx, out: *[12]u32) c_int;
+pub extern fn vrt_read_schedule(ctx: ?*Ctx, part: u32, dst: ?*anyopaque, nbytes: u64) c_int;
+pub extern fn vrt_schedule_sort(ctx: ?*Ctx, cost: [*c]const u32, snap_state: [*c]u32, prev_order: [*c]const u32, order: [*c]u32, n: u32, extra_max: u32, extra: u32, wave_slots: u32, in_place: u32) c_int;
 pub extern fn vrt_device_info(device: c_int, out: *[4]i64) c_int;
 pub extern fn vrt_last_error(ctx: ?*const Ctx) [*:0]const u8;
 pub extern fn vrt_abi_version() u32;

@@ -379,6 +379,39 @@ int vrt_get_wave_counters(vrt_ctx *ctx, uint64_t out[3]);
 int vrt_trace_wave_timeline(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_sun_device *sun, uint64_t *out,
                             uint64_t capacity_pairs, uint64_t *n_pairs);
 
+/* ---- Read-back of the cost-feedback tile schedule, and one sort on the caller's arrays: a test and diagnosis aid ---------------
+ * The schedule orders the launch of a frame's tiles (kernel_variant's order field 5 and 7, and 7 chosen by the library); it affects
+ * timing only, never pixels, so no image can tell whether it is right.  These three hand it out, so that a test can compare it with a
+ * model of its definition.  THE LAYOUTS ARE THE LIBRARY'S OWN AND MAY CHANGE with any release: nothing but tests and diagnosis tools
+ * should call these.
+ * vrt_schedule_info: out = {tile order (3, 5, 7, ...), owned tiles n, spare entries of an order buffer (extra_max), words of an order
+ * buffer (8 * ceil((n + extra_max) / 8)), the order buffer frames read (0 / 1), the rule the current order was sorted under (0 / 1),
+ * tiles a sort may split under rule 0, under rule 1, wave slots of rule 0, of rule 1, frames between two sorts (0: none, or before
+ * every frame), sorts so far (low word)}.  VRT_E_INVALID_ARG: a NULL pointer.
+ * vrt_read_schedule: waits for both of the context's streams, then copies the first nbytes of one part: the order frames read now,
+ * the other order buffer (an order is stored in 8 rows: entry k at (k % 8) * words / 8 + k / 8; an entry is a tile, tile | 0x80000000
+ * and tile | 0xC0000000 for the two halves of a split tile, or 0xFFFFFFFF: idle), the snapshot of the costs (a word per tile), the
+ * split state (a word per tile: bit 0 split, bits 1-31 the slowest wave) or the costs ([half][tile][wave], 8 n words, as the most
+ * recent frames wrote them).  VRT_E_INVALID_ARG: a NULL ctx, a bad part, a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: more than the
+ * part holds.
+ * vrt_schedule_sort: runs the schedule's kernel once, launched as the frames' sorts launch it, on copies of the caller's arrays in
+ * scratch device buffers of exactly these sizes: cost 8 n words, snap_state 2 n (in and out: the snapshot, then the split state),
+ * prev_order and order 8 * ceil((n + extra_max) / 8) each (in_place != 0: one buffer, which starts as prev_order).  extra <= extra_max:
+ * the tiles this sort may split.  Waits, and copies snap_state and order back; the scratch buffers are freed before it returns.  At
+ * least 64 guard words lie before and after each buffer and order starts as a pattern: VRT_E_STATE if the kernel changed a guard
+ * word, the costs or (not in place) the previous order.  VRT_E_INVALID_ARG: a NULL pointer, n == 0, extra > extra_max;
+ * VRT_E_OUT_OF_RANGE: n or extra_max above 2^24.  The context's own schedule is not touched. */
+#define VRT_SCHEDULE_ORDER_CURRENT 0u
+#define VRT_SCHEDULE_ORDER_OTHER   1u
+#define VRT_SCHEDULE_SNAPSHOT      2u
+#define VRT_SCHEDULE_SPLIT_STATE   3u
+#define VRT_SCHEDULE_COST          4u
+#define VRT_SCHEDULE_PART_COUNT    5u
+int vrt_schedule_info(const vrt_ctx *ctx, uint32_t out[12]);
+int vrt_read_schedule(vrt_ctx *ctx, uint32_t part, void *dst, uint64_t nbytes);
+int vrt_schedule_sort(vrt_ctx *ctx, const uint32_t *cost, uint32_t *snap_state, const uint32_t *prev_order, uint32_t *order, uint32_t n,
+                      uint32_t extra_max, uint32_t extra, uint32_t wave_slots, uint32_t in_place);
+
 /* out = {engine clock in kHz, compute units, wavefront size, L2 bytes} of HIP device `device` (-1: current):
  * what bench.py prices an instruction-issue rate against. */
 int vrt_device_info(int device, int64_t out[4]);

@@ -56,6 +56,11 @@ BUF_COUNT = 7
 DERIVED_COUNT = 8
 DERIVED_NAMES = ("cell_bounds", "status_bytes", "status_halfblocks", "cell_occupancy", "cell_material", "cell_box", "start_is_slot", "materials_plain")
 
+# parts of the cost-feedback tile schedule (vrt_read_schedule) and the fields of vrt_schedule_info: a test and diagnosis aid
+SCHEDULE_ORDER_CURRENT, SCHEDULE_ORDER_OTHER, SCHEDULE_SNAPSHOT, SCHEDULE_SPLIT_STATE, SCHEDULE_COST = range(5)
+SCHEDULE_PART_COUNT = 5
+SCHEDULE_INFO_FIELDS = ("tile_order", "n", "extra", "stride", "cur", "mode", "cap0", "cap1", "slots0", "slots1", "period", "seq")
+
 
 class VrtError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -279,6 +284,9 @@ SIGNATURES = {
     "vrt_scene_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
     "vrt_derived_size": (C.c_uint64, [_ctx, C.c_int]),
     "vrt_read_derived": (C.c_int, [_ctx, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_schedule_info": (C.c_int, [_ctx, _P(C.c_uint32 * 12)]),
+    "vrt_read_schedule": (C.c_int, [_ctx, C.c_uint32, C.c_void_p, C.c_uint64]),
+    "vrt_schedule_sort": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vrt_compact_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
     "vrt_grid_fill_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
     "vrt_grid_clear_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),

@@ -19,6 +19,7 @@
 // What a sort computes is the kernel's comment; it affects timing only, never pixels.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <string>
 #include <vector>
 #include "vrt_ctx.h"
 
@@ -82,7 +83,11 @@ __global__ __launch_bounds__(1024) void vrt_schedule_kernel(const uint32_t *__re
         const uint32_t prev = snap[i];
         if (prev) v = (uint32_t)(((unsigned long long)prev + v) >> 1);
         snap[i] = v;
-        state[i] = (min(longest, 0x7FFFFFFFu) << 1) | was_split;
+        // (kept in 31 bits, and the frame's longest wave is the longest of what is KEPT: the bars and the classes below compare it with
+        // state[] — against the unclamped maximum the longest wave itself fell below 0.85 x the longest and into a class of its own
+        // making, and the order was no function of snap[] and state[])
+        longest = min(longest, 0x7FFFFFFFu);
+        state[i] = (longest << 1) | was_split;
         m = max(m, v);
         ml = max(ml, longest);
         total += v;
@@ -204,13 +209,20 @@ using vrt::ScheduleFrame;
 using vrt::TileSchedule;
 #define VRT_TRY(call) do { if (const hipError_t e_ = (call); e_ != hipSuccess) return e_; } while (0)
 
-// order `into` sorted from order `from` by the measured costs, on the primary stream; units, wave_slots: the rule (tiles it may split, its bar)
-static hipError_t launch_schedule(const vrt_ctx *ctx, uint32_t from, uint32_t into, uint32_t units, uint32_t wave_slots) {
+// one sort, on `stream`: the only place vrt_schedule_kernel is launched from.  cost: 8 n words; snap: 2 n (snapshot, split state); from / into: order
+// buffers of 8 * ceil((n + extra_max) / 8) words (the same buffer: in place); extra, wave_slots: the rule (tiles it may split, its bar)
+static hipError_t launch_schedule(hipStream_t stream, const uint32_t *cost, uint32_t *snap, const uint32_t *from, uint32_t *into, uint32_t n,
+                                  uint32_t extra_max, uint32_t extra, uint32_t wave_slots) {
+    VRT_LAUNCH(vrt::vrt_schedule_kernel, dim3(1), dim3(1024), 0, stream, cost, snap, from, into, n, extra_max, extra, wave_slots);
+    return hipGetLastError();
+}
+
+// order `into` of the context sorted from its order `from` by the measured costs, on the primary stream; units, wave_slots: the rule
+static hipError_t sort_orders(const vrt_ctx *ctx, uint32_t from, uint32_t into, uint32_t units, uint32_t wave_slots) {
     const TileSchedule &s = ctx->sched;
     uint32_t *const order = s.d_tile_schedule, *const snap = order + 2u * (size_t)s.stride;
-    VRT_LAUNCH(vrt::vrt_schedule_kernel, dim3(1), dim3(1024), 0, ctx->stream, s.d_tile_cost, snap, order + (size_t)from * s.stride, order + (size_t)into * s.stride,
-               ctx->shard.owned_tiles, s.extra, std::min(units, s.extra), wave_slots);
-    return hipGetLastError();
+    return launch_schedule(ctx->stream, s.d_tile_cost, snap, order + (size_t)from * s.stride, order + (size_t)into * s.stride, ctx->shard.owned_tiles, s.extra,
+                           std::min(units, s.extra), wave_slots);
 }
 
 hipError_t schedule_create(vrt_ctx *c, uint32_t cus) {
@@ -247,7 +259,7 @@ hipError_t schedule_create(vrt_ctx *c, uint32_t cus) {
     VRT_TRY(hipMemcpy(s.d_tile_schedule, init.data(), ns * 4u, hipMemcpyHostToDevice));
     // first launch of the schedule kernel now (code-object load, about 2 ms, stays out of the frames): with no cost
     // measured yet it copies the initial order into the second buffer
-    if (n > 1u) VRT_TRY(launch_schedule(c, 0u, 1u, s.cap[0], s.slots[0]));
+    if (n > 1u) VRT_TRY(sort_orders(c, 0u, 1u, s.cap[0], s.slots[0]));
     if (order != 7u) return hipSuccess;
     // the cost-feedback schedule, re-sorted every 32 frames instead of every frame: the kernel sees order 5
     s.period = (variant >> 28) ? (1u << (variant >> 28)) : 32u; // tuning knob: log2 of the period
@@ -293,7 +305,7 @@ hipError_t schedule_after_b(vrt_ctx *ctx) {
 hipError_t schedule_sort_in_place(vrt_ctx *ctx, const ScheduleFrame &f) {
     if (!(ctx->params.tile_order == 5u && ctx->shard.owned_tiles > 1u && !ctx->sched.period && f.scheduled)) return hipSuccess;
     // re-sort the tile list by last frame's measured cost (inside the timed region: it is per-frame work)
-    return launch_schedule(ctx, 0u, 0u, 0u, ctx->sched.slots[0]);
+    return sort_orders(ctx, 0u, 0u, 0u, ctx->sched.slots[0]);
 }
 
 hipError_t schedule_change_rule(vrt_ctx *ctx, const ScheduleFrame &f) {
@@ -320,7 +332,7 @@ hipError_t schedule_before_frame(vrt_ctx *ctx, const ScheduleFrame &f) {
         // stream with event waits 80 us per sort; on a second stream with the host polling for its completion nothing, but
         // then the order lags behind frames that are queued ahead (vrt_dispatch_repeat) by a whole call.
         if (s.b_recorded) VRT_TRY(hipStreamWaitEvent(ctx->stream, s.ev_b_sched, 0)); // (signalled a period ago)
-        VRT_TRY(launch_schedule(ctx, s.cur, s.cur ^ 1u, s.cap[s.mode], s.slots[s.mode]));
+        VRT_TRY(sort_orders(ctx, s.cur, s.cur ^ 1u, s.cap[s.mode], s.slots[s.mode]));
         VRT_TRY(hipEventRecord(s.ev_sched, ctx->stream));
         s.cur ^= 1u;
         ctx->params.tile_schedule = s.d_tile_schedule + (size_t)s.cur * s.stride;
@@ -336,3 +348,89 @@ uint32_t schedule_groups(const vrt_ctx *ctx, bool any_rule) {
 }
 #undef VRT_TRY
 } // namespace vrt_impl
+
+using namespace vrt_impl;
+
+extern "C" {
+
+// ---- read-back and a sort on the caller's arrays: a test and diagnosis aid (include/vrt_hip.h) ----
+
+int vrt_schedule_info(const vrt_ctx *ctx, uint32_t out[12]) {
+    if (!ctx || !out) return VRT_E_INVALID_ARG;
+    const vrt::TileSchedule &s = ctx->sched;
+    const uint32_t v[12] = {s.tile_order, ctx->shard.owned_tiles, s.extra, s.stride, s.cur, s.mode, s.cap[0], s.cap[1], s.slots[0], s.slots[1], s.period, (uint32_t)s.seq};
+    std::copy(v, v + 12, out);
+    return VRT_OK;
+}
+
+int vrt_read_schedule(vrt_ctx *ctx, uint32_t part, void *dst, uint64_t nbytes) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (part >= VRT_SCHEDULE_PART_COUNT) return fail(ctx, VRT_E_INVALID_ARG, "bad schedule part");
+    if (nbytes && !dst) return fail(ctx, VRT_E_INVALID_ARG, "dst is NULL");
+    const vrt::TileSchedule &s = ctx->sched;
+    if (!s.d_tile_schedule || !s.d_tile_cost) return fail(ctx, VRT_E_STATE, "this context holds no tile schedule");
+    const size_t n = ctx->shard.owned_tiles ? ctx->shard.owned_tiles : 1u; // (what schedule_create sized the buffers for)
+    const uint32_t *src = nullptr;
+    size_t words = 0;
+    switch (part) {
+    case VRT_SCHEDULE_ORDER_CURRENT: src = s.d_tile_schedule + (size_t)s.cur * s.stride, words = s.stride; break;
+    case VRT_SCHEDULE_ORDER_OTHER: src = s.d_tile_schedule + (size_t)(s.cur ^ 1u) * s.stride, words = s.stride; break;
+    case VRT_SCHEDULE_SNAPSHOT: src = s.d_tile_schedule + 2u * (size_t)s.stride, words = n; break;
+    case VRT_SCHEDULE_SPLIT_STATE: src = s.d_tile_schedule + 2u * (size_t)s.stride + n, words = n; break;
+    default: src = s.d_tile_cost, words = 8u * n; break;
+    }
+    if (nbytes > words * 4u) return fail(ctx, VRT_E_OUT_OF_RANGE, "read exceeds the schedule part");
+    if (nbytes == 0) return VRT_OK;
+    DeviceGuard dg(ctx->device);
+    VRT_HIP(ctx, wait_stream(ctx->stream)); // (frames and sorts of both streams write what is read here)
+    if (ctx->stream_b) VRT_HIP(ctx, wait_stream(ctx->stream_b));
+    VRT_HIP(ctx, hipMemcpy(dst, src, nbytes, hipMemcpyDeviceToHost));
+    return VRT_OK;
+}
+
+int vrt_schedule_sort(vrt_ctx *ctx, const uint32_t *cost, uint32_t *snap_state, const uint32_t *prev_order, uint32_t *order, uint32_t n, uint32_t extra_max,
+                      uint32_t extra, uint32_t wave_slots, uint32_t in_place) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (!cost || !snap_state || !prev_order || !order) return fail(ctx, VRT_E_INVALID_ARG, "a NULL array");
+    if (n == 0u) return fail(ctx, VRT_E_INVALID_ARG, "n is 0");
+    if (extra > extra_max) return fail(ctx, VRT_E_INVALID_ARG, "extra exceeds extra_max");
+    if (n > (1u << 24) || extra_max > (1u << 24)) return fail(ctx, VRT_E_OUT_OF_RANGE, "more than 2^24 tiles or spare entries");
+    // one allocation: guard | cost | guard | snapshot + state | guard | previous order | guard | order | guard (in place: one order buffer), each
+    // buffer of exactly its documented size, so that a write one word outside lands in a guard
+    constexpr size_t kGuard = 64; // words; keeps cost (read as uint4) 16-byte aligned
+    constexpr uint32_t kGuardWord = 0x6A5D0000u, kFill = 0x5EED5EEDu;
+    const size_t ns = 8u * (((size_t)n + extra_max + 7u) / 8u);
+    const size_t at_cost = kGuard, at_snap = at_cost + 8u * (size_t)n + kGuard, at_prev = at_snap + 2u * (size_t)n + kGuard;
+    const size_t at_order = in_place ? at_prev : at_prev + ns + kGuard, total = at_order + ns + kGuard;
+    std::vector<uint32_t> host(total), back(total);
+    for (size_t i = 0; i < total; i++) host[i] = kGuardWord | (uint32_t)(i & 0xFFFFu); // (every word that is no buffer is a guard)
+    std::copy(cost, cost + 8u * (size_t)n, host.begin() + at_cost);
+    std::copy(snap_state, snap_state + 2u * (size_t)n, host.begin() + at_snap);
+    if (!in_place) std::fill(host.begin() + at_order, host.begin() + at_order + ns, kFill);
+    std::copy(prev_order, prev_order + ns, host.begin() + at_prev);
+    DeviceGuard dg(ctx->device);
+    uint32_t *d = nullptr;
+    if (const hipError_t e = hipMalloc(&d, total * 4u); e != hipSuccess) return hip_fail(ctx, e, "hipMalloc of the sort's scratch buffers");
+    hipError_t e = hipMemcpy(d, host.data(), total * 4u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_schedule(ctx->stream, d + at_cost, d + at_snap, d + at_prev, d + at_order, n, extra_max, extra, wave_slots);
+    if (e == hipSuccess) e = wait_stream(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(back.data(), d, total * 4u, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return hip_fail(ctx, e, "vrt_schedule_sort");
+    std::copy(back.begin() + at_snap, back.begin() + at_snap + 2u * (size_t)n, snap_state);
+    std::copy(back.begin() + at_order, back.begin() + at_order + ns, order);
+    const auto buffer = [&](size_t i) {
+        return (i >= at_cost && i < at_cost + 8u * (size_t)n) || (i >= at_snap && i < at_snap + 2u * (size_t)n) || (i >= at_prev && i < at_prev + ns) ||
+               (i >= at_order && i < at_order + ns);
+    };
+    for (size_t i = 0; i < total; i++)
+        if (!buffer(i) && back[i] != host[i]) return fail(ctx, VRT_E_STATE, "vrt_schedule_kernel wrote outside its buffers (guard word " + std::to_string(i) + ")");
+    for (size_t i = at_cost; i < at_cost + 8u * (size_t)n; i++)
+        if (back[i] != host[i]) return fail(ctx, VRT_E_STATE, "vrt_schedule_kernel wrote to the costs");
+    if (!in_place)
+        for (size_t i = at_prev; i < at_prev + ns; i++)
+            if (back[i] != host[i]) return fail(ctx, VRT_E_STATE, "vrt_schedule_kernel wrote to the previous order");
+    return VRT_OK;
+}
+
+} // extern "C"

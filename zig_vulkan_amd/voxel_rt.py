@@ -526,6 +526,40 @@ class VoxelRT:
         self._check(self._lib.vrt_read_derived(self._h, derived_id, 0, out.ctypes.data, n))
         return out.view(_DERIVED_DTYPES.get(derived_id, np.uint8))
 
+    def schedule_info(self) -> dict:
+        """The cost-feedback tile schedule's host state (vrt_schedule_info: a test and diagnosis aid), by L.SCHEDULE_INFO_FIELDS: tile_order,
+        n (owned tiles), extra (spare entries), stride (words of an order buffer), cur, mode, cap0, cap1, slots0, slots1, period, seq."""
+        out = (C.c_uint32 * 12)()
+        self._check(self._lib.vrt_schedule_info(self._h, C.byref(out)))
+        return dict(zip(L.SCHEDULE_INFO_FIELDS, (int(v) for v in out)))
+
+    def read_schedule(self, part: int) -> np.ndarray:
+        """uint32 copy of one part of the tile schedule (L.SCHEDULE_*: the order frames read, the other order, the snapshot, the split
+        state, the costs as [half, tile, wave]) once both streams are idle (vrt_read_schedule: a test and diagnosis aid, the layouts are
+        the library's own)."""
+        info = self.schedule_info()
+        n = max(1, info["n"])
+        words = {L.SCHEDULE_ORDER_CURRENT: info["stride"], L.SCHEDULE_ORDER_OTHER: info["stride"], L.SCHEDULE_SNAPSHOT: n,
+                 L.SCHEDULE_SPLIT_STATE: n, L.SCHEDULE_COST: 8 * n}[part]
+        out = np.empty(words, dtype=np.uint32)
+        self._check(self._lib.vrt_read_schedule(self._h, part, out.ctypes.data, out.nbytes))
+        return out.reshape(2, n, 4) if part == L.SCHEDULE_COST else out
+
+    def schedule_sort(self, cost, snap_state, prev_order, n: int, extra_max: int, extra: int, wave_slots: int, in_place: bool = False):
+        """One run of the schedule's kernel on host arrays (vrt_schedule_sort: a test and diagnosis aid): cost 8 n words, snap_state
+        2 n (snapshot, then split state), prev_order 8 * ceil((n + extra_max) / 8).  Returns (snap_state, order) as the kernel left them;
+        raises if it wrote outside its buffers."""
+        cost = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+        snap_state = np.array(snap_state, dtype=np.uint32).reshape(-1)
+        prev_order = np.ascontiguousarray(prev_order, dtype=np.uint32).reshape(-1)
+        ns = 8 * ((n + extra_max + 7) // 8)
+        if cost.size != 8 * n or snap_state.size != 2 * n or prev_order.size != ns:
+            raise ValueError("schedule_sort: cost holds 8 n words, snap_state 2 n, prev_order 8 * ceil((n + extra_max) / 8)")
+        order = np.empty(ns, dtype=np.uint32)
+        self._check(self._lib.vrt_schedule_sort(self._h, cost.ctypes.data, snap_state.ctypes.data, prev_order.ctypes.data, order.ctypes.data,
+                                                n, extra_max, extra, wave_slots, 1 if in_place else 0))
+        return snap_state, order
+
     def scene_bricks(self) -> Tuple[int, int]:
         """(allocated bricks, next material entry) as the next insert continues them (vrt_scene_bricks)."""
         out = (C.c_uint32 * 2)()
