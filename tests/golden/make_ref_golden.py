@@ -243,8 +243,48 @@ def main_big(only=()):
         print(f"{name}: {width}x{height}, {spp} spp, max_bounce {bounce}, {time.time() - t0:.1f} s under llvmpipe, mean colour {f[:, :, :3].mean(axis=(0, 1))}", flush=True)
 
 
+# ---- frames built to tie in the DDA (tests/tie_rays.py): the fan cameras on the island scene, one per brick size, 17 x 17, one sample, hard
+# sun.  A folder of their own: the fused-lowering tolerance tests glob tests/golden/ref/, and a tie is where a last-bit difference flips a pixel.
+TIES_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_ties")
+
+
+def tie_cases():
+    from tests import tie_rays as T
+    want = [("island", 8, "lattice_out", 17), ("island", 4, "lattice_out", 17), ("island", 8, "cell_centre", 17)]
+    return [next(c for c in T.FRAME_CASES if (c.kind, c.b, c.origin, c.width) == w and c.dims == T.CUBE) for w in want]
+
+
+def main_ties():
+    from tests import tie_rays as T
+    os.makedirs(TIES_OUT, exist_ok=True)
+    info = GlRef().info()
+    check_implementation(info, OUT)        # (the first tie fixture is made under the implementation of tests/golden/ref/ too)
+    check_implementation(info, TIES_OUT)
+    for case in tie_cases():
+        scene = oracle_scene_from_grid(case.grid(), T.materials())
+        pc = O.push_constants(case.camera(), case.sun())
+        f, u = ReferenceShader(case.b).render(scene, pc)
+        fo, uo, _ = O.render(scene, pc, lowering="llvmpipe")
+        same = bool(np.array_equal(f.view(np.uint32), fo.view(np.uint32)) and np.array_equal(u, uo))
+        name = f"ties_b{case.b}_{case.origin}_{'m' if case.axis[0] == '-' else 'p'}{case.axis[1]}"
+        np.savez_compressed(
+            os.path.join(TIES_OUT, name + ".npz"),
+            provenance=np.array(f"brick_raytracer.comp + rand.comp of /root/reference, OpenGL dialect edits E1-E8 of "
+                                f"oracle/ref_gl/recipe.py, {info}"),
+            case=np.array(case.id), brick_dimension=np.int32(case.b),
+            grid_state=scene.grid_state, materials=scene.materials.view(np.uint8).reshape(-1),
+            brick_status=scene.brick_status, brick_index=scene.brick_index, brick_occupancy=scene.brick_occupancy,
+            brick_start_index=scene.brick_start_index, material_index=scene.material_index,
+            push_constants=pc,
+            rgba8=u, rgb32f=np.ascontiguousarray(f[:, :, :3]),
+            float_sha256=np.array(hashlib.sha256(f.tobytes()).hexdigest()))
+        print(f"{name}: {case.width}x{case.width}, oracle(llvmpipe lowering) bit-equal: {same}")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "big":
+    if len(sys.argv) > 1 and sys.argv[1] == "ties":
+        main_ties()
+    elif len(sys.argv) > 1 and sys.argv[1] == "big":
         main_big(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "full":
         main_full(sys.argv[2:])
@@ -252,3 +292,4 @@ if __name__ == "__main__":
         main()
         main_present()
         main_full()
+        main_ties()

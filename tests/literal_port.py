@@ -71,12 +71,15 @@ def ray_at(origin, direction, t):
     return [fma(t, direction[i], origin[i]) for i in range(3)]
 
 
-def adv_norm_intersect(sc: Scene, origin, inv_dir, t_min, t_max):
+def adv_norm_intersect(sc: Scene, origin, inv_dir, t_min, t_max, entry_select=None):
+    """entry_select: None, or a function t_mins -> axis that takes indexOfMaxComponent's place (tests/tie_rays.py)."""
     t_lower = [(sc.g_min[i] - origin[i]) * inv_dir[i] for i in range(3)]
     t_upper = [(sc.g_max[i] - origin[i]) * inv_dir[i] for i in range(3)]
     t_mins = [gl_min(t_lower[i], t_upper[i]) for i in range(3)]
     t_maxes = [gl_max(t_lower[i], t_upper[i]) for i in range(3)]
     index = int(t_mins[1] > t_mins[0] and t_mins[1] > t_mins[2]) + 2 * int(t_mins[2] > t_mins[0] and t_mins[2] > t_mins[1])
+    if entry_select is not None:
+        index = entry_select(t_mins)
     normal = [f32(0.0)] * 3
     normal[index] = sign(inv_dir[index])
     t_min = gl_max(t_min, t_mins[index])
@@ -84,9 +87,12 @@ def adv_norm_intersect(sc: Scene, origin, inv_dir, t_min, t_max):
     return bool(t_min <= t_max), normal, t_min, t_max
 
 
-def _dda_step(side, delta, step, pos, scale, normal_axis):
-    """The shader's nested branches; returns the new t_value and normal, updates side/pos in place."""
-    if side[0] < side[1]:
+def _dda_step(side, delta, step, pos, scale, normal_axis, select=None):
+    """The shader's nested branches; returns the new t_value and normal, updates side/pos in place.  select: None, or a function
+    side -> axis that takes the branches' place (tests/tie_rays.py: the same walk under another tie rule, with the ties counted)."""
+    if select is not None:
+        a = select(side)
+    elif side[0] < side[1]:
         a = 0 if side[0] < side[2] else 2
     else:
         a = 1 if side[1] < side[2] else 2
@@ -107,7 +113,7 @@ def _side_dist(step, fposition, delta):
     return out
 
 
-def brick_hit(sc: Scene, origin, direction, ignore_type, internal_reflection, t_max, delta, step, brick, brick_min, hit):
+def brick_hit(sc: Scene, origin, direction, ignore_type, internal_reflection, t_max, delta, step, brick, brick_min, hit, select=None):
     voxel_scale = sc.scale * sc.brick_voxel_scale
     base = brick * sc.brick_bytes
     p = ray_at(origin, direction, hit["t"])
@@ -134,17 +140,18 @@ def brick_hit(sc: Scene, origin, direction, ignore_type, internal_reflection, t_
                 q = ray_at(origin, direction, hit["t"])
                 hit["point"] = [q[i] + hit["normal"][i] * t_offset for i in range(3)]
                 return True
-        t_value, hit["normal"] = _dda_step(side, delta, step, pos, voxel_scale, normal_axis)
+        t_value, hit["normal"] = _dda_step(side, delta, step, pos, voxel_scale, normal_axis, select)
     return False
 
 
-def grid_hit(sc: Scene, origin, direction, ignore_type=3, internal_reflection=1.0, t_min=f32(0.00001), t_max=INF):
-    """Returns (hit?, record) with record = dict(t, point, normal, index)."""
+def grid_hit(sc: Scene, origin, direction, ignore_type=3, internal_reflection=1.0, t_min=f32(0.00001), t_max=INF, select=None, brick_select=None, entry_select=None):
+    """Returns (hit?, record) with record = dict(t, point, normal, index).  select / brick_select: the min-axis choice of the grid walk and
+    of the brick walks (see _dda_step), entry_select: the slab entry's axis (see adv_norm_intersect); None: the shader's own."""
     origin = [f32(v) for v in origin]
     direction = [f32(v) for v in direction]
     hit = {"t": f32(0.0), "point": [f32(0.0)] * 3, "normal": [f32(0.0)] * 3, "index": 0}
     inv = [safe_inverse(d) for d in direction]
-    ok, hit["normal"], grid_t_min, grid_t_max = adv_norm_intersect(sc, origin, inv, f32(t_min), f32(t_max))
+    ok, hit["normal"], grid_t_min, grid_t_max = adv_norm_intersect(sc, origin, inv, f32(t_min), f32(t_max), entry_select)
     if not ok:
         return False, hit
     global_t = grid_t_min + f32(0.0001) * sc.scale
@@ -169,9 +176,9 @@ def grid_hit(sc: Scene, origin, direction, ignore_type=3, internal_reflection=1.
             brick_min = [fma(f32(pos[i]), sc.scale, sc.g_min[i]) for i in range(3)]
             global_t = t_value + grid_t_min + f32(0.01) * sc.scale
             hit["t"] = global_t
-            if brick_hit(sc, origin, direction, ignore_type, internal_reflection, grid_t_max, delta, step, int(sc.brick_index[cell]), brick_min, hit):
+            if brick_hit(sc, origin, direction, ignore_type, internal_reflection, grid_t_max, delta, step, int(sc.brick_index[cell]), brick_min, hit, brick_select):
                 return True, hit
-        t_value, hit["normal"] = _dda_step(side, delta, step, pos, sc.scale, normal_axis)
+        t_value, hit["normal"] = _dda_step(side, delta, step, pos, sc.scale, normal_axis, select)
     return False, hit
 
 
@@ -187,9 +194,9 @@ def normalize(v):
     return [c * inv for c in v]
 
 
-def pixel(sc: Scene, cam: dict, sun: dict, px: int, py: int):
+def pixel(sc: Scene, cam: dict, sun: dict, px: int, py: int, select=None, brick_select=None, entry_select=None):
     """cam: image_width, image_height, horizontal, vertical, lower_left_corner, origin (lists of float32), max_bounce;
-    sun: position, enabled, color.  Returns (rgb float32 list, rgba8 list)."""
+    sun: position, enabled, color.  Returns (rgb float32 list, rgba8 list).  select / brick_select / entry_select: passed to both rays' grid_hit."""
     u = f32(px) / f32(cam["image_width"] - 1)
     v = f32(py) / f32(cam["image_height"] - 1)
     ray_dir = [fma(cam["horizontal"][i], u, cam["lower_left_corner"][i]) + fma(v, cam["vertical"][i], -cam["origin"][i]) for i in range(3)]
@@ -198,7 +205,7 @@ def pixel(sc: Scene, cam: dict, sun: dict, px: int, py: int):
     color = [f32(0.0)] * 3
     loop_count = 0
     if cam["max_bounce"] > 0:
-        ok, hit = grid_hit(sc, origin, direction, 3, 1.0)
+        ok, hit = grid_hit(sc, origin, direction, 3, 1.0, select=select, brick_select=brick_select, entry_select=entry_select)
         if ok:
             loop_count = 1
             m = sc.materials[hit["index"]]
@@ -207,7 +214,7 @@ def pixel(sc: Scene, cam: dict, sun: dict, px: int, py: int):
                 loop_count = 0
             if sun_on:
                 shadow_dir = normalize([f32(sun["position"][i]) - hit["point"][i] for i in range(3)])
-                shadowed, _ = grid_hit(sc, hit["point"], shadow_dir, 3, 1.0)
+                shadowed, _ = grid_hit(sc, hit["point"], shadow_dir, 3, 1.0, select=select, brick_select=brick_select, entry_select=entry_select)
                 if not shadowed:
                     color = [color[i] + attenuation[i] * f32(sun["color"][i]) for i in range(3)]
             else:
