@@ -315,6 +315,8 @@ pub const SHAPE_BOX: u32 = 0;
 pub const SHAPE_SPHERE: u32 = 1;
 pub const SHAPE_MAX_RADIUS: i32 = 16384;
 pub const SHAPES_MAX: u32 = 4096;
+/// vrt_paint_shapes' `only`: paint every solid voxel of the shapes, whatever material it holds.
+pub const PAINT_ANY: u32 = 0xFFFFFFFF;
 pub const Shape = extern struct {
     lo: [3]i32,
     hi: [3]i32,
@@ -407,6 +409,8 @@ pub extern fn vrt_grid_fill_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c
 pub extern fn vrt_grid_clear_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_fill_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_clear_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;
+pub extern fn vrt_paint_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64, only: u32, painted: [*c]u64) c_int;
+pub extern fn vrt_grid_paint_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64, only: u32, painted: [*c]u64) c_int;
 pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_derived_size(ctx: ?*const Ctx, id: DerivedId) u64;

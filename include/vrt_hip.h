@@ -725,6 +725,37 @@ int vrt_grid_clear_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n);
 /* on the scene the context holds; shapes in host memory */
 int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n);
 int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n);
+/* ---- Paint edits on the uploaded scene: recolour the solid voxels inside boxes and spheres -----------------------------------
+ * The brush that changes material and no geometry (one more mode of the vrt_edit_* kernels).  SHAPES: coordinates, clipping, sphere
+ * membership, VRT_SHAPES_MAX and VRT_SHAPE_MAX_RADIUS are exactly those of vrt_fill_shapes; vrt_shape.material is the new material,
+ * 0..255, screened as for a fill.
+ *
+ * A voxel is PAINTED when all of these hold: it is solid as it was before the call (its cell's status bit is 1 and its occupancy bit
+ * is 1; the status bit is tested first: brick_indices of a cell that is not loaded may be stale); it lies in at least one shape of the
+ * batch; and only == VRT_PAINT_ANY, or its material_indices entry AS IT WAS BEFORE THE CALL equals only.  THE FILTER IS PER CALL AND
+ * TESTS THE SCENE BEFORE THE CALL: it does not test the result of earlier shapes of the same batch, so a batch is not the sequence of
+ * its one-shape calls.  The entry of a painted voxel, material_indices[(brick_start_indices[brick] & 0x7FFFFFFF) + nth_bit], becomes
+ * the material of the LAST shape of the array that holds the voxel.  Nothing else is written: no entry of an empty voxel (unlike a
+ * fill), nothing of a cell that is not loaded, no byte of bindings 2-5.  *painted (may be NULL): the number of distinct painted voxels;
+ * a voxel whose entry already held the new value counts, and its entry counts as written.
+ *
+ * On a context whose bindings 2-6 equal a vrt_grid's arrays, after vrt_paint_shapes they equal that grid's arrays after
+ * vrt_grid_paint_shapes with the same arguments, byte for byte, and painted is equal.  The host twin registers, for material_indices
+ * alone, [first entry written, last entry written + 1), merged into an active delta; no delta when nothing was painted.
+ *
+ * ERRORS, all or nothing, on the twin too.  VRT_E_INVALID_ARG: a NULL ctx or grid; NULL shapes with n > 0; n > VRT_SHAPES_MAX; an
+ * unknown kind; a material above 255; a sphere refused as a fill refuses it; only neither VRT_PAINT_ANY nor 0..255.
+ * VRT_E_OUT_OF_RANGE: the batch's work items would reach 2^31, as for a fill.  VRT_E_STATE as for vrt_clear_shapes.  Never VRT_E_OOM.
+ * n == 0, or every shape empty after clipping: VRT_OK, *painted = 0, and the device is not touched.  *painted is written on VRT_OK only.
+ *
+ * ORDERING AND STAGING as for vrt_fill_shapes: one scene write on the context's stream, one small status read-back ends the call and
+ * carries painted; the derived structures are refreshed for the written range of binding 6, only when something was written, so
+ * vrt_get_voxels, frames and ray queries right after the call see the paint without a vrt_wait.  No _device form, for the fill's reason. */
+#define VRT_PAINT_ANY 0xFFFFFFFFu
+/* on the scene the context holds; shapes in host memory */
+int vrt_paint_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted /* may be NULL */);
+/* the CPU twin on a host grid */
+int vrt_grid_paint_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted /* may be NULL */);
 /* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);

@@ -185,6 +185,7 @@ class Shape(C.Structure):  # vrt_shape (32 bytes)
 SHAPE_BOX, SHAPE_SPHERE = 0, 1  # VRT_SHAPE_BOX, VRT_SHAPE_SPHERE
 SHAPE_MAX_RADIUS = 16384        # VRT_SHAPE_MAX_RADIUS
 SHAPES_MAX = 4096               # VRT_SHAPES_MAX
+PAINT_ANY = 0xFFFFFFFF          # VRT_PAINT_ANY
 RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
 VOXEL_EMPTY = 0xFFFF        # VRT_VOXEL_EMPTY
 
@@ -292,6 +293,8 @@ SIGNATURES = {
     "vrt_grid_clear_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
     "vrt_fill_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
     "vrt_clear_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
+    "vrt_paint_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_uint32, _P(C.c_uint64)]),
+    "vrt_grid_paint_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_uint32, _P(C.c_uint64)]),
     "vrt_camera_pixel_ray": (C.c_int, [_P(CameraDevice), C.c_uint32, C.c_uint32, _P(C.c_float * 3), _P(C.c_float * 3)]),
     "vrt_camera_init": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, _P(CameraConfig), _P(CameraDevice)]),
     "vrt_camera_set_forward": (C.c_int, [_P(CameraDevice), C.c_float, C.c_float, _P(C.c_float * 3)]),

@@ -446,6 +446,59 @@ int BrickGrid::clearShapes(const vrt_shape *shapes, uint64_t n) {
     return VRT_OK;
 }
 
+int BrickGrid::paintShapes(const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted) {
+    const vrt_grid_state &d = device_state_;
+    const uint32_t b = brick_dimension_;
+    if (only != VRT_PAINT_ANY && only > 255u) return VRT_E_INVALID_ARG;
+    std::vector<ClippedShape> clipped;
+    int rc = clip_batch(shapes, n, true, d, &clipped); // (the material is screened as a fill's)
+    if (rc != VRT_OK) return rc;
+    uint64_t items = 0; // the device's bound on a batch, so that the twin refuses what the device refuses
+    for (const ClippedShape &s : clipped)
+        if ((items += shape_items(s, b)) >= kShapeItemsEnd) return VRT_E_OUT_OF_RANGE;
+    uint8_t rows[64];
+    // first pass, no write: the entries of the solid voxels of every shape that pass the filter, in the order of the shapes; so the
+    // filter sees every entry as it was before the call
+    struct Write {
+        size_t entry;
+        uint8_t material;
+    };
+    std::vector<Write> writes;
+    for (const ClippedShape &s : clipped)
+        for_cells(s, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (!((brick_statuses[g / 32] >> (g % 32)) & 1u)) return; // not loaded: brick_indices[g] may be stale and is not read
+            if (!shapeRows(s, cx, cy, cz, rows)) return;
+            const uint32_t brick = brick_indices[g];
+            if (brick >= brick_alloc_ || brick_start_indices[brick] == 0xFFFFFFFFu) {
+                rc = VRT_E_STATE;
+                return;
+            }
+            const size_t occupancy_from = (size_t)brick * brick_bytes_, start = brick_start_indices[brick] & 0x7FFFFFFFu;
+            for (uint32_t r = 0; r < b * b; r++) {
+                const uint32_t bit = r * b; // the row's first voxel within the brick
+                const uint32_t solid = (brick_occupancy[occupancy_from + bit / 8] >> (bit % 8)) & rows[r];
+                for (uint32_t k = 0; k < b; k++)
+                    if (((solid >> k) & 1u) && (only == VRT_PAINT_ANY || material_indices[start + bit + k] == only))
+                        writes.push_back({start + bit + k, (uint8_t)s.material});
+            }
+        });
+    if (rc != VRT_OK) return rc;
+    // second pass: in the order of the shapes, so the last shape that holds a voxel gives it its material
+    size_t first = std::numeric_limits<size_t>::max(), last = 0;
+    for (const Write &w : writes) {
+        material_indices[w.entry] = w.material;
+        first = std::min(first, w.entry), last = std::max(last, w.entry);
+    }
+    if (!writes.empty()) material_indices_delta.registerDeltaRange(first, last);
+    if (painted) { // the distinct voxels: a voxel that several shapes hold came up once for each
+        std::vector<size_t> entries(writes.size());
+        for (size_t i = 0; i < writes.size(); i++) entries[i] = writes[i].entry;
+        std::sort(entries.begin(), entries.end());
+        *painted = (uint64_t)(std::unique(entries.begin(), entries.end()) - entries.begin());
+    }
+    return VRT_OK;
+}
+
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {
     switch (id) {
         case VRT_BUF_BRICK_STATUS: return &brick_statuses_delta;

@@ -88,6 +88,12 @@ public:
     // bricks it needs first (VRT_E_OOM; VRT_E_STATE for a loaded cell whose brick has no material entries).  Single-threaded.
     int fillShapes(const vrt_shape *shapes, uint64_t n);
     int clearShapes(const vrt_shape *shapes, uint64_t n);
+    // A paint: the material entry of every solid voxel (status bit, then occupancy bit, as the volume queries test) that lies in a shape
+    // and whose entry, AS IT WAS BEFORE THE CALL, equals `only` (VRT_PAINT_ANY: any entry) becomes the material of the last shape that
+    // holds the voxel.  No other byte is written.  *painted (may be null): the distinct voxels painted.  Refusals as fillShapes', without
+    // VRT_E_OOM; VRT_E_INVALID_ARG for an `only` that is neither VRT_PAINT_ANY nor 0..255; VRT_E_OUT_OF_RANGE for a batch whose work items
+    // on the device would reach 2^31.  Delta: material_indices from the first to the last entry written; none where nothing was painted.
+    int paintShapes(const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted);
 
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }

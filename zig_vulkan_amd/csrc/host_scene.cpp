@@ -282,6 +282,11 @@ int vrt_grid_clear_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {
     return reinterpret_cast<vrt::BrickGrid *>(g)->clearShapes(shapes, n);
 }
 
+int vrt_grid_paint_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->paintShapes(shapes, n, only, painted);
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

@@ -57,6 +57,25 @@
 //                         whole words of four and whole runs of 32 at once; the first item of a new cell writes the cell's words.
 //                         clear: phase 0 one atomicAnd of ~mask, phase 1 as for removals
 //   vrt_edit_finish
+//
+// A paint (vrt_paint_shapes) is the sixth mode, EditArgs::op = kEditOpPaint, on the work items of the shape edits.  It
+// writes binding 6 alone and needs no brick, no election and no last writer, so its chain is the shortest:
+//   vrt_edit_begin (+ the scan of binding 5, as above)
+//   vrt_edit_validate     per item: shape, cell, word, mask; a zero mask or a cell that is not loaded makes the item inert (the status
+//                         bit is tested before binding 3 is read); loaded cells: brick and the entry of the word's bit 0, as for a fill
+//   vrt_edit_write        keep = mask & the item's occupancy word & ~(the later shapes' masks); with a filter, the bits of keep whose
+//                         entry holds another material dropped; the material bytes of keep, stored as a fill stores them; popcount(keep)
+//                         summed into EditStatus::painted, one atomic per wave
+//   vrt_edit_finish
+// (vrt_edit_table is not launched: no cell's scratch word is touched.)
+//
+//   mode      op  validate  count scan_groups rank resolve  table  write       finish
+//   insert    0   x         x     x           x    x        x      x           x
+//   remove    1   x                                         x      phases 0, 1 x
+//   compact   2   x         x     x           x    x               phases 0, 1 x
+//   fill      3   x         x     x           x    x        x      x           x
+//   clear     4   x                                         x      phases 0, 1 x
+//   paint     5   x                                                x           x
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -71,7 +90,7 @@ namespace vrt {
 constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
-constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4; // EditArgs::op
+constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4, kEditOpPaint = 5; // EditArgs::op
 constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
@@ -104,6 +123,7 @@ struct EditStatus {
                                 // compaction: renamed (binding 3 only)
     uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit; removal: that lost one; compaction: first hole to the end of brick A - 1
     uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
+    uint64_t painted;           // paint: the voxels painted
 };
 
 // One shape of a fill or clear batch as the kernels read it (64 bytes): ClippedShape (y flipped; index 0 = x, 1 = flipped y, 2 = z),
@@ -134,7 +154,7 @@ struct EditArgs {
     uint32_t n;
     uint32_t groups;         // ceil(n / kEditBlock)
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
-    uint32_t op;             // kEditOpInsert / kEditOpRemove / kEditOpCompact / kEditOpFill / kEditOpClear (uniform: every kernel of a chain sees the same)
+    uint32_t op;             // kEditOpInsert / kEditOpRemove / kEditOpCompact / kEditOpFill / kEditOpClear / kEditOpPaint (uniform: every kernel of a chain sees the same)
     uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks;
                              // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells
     // scratch (the context's, grown on demand)
@@ -156,6 +176,7 @@ struct EditArgs {
     uint32_t start_words;           // entries of binding 5 scanned by vrt_edit_scan_start (= brick_alloc)
     uint64_t material_entries;      // bytes of binding 6 (brick_alloc * B^3)
     uint32_t cells;                 // compaction: cells of the grid (n = max(cells, brick_alloc): the threads of its per-cell kernels)
+    uint32_t only;                  // paint: the material an entry must hold to be painted (VRT_PAINT_ANY: whatever it holds)
 };
 
 } // namespace vrt
@@ -326,6 +347,7 @@ __global__ void __launch_bounds__(64) vrt_edit_begin(EditArgs a) {
     s.cell_lo = kEditNone, s.cell_hi = 0;
     s.occ_lo = kEditNone, s.occ_hi = 0;
     s.mat_lo = kEditNone, s.mat_hi = 0;
+    s.painted = 0;
     *a.out = s;
     if (a.rescan) {
         a.state->first_unset = kEditNone;
@@ -386,10 +408,10 @@ __device__ inline void compact_validate(const EditArgs &a) {
     wave_atomic_or(&a.out->err, err);
 }
 
-// a fill's or a clear's items (every lane gets to the reduction)
+// a fill's, a clear's or a paint's items (every lane gets to the reduction)
 __device__ inline void shape_validate(const EditArgs &a) {
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
-    const bool ok = a.state->ok != 0, fill = a.op == kEditOpFill;
+    const bool ok = a.state->ok != 0, fill = a.op == kEditOpFill, clear = a.op == kEditOpClear;
     const uint32_t bricks = a.state->bricks;
     uint32_t cell = kEditNone, info = 0, err = 0;
     if (i < a.n && ok) {
@@ -405,7 +427,7 @@ __device__ inline void shape_validate(const EditArgs &a) {
                     err = kEditErrCell;
                 } else {
                     a.vbrick[i] = brick;
-                    if (fill) {
+                    if (!clear) {
                         a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + first_bit; // the entry of binding 6 of the word's bit 0
                     } else {
                         a.vslot[i] = mask;               // (a clear writes no entry of binding 6: the word holds the mask for phase 0)
@@ -414,7 +436,7 @@ __device__ inline void shape_validate(const EditArgs &a) {
                     cell = g;
                     info = first_bit;
                 }
-            } else if (fill) { // (a clear of a cell that is not loaded: a no-op)
+            } else if (fill) { // (a clear or a paint of a cell that is not loaded: a no-op; binding 3 may be stale there and is not read)
                 atomicMin(&a.cell_first[g], i); // the minimum ranks the new cells shape-major, then by cell index
                 cell = g;
                 info = 0x80000000u | first_bit;
@@ -434,7 +456,7 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
         compact_validate(a);
         return;
     }
-    if (a.op == kEditOpFill || a.op == kEditOpClear) {
+    if (a.op >= kEditOpFill) { // fill, clear, paint
         shape_validate(a);
         return;
     }
@@ -670,6 +692,28 @@ __device__ inline void compact_write(const EditArgs &a) {
     wave_atomic_max(&a.out->cell_hi, hi);
 }
 
+// `material` into the entries of binding 6 that `keep` names, bit k = entries[k], entries = binding 6 + slot (slot + 31 lies within the
+// brick's B^3 entries): a whole run of 32 on a 16-byte aligned slot as two 16-byte stores, otherwise a whole nibble on a 4-byte aligned
+// slot as one dword, the rest as bytes
+__device__ inline void store_materials(uint8_t *entries, uint32_t slot, uint32_t keep, uint32_t material) {
+    const uint32_t four = material * 0x01010101u;
+    if (keep == 0xFFFFFFFFu && !(slot & 15u)) {
+        reinterpret_cast<uint4 *>(entries)[0] = make_uint4(four, four, four, four);
+        reinterpret_cast<uint4 *>(entries)[1] = make_uint4(four, four, four, four);
+        return;
+    }
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (uint32_t k = 0; k < 32u; k += 4u) {
+        const uint32_t nibble = (keep >> k) & 15u;
+        if (nibble == 15u && !(slot & 3u)) {
+            *reinterpret_cast<uint32_t *>(entries + k) = four;
+        } else {
+            for (uint32_t j = 0; j < 4u; j++)
+                if ((nibble >> j) & 1u) entries[k + j] = (uint8_t)material;
+        }
+    }
+}
+
 // a fill's items (every lane of the wave gets to the three pairs of reductions).  The loop over the later shapes comes first, with little
 // else alive, and what follows it reads the item's words again: so the kernel stays within its 32 VGPRs.
 __device__ inline void fill_write(const EditArgs &a) {
@@ -707,31 +751,61 @@ __device__ inline void fill_write(const EditArgs &a) {
     wave_atomic_max(&a.out->occ_hi, hi);
     lo = kEditNone, hi = 0;
     if (keep) {
-        const uint32_t slot = a.vslot[i], four = material * 0x01010101u;
-        uint8_t *entries = a.material + slot; // (slot + 31 lies within the brick's B^3 entries)
-        if (keep == 0xFFFFFFFFu && !(slot & 15u)) { // a whole run of 32 entries
-            reinterpret_cast<uint4 *>(entries)[0] = make_uint4(four, four, four, four);
-            reinterpret_cast<uint4 *>(entries)[1] = make_uint4(four, four, four, four);
-        } else {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (uint32_t k = 0; k < 32u; k += 4u) {
-                const uint32_t nibble = (keep >> k) & 15u;
-                if (nibble == 15u && !(slot & 3u)) { // four entries at once
-                    *reinterpret_cast<uint32_t *>(entries + k) = four;
-                } else {
-                    for (uint32_t j = 0; j < 4u; j++)
-                        if ((nibble >> j) & 1u) entries[k + j] = (uint8_t)material;
-                }
-            }
-        }
+        const uint32_t slot = a.vslot[i];
+        store_materials(a.material + slot, slot, keep, material);
         lo = slot + (uint32_t)__builtin_ctz(keep), hi = slot + 31u - (uint32_t)__builtin_clz(keep);
     }
     wave_atomic_min(&a.out->mat_lo, lo);
     wave_atomic_max(&a.out->mat_hi, hi);
 }
 
+// a paint's items (every lane of the wave gets to the reductions).  keep: the item's voxels that are solid and that no later shape of
+// the batch covers, so no two items write one entry, and an entry's old byte is read by the one item that may write it: the filter sees
+// the scene as it was before the call.  (An item may load a dword of which another item writes other bytes: those it does not test.)
+__device__ inline void paint_write(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    uint32_t keep = 0, material = 0;
+    if (i < a.n && a.vcell[i] != kEditNone) {
+        const ShapeItem it = shape_item(a, i);
+        const ShapeRec &r = shape_rec(a, it.shape);
+        keep = shape_mask(r, a.b, it) & a.occupancy[a.vbrick[i] * (a.brick_bytes >> 2) + it.word]; // (the cell is loaded: validated)
+        material = r.material;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (uint32_t t = it.shape + 1u; t < a.shape_count && keep; t++) keep &= ~shape_mask(shape_rec(a, t), a.b, it);
+    }
+    uint32_t lo = kEditNone, hi = 0;
+    if (keep && a.only != VRT_PAINT_ANY) { // the filter: a bit of keep whose old entry differs from `only` goes, four entries at once
+        const uint32_t slot = a.vslot[i], only4 = a.only * 0x01010101u;
+        const uint8_t *entries = a.material + slot; // (slot + 31 lies within the brick's B^3 entries)
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (uint32_t k = 0; k < 32u; k += 4u) {
+            if (!((keep >> k) & 15u)) continue;
+            uint32_t old;
+            if (!(slot & 3u)) old = *reinterpret_cast<const uint32_t *>(entries + k);
+            else old = entries[k] | (uint32_t)entries[k + 1u] << 8 | (uint32_t)entries[k + 2u] << 16 | (uint32_t)entries[k + 3u] << 24;
+            old ^= only4;
+            for (uint32_t j = 0; j < 4u; j++)
+                if ((old >> (8u * j)) & 0xFFu) keep &= ~(1u << (k + j));
+        }
+    }
+    if (keep) {
+        const uint32_t slot = a.vslot[i];
+        store_materials(a.material + slot, slot, keep, material);
+        lo = slot + (uint32_t)__builtin_ctz(keep), hi = slot + 31u - (uint32_t)__builtin_clz(keep);
+    }
+    wave_atomic_min(&a.out->mat_lo, lo);
+    wave_atomic_max(&a.out->mat_hi, hi);
+    uint32_t count = (uint32_t)__popc(keep);
+    for (int o = 32; o > 0; o >>= 1) count += (uint32_t)__shfl_xor((int)count, o);
+    if (lane_id() == 0 && count) atomicAdd(reinterpret_cast<unsigned long long *>(&a.out->painted), (unsigned long long)count);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     if (a.out->err) return;
+    if (a.op == kEditOpPaint) {
+        paint_write(a);
+        return;
+    }
     if (a.op == kEditOpRemove || a.op == kEditOpClear) {
         remove_write(a);
         return;
@@ -942,7 +1016,7 @@ struct EditStep {
 };
 using EditSteps = std::vector<EditStep>;
 
-// The chains of the five ops (the header comment of this file says what each kernel does in each).  Inserts and fills over the g
+// The chains of the six ops (the header comment of this file says what each kernel does in each).  Inserts and fills over the g
 // workgroups of the batch's voxels or items:
 EditSteps insert_steps(uint32_t g) {
     return {{vrt_edit_validate, g}, {vrt_edit_count, g}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, g},
@@ -952,6 +1026,8 @@ EditSteps insert_steps(uint32_t g) {
 EditSteps remove_steps(uint32_t g) {
     return {{vrt_edit_validate, g}, {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
 }
+// ... a paint:
+EditSteps paint_steps(uint32_t g) { return {{vrt_edit_validate, g}, {vrt_edit_write, g}}; }
 // ... compaction: over the cells (and bricks), over the bricks (also what vrt_edit_scan_groups scans), and its grid-stride passes
 EditSteps compact_steps(uint32_t cells, uint32_t bricks, uint32_t copy) {
     return {{vrt_edit_validate, cells}, {vrt_edit_count, bricks}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, bricks},
@@ -998,6 +1074,7 @@ constexpr uint32_t kErrsOfRemove = vrt::kEditErrShape | vrt::kEditErrRange | vrt
 constexpr uint32_t kErrsOfCompact = vrt::kEditErrShape | vrt::kEditErrSlot | vrt::kEditErrCell;
 constexpr uint32_t kErrsOfFill = vrt::kEditErrShape | vrt::kEditErrCell | vrt::kEditErrOom;
 constexpr uint32_t kErrsOfClear = vrt::kEditErrShape | vrt::kEditErrCell;
+constexpr uint32_t kErrsOfPaint = kErrsOfClear;
 
 // The derived structures follow exactly what was written (refresh_derived, before the next frame or query): the status ranges of the
 // buffers the op writes (`writes`: a bit per vrt_buffer_id), marked dirty.  start_first: the first of the s.new_bricks entries of
@@ -1006,6 +1083,7 @@ constexpr uint32_t buf_bit(vrt_buffer_id id) { return 1u << id; }
 constexpr uint32_t kWritesOfRemove = buf_bit(VRT_BUF_BRICK_STATUS) | buf_bit(VRT_BUF_BRICK_OCCUPANCY); // (a batch of no-ops: nothing)
 constexpr uint32_t kWritesOfInsert = kWritesOfRemove | buf_bit(VRT_BUF_BRICK_INDEX) | buf_bit(VRT_BUF_BRICK_START_INDEX) | buf_bit(VRT_BUF_MATERIAL_INDEX);
 constexpr uint32_t kWritesOfCompact = kWritesOfInsert & ~buf_bit(VRT_BUF_BRICK_STATUS);
+constexpr uint32_t kWritesOfPaint = buf_bit(VRT_BUF_MATERIAL_INDEX);
 void mark_written(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t writes, uint32_t start_first) {
     if (s.cell_lo <= s.cell_hi) {
         if (writes & buf_bit(VRT_BUF_BRICK_STATUS))
@@ -1071,18 +1149,24 @@ int compact(vrt_ctx *ctx, uint32_t out[2]) {
     return VRT_OK;
 }
 
-// n shapes (host memory) filled into or cleared from the scene: the batch screened and clipped on the host, one record per shape that
-// holds a voxel of the grid's range staged into device memory, then the fill's or the clear's part of the chain as one scene write
-int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
+// n shapes (host memory) filled into, cleared from or painted on the scene (op: kEditOpFill / kEditOpClear / kEditOpPaint): the batch
+// screened and clipped on the host, one record per shape that holds a voxel of the grid's range staged into device memory, then the
+// op's part of the chain as one scene write.  A paint: `only` is its filter, *painted (may be NULL) the voxels it painted.
+int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t op, uint32_t only = VRT_PAINT_ANY, uint64_t *painted = nullptr) {
     if (!ctx) return VRT_E_INVALID_ARG;
-    if (n == 0) return VRT_OK;
-    const char *nothing = fill ? "; nothing was filled" : "; nothing was cleared";
+    const bool fill = op == vrt::kEditOpFill, paint = op == vrt::kEditOpPaint;
+    const char *nothing = fill ? "; nothing was filled" : paint ? "; nothing was painted" : "; nothing was cleared";
+    if (only != VRT_PAINT_ANY && only > 255u) return fail(ctx, VRT_E_INVALID_ARG, std::string("only is neither VRT_PAINT_ANY nor a material 0..255") + nothing);
+    if (n == 0) {
+        if (painted) *painted = 0;
+        return VRT_OK;
+    }
     std::string why;
-    int rc = vrt::screen_shapes(shapes, n, fill, &why);
+    int rc = vrt::screen_shapes(shapes, n, fill || paint, &why); // (a paint's material is screened as a fill's)
     if (rc != VRT_OK) return fail(ctx, rc, why + nothing);
     if (ctx->dist) return fail(ctx, VRT_E_STATE, "shape edits are not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
-    const uint32_t b = ctx->cfg.brick_dimension, words = b * b * b / 32u;
+    const uint32_t b = ctx->cfg.brick_dimension;
     const uint32_t dim[3] = {ctx->cfg.dim_x * b, ctx->cfg.dim_y * b, ctx->cfg.dim_z * b};
     std::vector<vrt::ShapeRec> recs;
     uint64_t items = 0;
@@ -1099,12 +1183,15 @@ int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
         r.first = (uint32_t)items;
         r.ncx = (uint32_t)cells[0];
         r.ncxz = (uint32_t)(cells[0] * cells[2]); // (below the grid's cells, which fit 32 bits)
-        items += cells[0] * cells[1] * cells[2] * words; // (< 2^32 * 16 each, and the sum is tested before it can wrap: items < 2^31 so far)
-        if (items >= (1ull << 31))
+        items += vrt::shape_items(c, b); // (the sum is tested before it can wrap: items < 2^31 so far)
+        if (items >= vrt::kShapeItemsEnd)
             return fail(ctx, VRT_E_OUT_OF_RANGE, "shape " + std::to_string(i) + ": the batch's work items (one per occupancy word of every cell of every shape's clipped cell box) reach 2^31");
         recs.push_back(r);
     }
-    if (recs.empty()) return VRT_OK; // every shape empty after clipping: the device is not touched
+    if (recs.empty()) { // every shape empty after clipping: the device is not touched
+        if (painted) *painted = 0;
+        return VRT_OK;
+    }
     DeviceGuard dg(ctx->device);
     rc = edit_prepare(ctx, "shape edits are");
     if (rc != VRT_OK) return rc;
@@ -1112,14 +1199,16 @@ int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, bool fill) {
     rc = stage_input(ctx, recs.data(), recs.size() * sizeof(vrt::ShapeRec));
     if (rc == VRT_OK) rc = edit_scratch(ctx, items);
     if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, fill ? vrt::kEditOpFill : vrt::kEditOpClear, nullptr, nullptr, (uint32_t)items);
+    vrt::EditArgs a = edit_args(ctx, op, nullptr, nullptr, (uint32_t)items);
     a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
     a.shape_count = (uint32_t)recs.size();
+    a.only = only;
     vrt::EditStatus s;
-    rc = run_edit(ctx, a, fill ? insert_steps(a.groups) : remove_steps(a.groups), true, &s);
-    if (rc == VRT_OK) rc = edit_error(ctx, s, fill ? kErrsOfFill : kErrsOfClear, nothing);
+    rc = run_edit(ctx, a, fill ? insert_steps(a.groups) : paint ? paint_steps(a.groups) : remove_steps(a.groups), !paint, &s);
+    if (rc == VRT_OK) rc = edit_error(ctx, s, fill ? kErrsOfFill : paint ? kErrsOfPaint : kErrsOfClear, nothing);
     if (rc != VRT_OK) return rc;
-    mark_written(ctx, s, fill ? kWritesOfInsert : kWritesOfRemove, s.bricks - s.new_bricks);
+    mark_written(ctx, s, fill ? kWritesOfInsert : paint ? kWritesOfPaint : kWritesOfRemove, s.bricks - s.new_bricks);
+    if (painted) *painted = s.painted;
     return VRT_OK;
 }
 
@@ -1131,8 +1220,11 @@ int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *m
 int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, true); }
 int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, false); }
 int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, true); }
-int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, true); }
-int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, false); }
+int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, vrt::kEditOpFill); }
+int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, vrt::kEditOpClear); }
+int vrt_paint_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted) {
+    return edit_shapes(ctx, shapes, n, vrt::kEditOpPaint, only, painted);
+}
 
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     if (!ctx) return VRT_E_INVALID_ARG;

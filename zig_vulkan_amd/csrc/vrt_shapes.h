@@ -65,4 +65,13 @@ inline bool clip_shape(const vrt_shape &s, const uint32_t voxel_dim[3], ClippedS
     return true;
 }
 
+// The shape's work items on the device: one per 32-bit occupancy word of every cell of its clipped cell box (< 2^32 * 16).  A batch
+// whose items reach kShapeItemsEnd is refused, by the host twins of the edits that count them too.
+constexpr uint64_t kShapeItemsEnd = 1ull << 31;
+inline uint64_t shape_items(const ClippedShape &c, uint32_t b) {
+    uint64_t cells = 1;
+    for (int k = 0; k < 3; k++) cells *= (uint64_t)(c.hi[k] / b) - c.lo[k] / b + 1u;
+    return cells * (b * b * b / 32u);
+}
+
 } // namespace vrt

@@ -100,6 +100,15 @@ class BrickGrid:
         s = shape_records(shapes)
         check(lib.vrt_grid_clear_shapes(self._h, s.ctypes.data, s.shape[0]))
 
+    def paint_shapes(self, shapes, only=None) -> int:
+        """vrt_grid_paint_shapes: every solid voxel inside a shape takes the material of the last shape that holds it; no voxel appears
+        or goes.  only: paint only the voxels whose material before the call is `only` (None: every solid voxel).  Returns the number of
+        voxels painted."""
+        s = shape_records(shapes)
+        painted = C.c_uint64(0)
+        check(lib.vrt_grid_paint_shapes(self._h, s.ctypes.data, s.shape[0], L.PAINT_ANY if only is None else only, C.byref(painted)))
+        return int(painted.value)
+
     def get_voxels(self, xyz) -> np.ndarray:
         """vrt_grid_get_voxels: the material entry (0..255) of each voxel of xyz (n, 3), as insert_many takes it, or VOXEL_EMPTY where the
         voxel is not solid or lies outside the grid; (n,) uint16."""
@@ -495,6 +504,14 @@ class VoxelRT:
         """BrickGrid.clear_shapes on the scene the context holds (vrt_clear_shapes): the shapes' voxels removed; material must be 0."""
         s = shape_records(shapes)
         self._check(self._lib.vrt_clear_shapes(self._h, s.ctypes.data, s.shape[0]))
+
+    def paint_shapes(self, shapes, only=None) -> int:
+        """BrickGrid.paint_shapes on the scene the context holds (vrt_paint_shapes): the solid voxels inside the shapes recoloured, no
+        geometry changed; only: the material a voxel must hold before the call (None: any).  Returns the number of voxels painted."""
+        s = shape_records(shapes)
+        painted = C.c_uint64(0)
+        self._check(self._lib.vrt_paint_shapes(self._h, s.ctypes.data, s.shape[0], L.PAINT_ANY if only is None else only, C.byref(painted)))
+        return int(painted.value)
 
     def compact_bricks(self) -> Tuple[int, int]:
         """BrickGrid.compact on the scene the context holds (vrt_compact_bricks): bindings 2-6 afterwards equal the host grid's arrays
