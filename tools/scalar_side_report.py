@@ -8,7 +8,8 @@
 A loop body is every basic block that lies on a cycle of the kernel's control-flow graph (built from the branch instructions); the
 hand-written walk loops are such cycles like the compiler's own.  (Not "everything between a backward branch and its target": the
 compiler lays the kernel's exit block out early, and the branches back to it from the kernel's end would make the whole kernel a loop.)
-usage: scalar_side_report.py [--json] [--all] [libvrt_hip.so]      (default: the four one-sample kernels; --all: every kernel)"""
+usage: scalar_side_report.py [--json] [--all] [libvrt_hip.so]      (default: the four one-sample kernels; --all: every kernel)
+       scalar_side_report.py --compare <parent's libvrt_hip.so> <libvrt_hip.so>      (which kernels differ, instruction for instruction)"""
 import json
 import os
 import re
@@ -171,8 +172,44 @@ def report(lib=DEFAULT_LIB, every=False):
     return out
 
 
+def _instructions(lib):
+    """{kernel symbol: [(mnemonic, operands)]} of every kernel of `lib`."""
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name in _code_objects(lib, d):
+            notes = _notes(d, name)
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", name], cwd=d, check=True, capture_output=True, text=True).stdout
+            kernel = None
+            for line in dis.splitlines():
+                m = re.match(r"^[0-9a-fA-F]+ <(\S+)>:$", line)
+                if m:
+                    kernel = m.group(1) if m.group(1) in notes else None
+                    if kernel:
+                        out[kernel] = []
+                    continue
+                m = _INSN.match(line)
+                if m and kernel:
+                    out[kernel].append((m.group(1), m.group(2)))
+    return out
+
+
+def compare(parent, new):
+    """Which kernels of two builds differ, instruction for instruction (a change meant for some kernels must leave the others' code alone)."""
+    a, b = _instructions(parent), _instructions(new)
+    differ = sorted(k for k in a if k in b and a[k] != b[k])
+    print("# every kernel of libvrt_hip.so, the parent commit's build against this one: mnemonics and operands of every instruction (llvm-objdump -d)")
+    print(f"{len(a)} kernels in the parent's library, {len(b)} in this one; identical instruction for instruction: "
+          f"{sum(1 for k in a if k in b and a[k] == b[k])}; different: {len(differ)}")
+    for k in differ:
+        print(f"  differs: {k} {len(a[k])} -> {len(b[k])} instructions")
+    for k in sorted(set(a) ^ set(b)):
+        print(f"  only in {'the parent' if k in a else 'this one'}: {k}")
+
+
 def main(argv):
     args = [a for a in argv if not a.startswith("--")]
+    if "--compare" in argv:
+        return compare(os.path.abspath(args[0]), os.path.abspath(args[1]))
     rep = report(os.path.abspath(args[0]) if args else DEFAULT_LIB, every="--all" in argv)
     if "--json" in argv:
         print(json.dumps(rep, indent=1, sort_keys=True))

@@ -1038,7 +1038,7 @@ VRT_DI bool box_miss(const f3 &origin, const f3 &inv_dir, const int (&bounds)[6]
 struct BrickConsts {
     BrickArgs a;                   // the round's pointers (cell_box nullptr: the context holds none)
     uint32_t occupancy_words;      // TraceParams::occupancy_words
-    uint32_t start_is_slot;        // *TraceParams::start_is_slot (0: no flag, or the flag says no)
+    uint32_t start_is_slot;        // DerivedWords::start_is_slot: kFlagStartIsSlot | kFlagMaterialsPlain (a bit is 0: no flag, or the flag says no)
     uint32_t scale_pow2;           // TraceParams::scale_pow2, as a scalar the round tests by s_cmp (not as a lane mask: two registers)
     float inv_voxel_scale;         // TraceParams::inv_voxel_scale
 };
@@ -1073,17 +1073,21 @@ VRT_DI unsigned long long kernarg_address() { return (unsigned long long)__built
 struct DerivedPtrs {
     const int *cell_bounds;
     const uint32_t *start_is_slot;
+    const uint32_t *materials_plain; // (the plain TraceParams field: GridExtra has no dword to spare)
     uint32_t skip_to_box;
 };
 VRT_DI TileArgs kernarg_tile_args(DerivedPtrs &dp) {
     u32x16 v;
-    u32x2 b, f;
-    asm volatile("s_load_dwordx16 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\ts_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(v), "=&s"(b), "=&s"(f), "=&s"(dp.skip_to_box)
+    u32x2 b, f, m;
+    asm volatile("s_load_dwordx16 %0, %5, %6\n\ts_load_dwordx2 %1, %5, %7\n\ts_load_dwordx2 %2, %5, %8\n\ts_load_dword %3, %5, %9\n\ts_load_dwordx2 %4, %5, %10\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v), "=&s"(b), "=&s"(f), "=&s"(dp.skip_to_box), "=&s"(m)
                  : "s"(kernarg_address()), "n"(offsetof(TraceParams, tile_args)), "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, cell_bounds)),
-                   "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, start_is_slot)), "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, skip_to_box)));
+                   "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, start_is_slot)), "n"(offsetof(TraceParams, grid_extra) + offsetof(GridExtra, skip_to_box)),
+                   "n"(offsetof(TraceParams, materials_plain)));
     dp.cell_bounds = (const int *)__builtin_bit_cast(unsigned long long, b);
     dp.start_is_slot = (const uint32_t *)__builtin_bit_cast(unsigned long long, f);
+    dp.materials_plain = (const uint32_t *)__builtin_bit_cast(unsigned long long, m);
     return __builtin_bit_cast(TileArgs, v);
 }
 // the camera of frame `frame` of the launch (24 dwords, for ray generation: kernarg_camera_box) and its sun (8 dwords: fetched behind the
@@ -1092,10 +1096,19 @@ VRT_DI TileArgs kernarg_tile_args(DerivedPtrs &dp) {
 // the box of the occupied cells and the flag word (DerivedWords), read from the DEVICE's words — which the builders of the derived
 // structures keep current behind every upload and every edit on the GPU; a host copy could be stale — with the grid's origin and cell
 // size: what box_miss needs, and what the primary grid_hit then takes instead of fetching the words itself
+// (start_is_slot is a word of flags: bit 0 = *TraceParams::start_is_slot says yes, bit 1 = *TraceParams::materials_plain does — no
+// material record has the type MAT_NONE, the only type a ray made by create_ray ignores, so that comp:427 is false for every voxel and
+// a brick round needs no material; a context without a flag has its bit clear)
+constexpr uint32_t kFlagStartIsSlot = 1u, kFlagMaterialsPlain = 2u;
 struct DerivedWords {
     int bounds[6];
     uint32_t start_is_slot;
 };
+VRT_DI uint32_t derived_flags(const uint32_t *start_is_slot, uint32_t slot_word, const uint32_t *materials_plain, uint32_t plain_word) {
+    // (the builders leave 1 or 0 in a flag word; bit arithmetic on the scalar unit, no lane masks)
+    const uint32_t slot = start_is_slot ? slot_word : 0u, plain = materials_plain ? plain_word : 0u;
+    return (slot & 1u) | ((plain & 1u) << 1);
+}
 struct EarlyBox {
     DerivedWords dw;
     float g_min[3], g_scale;
@@ -1107,16 +1120,17 @@ VRT_DI vrt_camera_device kernarg_camera_box(uint32_t frame, const DerivedPtrs &d
     struct Parts { u32x16 a; u32x8 b; } v;
     u32x4 lo, gm;
     u32x2 hi;
-    uint32_t flag, sc;
+    uint32_t flag, sc, plain;
     const unsigned long long ka = kernarg_address();
     const unsigned long long at = ka + offsetof(TraceParams, pcs) + (unsigned long long)frame * sizeof(PushConstants);
     const unsigned long long b = dp.cell_bounds ? (unsigned long long)dp.cell_bounds : ka, f = dp.start_is_slot ? (unsigned long long)dp.start_is_slot : ka;
-    asm volatile("s_load_dwordx16 %0, %7, 0x0\n\ts_load_dwordx8 %1, %7, 0x40\n\ts_load_dwordx4 %2, %8, 0x0\n\ts_load_dwordx2 %3, %8, 0x10\n\t"
-                 "s_load_dword %4, %9, 0x0\n\ts_load_dwordx4 %5, %10, %11\n\ts_load_dword %6, %10, %12\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(v.a), "=&s"(v.b), "=&s"(lo), "=&s"(hi), "=&s"(flag), "=&s"(gm), "=&s"(sc)
+    const unsigned long long m = dp.materials_plain ? (unsigned long long)dp.materials_plain : ka;
+    asm volatile("s_load_dwordx16 %0, %8, 0x0\n\ts_load_dwordx8 %1, %8, 0x40\n\ts_load_dwordx4 %2, %9, 0x0\n\ts_load_dwordx2 %3, %9, 0x10\n\t"
+                 "s_load_dword %4, %10, 0x0\n\ts_load_dwordx4 %5, %11, %12\n\ts_load_dword %6, %11, %13\n\ts_load_dword %7, %14, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v.a), "=&s"(v.b), "=&s"(lo), "=&s"(hi), "=&s"(flag), "=&s"(gm), "=&s"(sc), "=&s"(plain)
                  : "s"(at), "s"(b), "s"(f), "s"(ka), "n"(offsetof(TraceParams, grid) + offsetof(vrt_grid_state, min_point_base_t)),
-                   "n"(offsetof(TraceParams, grid) + offsetof(vrt_grid_state, max_point_scale) + 12));
-    eb.dw = DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, dp.start_is_slot ? flag : 0u};
+                   "n"(offsetof(TraceParams, grid) + offsetof(vrt_grid_state, max_point_scale) + 12), "s"(m));
+    eb.dw = DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, derived_flags(dp.start_is_slot, flag, dp.materials_plain, plain)};
     // (the elements as values first: a bit cast straight from `gm.y` reads element 0)
     const uint32_t gx = gm.x, gy = gm.y, gz = gm.z;
     eb.g_min[0] = __builtin_bit_cast(float, gx), eb.g_min[1] = __builtin_bit_cast(float, gy), eb.g_min[2] = __builtin_bit_cast(float, gz);
@@ -1146,27 +1160,31 @@ struct GridArgs {
 static_assert(sizeof(GridArgs) == sizeof(vrt_grid_state) + sizeof(GridExtra) && offsetof(GridArgs, cell_bounds) - 64 == offsetof(GridExtra, cell_bounds) &&
                   offsetof(GridArgs, start_is_slot) - 64 == offsetof(GridExtra, start_is_slot) && offsetof(GridArgs, count_box) - 64 == offsetof(GridExtra, count_box),
               "GridArgs = vrt_grid_state + GridExtra, field for field");
-VRT_DI GridArgs kernarg_grid_args() {
+// (materials_plain: the plain TraceParams field, in the same round trip — for scalar_derived_words, the shadow ray's flags)
+VRT_DI GridArgs kernarg_grid_args(const uint32_t *&materials_plain) {
     struct Parts { u32x16 grid; u32x8 a; u32x4 b; } v;
-    asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %3, %4\n\ts_load_dwordx4 %2, %3, %5\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(v.grid), "=&s"(v.a), "=&s"(v.b)
-                 : "s"(kernarg_address()), "n"(offsetof(TraceParams, grid_extra)), "n"(offsetof(TraceParams, grid_extra) + 32));
+    u32x2 m;
+    asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx8 %1, %4, %5\n\ts_load_dwordx4 %2, %4, %6\n\ts_load_dwordx2 %3, %4, %7\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(v.grid), "=&s"(v.a), "=&s"(v.b), "=&s"(m)
+                 : "s"(kernarg_address()), "n"(offsetof(TraceParams, grid_extra)), "n"(offsetof(TraceParams, grid_extra) + 32), "n"(offsetof(TraceParams, materials_plain)));
+    materials_plain = (const uint32_t *)__builtin_bit_cast(unsigned long long, m);
     static_assert(sizeof(Parts) == sizeof(GridArgs) + 16 && offsetof(Parts, a) == 64 && offsetof(Parts, b) == 96, "x16 | x8 | x4, padded to the alignment of the first");
     struct Padded { GridArgs g; uint32_t pad[4]; };
     return __builtin_bit_cast(Padded, v).g;
 }
-// the box of the occupied cells (six ints behind TraceParams::cell_bounds) and the flag word behind start_is_slot, through the scalar
-// unit behind one wait; a null pointer reads the kernarg segment instead (any readable address) and its words are not used
-VRT_DI DerivedWords scalar_derived_words(const GridArgs &ga) {
+// the box of the occupied cells (six ints behind TraceParams::cell_bounds) and the flag words behind start_is_slot and materials_plain,
+// through the scalar unit behind one wait; a null pointer reads the kernarg segment instead (any readable address) and its words are not used
+VRT_DI DerivedWords scalar_derived_words(const GridArgs &ga, const uint32_t *materials_plain) {
     u32x4 lo;
     u32x2 hi;
-    uint32_t flag;
+    uint32_t flag, plain;
     const unsigned long long ka = kernarg_address();
     const unsigned long long b = ga.cell_bounds ? (unsigned long long)ga.cell_bounds : ka, f = ga.start_is_slot ? (unsigned long long)ga.start_is_slot : ka;
-    asm volatile("s_load_dwordx4 %0, %3, 0x0\n\ts_load_dwordx2 %1, %3, 0x10\n\ts_load_dword %2, %4, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(lo), "=&s"(hi), "=&s"(flag)
-                 : "s"(b), "s"(f));
-    return DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, ga.start_is_slot ? flag : 0u};
+    const unsigned long long m = materials_plain ? (unsigned long long)materials_plain : ka;
+    asm volatile("s_load_dwordx4 %0, %4, 0x0\n\ts_load_dwordx2 %1, %4, 0x10\n\ts_load_dword %2, %5, 0x0\n\ts_load_dword %3, %6, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(lo), "=&s"(hi), "=&s"(flag), "=&s"(plain)
+                 : "s"(b), "s"(f), "s"(m));
+    return DerivedWords{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}, derived_flags(ga.start_is_slot, flag, materials_plain, plain)};
 }
 VRT_DI BrickConsts kernarg_brick_consts(const GridArgs &ga, uint32_t start_is_slot) {
     u32x16 v;
@@ -1185,11 +1203,20 @@ VRT_DI int steps_left_fresh(int step, int pos, int dim, int zero_budget) {
 
 // CONSTS (the one-sample kernels, grid_hit<KARGS>): the round's uniform operands come from `bc`; otherwise the round reads `p` as it
 // always did — the other kernel families sit at the edge of their register budgets, and their code is left as it is.
-template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false, bool CONSTS = false>
+// PLAIN (with CONSTS; the ray is one create_ray made: it ignores MAT_NONE at refraction index 1.0): where the flags word says that no
+// material record has that type (kFlagMaterialsPlain) comp:427 is false whatever the voxel's material, and a lane that leaves the voxel walk
+// on a solid voxel has its hit without the round's two dependent look-ups, material_index[start + voxel] -> materials[mi] — with
+// the other lanes of the wave waiting for them.  kPlainHit: hit.index is then the POSITION in material_index, start + voxel, and the
+// caller looks the material up once the walk is over (grid_hit).  kPlainAnyHit: the caller only asks whether there is a hit (a shadow
+// ray); `hit` and hit_axis are not outputs.  Where the bit is clear — a scene with a MAT_NONE record, a context made without the
+// flag — the round is the one every other kernel runs, and hit.index is the material.
+constexpr int kPlainOff = 0, kPlainHit = 1, kPlainAnyHit = 2;
+template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false, bool CONSTS = false, int PLAIN = kPlainOff>
 VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min,
                               Hit &hit, int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u) {
     constexpr bool kConsts = CONSTS;
     static_assert(!(CONSTS && BY_CELL), "the by-cell copy is the bounce kernel's");
+    static_assert(PLAIN == kPlainOff || CONSTS, "the flags word is BrickConsts'");
     const float brick_voxel_scale = 1.0f / (float)B; // spec const 5, Pipeline.zig:313
     const float voxel_scale = g_scale * brick_voxel_scale;
     const bool pow2 = kConsts ? opaque_uniform(bc.scale_pow2) != 0u : p.scale_pow2 != 0u;
@@ -1211,6 +1238,10 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const
     uint32_t bit_index = base + ((uint32_t)px + (uint32_t)B * ((uint32_t)pz + (uint32_t)B * (uint32_t)py));
     const uint32_t stride_x = (uint32_t)s.sx, stride_y = (uint32_t)(s.sy * (B * B)), stride_z = (uint32_t)(s.sz * B);
     bool more = more_init(px, py, pz, B) && (0.0f <= local_t_max); // comp:409 with t_value = 0
+    // (CONSTS: the occupancy word requested with `more` as it stands in front of the reject test, so that the request does not wait for
+    // the test; a lane the test then rejects has asked for a word of its own brick that it does not use)
+    [[maybe_unused]] uint32_t early_word = 0u;
+    if constexpr (kConsts && REJECT) early_word = global_ptr(reinterpret_cast<const uint32_t *>(bc.a.brick_occupancy))[more ? (bit_index >> 5) : 0u];
     if constexpr (REJECT) {
         more = more && !brick_reject<B>(fposition, s.inv_dir, box);
         if (__builtin_amdgcn_ballot_w64(more) == 0ull) return false;
@@ -1226,14 +1257,16 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const
     rsrc.y = (uint32_t)(occ_addr >> 32) | (4u << 16);
     rsrc.z = by_cell ? p.status_cells * (uint32_t)(B * B * B / 32) : (kConsts ? bc.occupancy_words : p.occupancy_words);
     rsrc.w = 0x00020000u;
-    uint32_t word = global_ptr(reinterpret_cast<const uint32_t *>(occupancy))[more ? (bit_index >> 5) : 0u];
+    uint32_t word;
+    if constexpr (kConsts && REJECT) word = early_word;
+    else word = global_ptr(reinterpret_cast<const uint32_t *>(occupancy))[more ? (bit_index >> 5) : 0u];
     // comp:422.  EAGER: requested before the walk, so that a solid voxel's material test starts one dependent load later
     // (scenes that stay in the caches).  Otherwise requested at the first solid voxel: on a scene larger than the caches
     // every request is a 128-byte line from HBM, and four of five brick walks of the path-trace configuration end without
     // a solid voxel (K = 3.2 bricks entered, H = 0.7 hits per ray).
     uint32_t brick_material_index = 0u;
     bool start_is_slot; // (wave-uniform; kConsts: read once in front of the walk, BrickConsts)
-    if constexpr (kConsts) start_is_slot = opaque_uniform(bc.start_is_slot) != 0u;
+    if constexpr (kConsts) start_is_slot = (opaque_uniform(bc.start_is_slot) & kFlagStartIsSlot) != 0u;
     else start_is_slot = p.start_is_slot != nullptr && __builtin_amdgcn_readfirstlane((int)*p.start_is_slot) != 0;
     if constexpr (EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (global_ptr(a.brick_start_index)[brick_index] & 0x7FFFFFFFu);
     GridWalkRegs g;
@@ -1253,21 +1286,28 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const
             VRT_PROF_BEGIN(tp4);
             const uint32_t voxel_index = solid_bit - base;
             if constexpr (!EAGER) brick_material_index = start_is_slot ? brick_index * (uint32_t)(B * B * B) : (global_ptr(a.brick_start_index)[brick_index] & 0x7FFFFFFFu);
-            const uint32_t mi = global_ptr(a.material_index)[brick_material_index + voxel_index];
-            const auto *m = global_ptr(kConsts ? opaque_uniform(a.materials) : a.materials) + mi;
-            const uint32_t mtype = m->type;
-            const float mdata = m->type_data;
-            const bool ignore_brick = (mtype == r.ignore_type_material) && (r.internal_reflection == mdata); // comp:427
+            uint32_t mi = brick_material_index + voxel_index; // (PLAIN on a plain scene: the position stands for the material)
+            bool ignore_brick = false;
+            // (wave-uniform, on the scalar the round already holds)
+            if (PLAIN == kPlainOff || (opaque_uniform(bc.start_is_slot) & kFlagMaterialsPlain) == 0u) {
+                mi = global_ptr(a.material_index)[mi];
+                const auto *m = global_ptr(kConsts ? opaque_uniform(a.materials) : a.materials) + mi;
+                const uint32_t mtype = m->type;
+                const float mdata = m->type_data;
+                ignore_brick = (mtype == r.ignore_type_material) && (r.internal_reflection == mdata); // comp:427
+            }
             if (!ignore_brick) {
-                const int a = (first && g.stub == 0u)
-                                  ? axis_in
-                                  : (__builtin_amdgcn_inverse_ballot_w64(g.in_x) ? 0 : (__builtin_amdgcn_inverse_ballot_w64(g.in_y) ? 1 : 2));
-                // (hit.normal and hit.point are derived from hit_axis and hit.t once the walk is over: six registers
-                // less to carry through both loops)
-                hit.index = mi;
-                const float t_offset = voxel_scale * 0.05f;
-                hit.t += g.t_in * voxel_scale - t_offset; // t_value of the step into this voxel (comp:442), 0 for the first
-                hit_axis = a;
+                if constexpr (PLAIN != kPlainAnyHit) {
+                    const int a = (first && g.stub == 0u)
+                                      ? axis_in
+                                      : (__builtin_amdgcn_inverse_ballot_w64(g.in_x) ? 0 : (__builtin_amdgcn_inverse_ballot_w64(g.in_y) ? 1 : 2));
+                    // (hit.normal and hit.point are derived from hit_axis and hit.t once the walk is over: six registers
+                    // less to carry through both loops)
+                    hit.index = mi;
+                    const float t_offset = voxel_scale * 0.05f;
+                    hit.t += g.t_in * voxel_scale - t_offset; // t_value of the step into this voxel (comp:442), 0 for the first
+                    hit_axis = a;
+                }
                 if constexpr (VOXEL) *hit_voxel = voxel_index;
                 found = true;
             }
@@ -1552,16 +1592,23 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 // the kernarg segment in three batches — the grid block in front of the slab test, the box of the occupied cells and the
 // start_is_slot flag through the scalar unit behind it, the brick rounds' pointers in front of the walk — instead of one load
 // and one wait per dword wherever the compiler sank it.  Without KARGS the same values are plain reads of `p`.
-template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false>
+// The rays of the KARGS kernels are create_ray's, so their brick rounds run without the material look-ups where the scene's flag allows
+// it (brick_walk_gfx950<..., PLAIN>): a hit's material is then requested HERE, once, behind the walk — the caller reads it behind
+// its next walk, and the round trip runs under that walk's set-up.  ANY_HIT (with KARGS: the shadow ray): only the answer counts; `hit`
+// is not an output, and on such a scene no round asks for a material at all.
+template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false, bool ANY_HIT = false>
 VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr,
                      const DerivedWords *early = nullptr, bool sits_out = false) {
     static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
                   "voxel coordinates come from the hand-written walk without batching");
     constexpr bool kHandWalk = (MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT;
     static_assert(!KARGS || (kHandWalk && !BATCH && MODE != kStatusLinearLds), "the batched arguments serve the one-sample kernels' walks");
+    static_assert(!ANY_HIT || KARGS, "any-hit walks are the one-sample kernels' shadow rays");
+    constexpr int kPlain = !KARGS ? kPlainOff : (ANY_HIT ? kPlainAnyHit : kPlainHit);
     // (without KARGS every VRT_GA(x) is the plain read p.x, where it stands)
     [[maybe_unused]] GridArgs ga;
-    if constexpr (KARGS) ga = kernarg_grid_args();
+    [[maybe_unused]] const uint32_t *plain_flag = nullptr;
+    if constexpr (KARGS) ga = kernarg_grid_args(plain_flag);
 #define VRT_GA(field) (KARGS ? ga.field : p.field)
     const float t_min = 0.00001f;
     const float t_max = __builtin_inff();
@@ -1580,7 +1627,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
     // (KARGS: the six words of the box and the flag word, one round trip to the scalar cache for both — or none: the primary ray's
     // came with the camera, `early`; otherwise the box by vector loads here and the flag in front of the walk)
     [[maybe_unused]] DerivedWords dw{};
-    if constexpr (KARGS) dw = early ? *early : scalar_derived_words(ga);
+    if constexpr (KARGS) dw = early ? *early : scalar_derived_words(ga, plain_flag);
 
     // (opaque: the product of a uniform is formed where it is used, from its scalar register — hoisted out of the sample loop it was the one
     // vector register the several-samples kernel spilled at seven waves per SIMD, round 6)
@@ -1720,7 +1767,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         bool found;
         if constexpr ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT) {
             [[maybe_unused]] uint32_t voxel_in_brick = 0u;
-            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT, KARGS>(p, bc, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
+            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT, KARGS, kPlain>(p, bc, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
             if constexpr (VOXEL) {
                 if (found) { // voxel index x + B (z + B y) in the brick (comp:412)
                     voxel[0] = cx * B + (int)(voxel_in_brick % (uint32_t)B);
@@ -1891,6 +1938,11 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
             first = false;
             if constexpr (KARGS) by_slab = 0ull;
         }
+        if constexpr (ANY_HIT) return stop == -1;
+        // (a plain scene's hit holds its position in material_index: the material, requested and not waited for)
+        if constexpr (kPlain == kPlainHit) {
+            if ((opaque_uniform(bc.start_is_slot) & kFlagMaterialsPlain) != 0u && stop == -1) hit.index = global_ptr(bc.a.material_index)[hit.index];
+        }
         finish_hit();
         return stop == -1;
     } else {
@@ -1978,7 +2030,8 @@ VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const 
     const vrt_sun_device &sun = KARGS ? sun_batch : pc.sun;
     if (primary_hit) {
         // (the material record is read AFTER the shadow ray: only its index stays live across the second walk — three registers
-        // fewer at the kernel's point of highest pressure; the record sits in the scalar / L1 cache)
+        // fewer at the kernel's point of highest pressure; the record sits in the scalar / L1 cache.  KARGS on a plain scene: the
+        // index itself is still on its way from material_index, grid_hit; nothing reads it before the shadow ray is through)
         const uint32_t material = hit.index;
         bool lit = true;
         if (sun_enabled) {
@@ -1987,7 +2040,7 @@ VRT_DI f3 ray_color_single(const TraceParams &p, const PushConstants &pc, const 
                                           sun.radius);
             const Ray shadow_ray = create_ray(hit.point, (sun_position + rv) - hit.point);
             Hit shadow_hit;
-            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS>(p, lds_filter, shadow_ray, shadow_hit, c);
+            lit = !grid_hit<B, COUNT, MODE, false, SCALAR_ENTRY, false, REJECT, KARGS, KARGS>(p, lds_filter, shadow_ray, shadow_hit, c);
         }
         const vrt_material *m = p.materials + material;
         const uint32_t mtype = m->type;
