@@ -296,6 +296,8 @@ pub const AuxPlanes = extern struct {
 };
 /// What vrt_get_voxels gives for a voxel that is not solid or lies outside the grid; a solid voxel gives its material entry, 0..255.
 pub const VOXEL_EMPTY: u16 = 0xFFFF;
+/// The most boxes one vrt_read_boxes batch holds (its elements, 2 bytes each, must stay below 2^31 as well).
+pub const READ_BOXES_MAX: u32 = 4096;
 /// One box of vrt_query_boxes, 32 bytes: inclusive corners in voxels, in the coordinates vrt_grid_insert takes; clipped to the grid.
 pub const BoxQuery = extern struct {
     lo: [3]i32,
@@ -400,6 +402,9 @@ pub extern fn vrt_grid_get_voxels(g: ?*const Grid, xyz: [*c]const u32, n: u64, o
 pub extern fn vrt_query_boxes(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
 pub extern fn vrt_query_boxes_device(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
 pub extern fn vrt_grid_query_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n: u64, results: [*c]BoxResult) c_int;
+pub extern fn vrt_read_boxes(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
+pub extern fn vrt_read_boxes_device(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
+pub extern fn vrt_grid_read_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
 pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;

@@ -628,6 +628,38 @@ int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_bo
 int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
 /* the CPU twin on a host grid */
 int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
+/* ---- Dense box reads: the voxels of a batch of boxes as arrays --------------------------------------------------------
+ * The content of a region, for a host that meshes a chunk, builds a collider, saves a region or keeps an undo record: 32 bytes per
+ * box go in (vrt_box_query), 2 bytes per voxel come out.  Mode 4 of vrt_ray_query_b4 / _b8; like the volume queries it reads
+ * bindings 2-6 alone, and it has a CPU twin on a vrt_grid, which reads the grid's arrays only and registers no delta.
+ *
+ * ARGUMENTS AND LAYOUT.  boxes is in host memory in all three forms: the host needs the boxes to size the launch, as for the shape
+ * edits; there is no form with boxes in device memory.  Box k has inclusive signed corners lo, hi, in the coordinates
+ * vrt_grid_insert takes, with y as insert counts it.  Its sides are s = hi - lo + 1, formed in 64 bits; its volume is sx * sy * sz; a
+ * box with lo > hi on any axis has volume 0 and writes nothing.  The boxes' elements are packed in array order: box k starts at
+ * element base_k = the sum of the volumes of the boxes before it.  Element
+ *     base_k + (x - lo.x) + sx * ((z - lo.z) + sz * (y - lo.y))
+ * is exactly what vrt_get_voxels returns for voxel (x, y, z): the material entry of a solid voxel, or VRT_VOXEL_EMPTY — also for
+ * every voxel of the box that lies outside the grid, negative coordinates too.  The box is NOT clipped, so the output always has the
+ * caller's shape (a chunk with a one-voxel apron at the border of the grid).  The order is x fastest, then z, then y: the order of
+ * nth_bit inside a brick, y ascending in insert's count.  Elements at or beyond the total are never written.
+ *
+ * ERRORS.  A refused call touches nothing.  VRT_E_INVALID_ARG: a NULL ctx or grid; NULL boxes with n > 0; n > VRT_READ_BOXES_MAX; a
+ * box with non-zero flags or _reserved (the host screens the batch in all three forms; the error text names the box, as
+ * vrt_query_boxes does); NULL out while the total is > 0; out_elements below the total; (device form) out not 2-byte aligned.
+ * VRT_E_OUT_OF_RANGE: the batch's total reaches 2^31 elements (tested before out is looked at; the twin counts first too).
+ * VRT_E_STATE as for vrt_get_voxels: no grid state uploaded, or a context of the multi-GPU pipeline.  n == 0 or a total of 0: VRT_OK,
+ * and the device is not touched.  A failed call leaves the context usable.
+ *
+ * ORDERING is that of the volume queries: on the context's primary stream behind every upload and edit so far, so a read right after
+ * vrt_insert_voxels, vrt_clear_shapes, vrt_compact_bricks, vrt_paint_shapes or vrt_update_grid_delta sees it without a vrt_wait.  The
+ * host form stages out through the ray queries' device buffers (grown on demand, never beyond the size a full piece of rays gives
+ * them), 2^22 elements at a time, and blocks until out is written; the device form returns after the last launch (vrt_wait).  The
+ * context keeps no new device allocation. */
+#define VRT_READ_BOXES_MAX 4096u
+int vrt_read_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements);        /* out in host memory; blocks */
+int vrt_read_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements); /* out in device memory, 2-byte aligned; asynchronous (vrt_wait) */
+int vrt_grid_read_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements); /* the CPU twin */
 /* ---- Batched voxel inserts into the uploaded scene --------------------------------------------------------------
  * BrickGrid.insert (Grid.zig:129-194) for n voxels at once, on the GPU, on the scene buffers the context holds: after
  * vrt_insert_voxels(ctx, xyz, m, n) on a context whose bindings 2-6 equal a vrt_grid's arrays, bindings 2-6 equal that grid's

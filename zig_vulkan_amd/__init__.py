@@ -7,7 +7,7 @@ Importing it loads the shared library and fails loudly if it is absent.
 """
 from . import _lib
 from .voxel_rt import (AUX_PLANES, AUX_PLANE_DTYPES, BOX_QUERY_DTYPE, BOX_RESULT_DTYPE, VOXEL_EMPTY, BrickGrid, Camera, CameraConfig, Config, MATERIAL_DTYPE, RAY_HIT_DTYPE, RAY_QUERY_DTYPE, SHAPE_DTYPE, Sun, SunConfig, VoxelRT,
-                       box, box_queries, default_materials, ray_queries, shape_records, sphere)
+                       box, box_queries, default_materials, ray_queries, read_box_layout, read_box_views, shape_records, sphere)
 
 __all__ = ["AUX_PLANES", "AUX_PLANE_DTYPES", "BOX_QUERY_DTYPE", "BOX_RESULT_DTYPE", "VOXEL_EMPTY", "BrickGrid", "Camera", "CameraConfig", "Config", "MATERIAL_DTYPE", "RAY_HIT_DTYPE", "RAY_QUERY_DTYPE", "SHAPE_DTYPE", "Sun", "SunConfig",
-           "VoxelRT", "box", "box_queries", "default_materials", "ray_queries", "shape_records", "sphere", "_lib"]
+           "VoxelRT", "box", "box_queries", "default_materials", "ray_queries", "read_box_layout", "read_box_views", "shape_records", "sphere", "_lib"]

@@ -307,6 +307,61 @@ void BrickGrid::queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_resul
     }
 }
 
+int BrickGrid::readBoxes(const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements, std::string *why) const {
+    const vrt_grid_state &d = device_state_;
+    const int64_t b = brick_dimension_;
+    std::string reason;
+    uint64_t total = 0;
+    const int rc = screen_read_boxes(boxes, n, brick_dimension_, out, out_elements, &total, &reason);
+    if (rc != VRT_OK) {
+        if (why) *why = reason;
+        return rc;
+    }
+    const int64_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
+    uint64_t base = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const vrt_box_query &q = boxes[i];
+        const ReadBoxShape s = read_box_shape(q, brick_dimension_);
+        if (!s.volume) continue;
+        uint16_t *box = out + base;
+        base += s.volume;
+        std::fill(box, box + s.volume, (uint16_t)VRT_VOXEL_EMPTY);
+        int64_t lo[3], hi[3]; // the part of the box inside the grid; y flipped from here on (Grid.zig:135)
+        bool outside = false;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = std::max<int64_t>(q.lo[k], 0);
+            hi[k] = std::min<int64_t>(q.hi[k], dim[k] - 1);
+            outside = outside || lo[k] > hi[k];
+        }
+        if (outside) continue;
+        const int64_t flipped_lo = dim[1] - 1 - hi[1], flipped_hi = dim[1] - 1 - lo[1];
+        lo[1] = flipped_lo, hi[1] = flipped_hi;
+        // cell by cell, and in a loaded cell row by row: the B voxels of a row (x) are B adjacent bits of one occupancy byte
+        for (int64_t cy = lo[1] / b; cy <= hi[1] / b; cy++)
+            for (int64_t cz = lo[2] / b; cz <= hi[2] / b; cz++)
+                for (int64_t cx = lo[0] / b; cx <= hi[0] / b; cx++) {
+                    const size_t grid_index = (size_t)cx + (size_t)d.dim_x * ((size_t)cz + (size_t)d.dim_z * (size_t)cy); // gridAt
+                    if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue;
+                    const uint32_t brick_index = brick_indices[grid_index];
+                    const uint8_t *occ = &brick_occupancy[(size_t)brick_index * brick_bytes_];
+                    const uint8_t *materials = &material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu)]; // comp:422-425
+                    const int64_t x0 = std::max(lo[0], cx * b), x1 = std::min(hi[0], cx * b + b - 1);
+                    const uint32_t row_mask = ((1u << (x1 - x0 + 1)) - 1u) << (x0 - cx * b);
+                    for (int64_t fy = std::max(lo[1], cy * b); fy <= std::min(hi[1], cy * b + b - 1); fy++)
+                        for (int64_t z = std::max(lo[2], cz * b); z <= std::min(hi[2], cz * b + b - 1); z++) {
+                            const uint32_t row_bit = (uint32_t)(b * ((z - cz * b) + b * (fy - cy * b))); // voxelAt of the row's x = 0
+                            const uint32_t row = (occ[row_bit / 8] >> (row_bit % 8)) & row_mask;
+                            if (!row) continue;
+                            const int64_t y = dim[1] - 1 - fy;
+                            uint16_t *dst = box + (uint64_t)(x0 - q.lo[0]) + s.side[0] * ((uint64_t)(z - q.lo[2]) + s.side[2] * (uint64_t)(y - q.lo[1])); // voxel x0
+                            for (int64_t x = x0; x <= x1; x++)
+                                if ((row >> (x - cx * b)) & 1u) dst[x - x0] = materials[row_bit + (uint32_t)(x - cx * b)];
+                        }
+                }
+    }
+    return VRT_OK;
+}
+
 bool BrickGrid::shapeRows(const ClippedShape &s, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t rows[64]) const {
     const uint32_t b = brick_dimension_;
     std::fill(rows, rows + b * b, (uint8_t)0);

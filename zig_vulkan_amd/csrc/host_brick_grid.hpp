@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/vrt_hip.h"
+#include "vrt_read_boxes.h"
 #include "vrt_shapes.h"
 
 namespace vrt {
@@ -81,6 +82,9 @@ public:
     // per box: the number and the tight bounds of the solid voxels in the box clipped to the grid; all zero for none, and for a box
     // with flag bits or a non-zero _reserved
     void queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_result *results) const;
+    // the voxels of every box as getVoxels answers them, packed box after box, x fastest, then z, then y; the box is not clipped, and
+    // what lies outside the grid is VRT_VOXEL_EMPTY.  A batch that is refused (screen_read_boxes) writes nothing; *why (may be null) says why.
+    int readBoxes(const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements, std::string *why = nullptr) const;
 
     // Shape edits (the reference has none: include/vrt_hip.h defines them).  The arrays and the deltas that insertUnlocked /
     // removeManyUnlocked give on the shapes' voxels (shapes in array order, within a shape the cells that hold a voxel of it in

@@ -272,6 +272,11 @@ int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t
     return VRT_OK;
 }
 
+int vrt_grid_read_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<const vrt::BrickGrid *>(g)->readBoxes(boxes, n, out, out_elements);
+}
+
 int vrt_grid_fill_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {
     if (!g) return VRT_E_INVALID_ARG;
     return reinterpret_cast<vrt::BrickGrid *>(g)->fillShapes(shapes, n);

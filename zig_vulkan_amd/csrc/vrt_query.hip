@@ -2,17 +2,19 @@
 // their host side; the first-hit buffer pass (vrt_trace_aux, vrt_trace_aux_device), a second mode of the same two kernels: the
 // camera ray of every pixel, formed in the kernel, and only the planes of its hit record that were asked for; and the camera ray of a
 // pixel (vrt_camera_pixel_ray); and the volume queries (vrt_get_voxels, vrt_query_boxes and their _device forms), modes 2 and 3 of the
-// same two kernels, which read bindings 2-6 only.  A ray query sees the scene as the next frame would: the structures
-// derived from the scene buffers are refreshed through the frames' own path (refresh_derived) on the primary stream, after every upload
-// so far.  The kernels are compiled with the product's arithmetic flags, so that a query is bit-equal to the shader's GridHit
-// (vrt_math.h's contract).
+// same two kernels, which read bindings 2-6 only, and the dense box reads (vrt_read_boxes, vrt_read_boxes_device), their mode 4.
+// A ray query sees the scene as the next frame would: the structures derived from the scene buffers are refreshed through the frames'
+// own path (refresh_derived) on the primary stream, after every upload so far.  The kernels are compiled with the product's
+// arithmetic flags, so that a query is bit-equal to the shader's GridHit (vrt_math.h's contract).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 #include "vrt_ctx.h"
+#include "vrt_read_boxes.h"
 #include "vrt_trace_kernels.h" // (after vrt_ctx.h: behind its <chrono>, the host pass rejects the walk's gfx950 inline assembly)
 
 namespace vrt {
@@ -44,8 +46,14 @@ struct QueryArgs {
     const u32x4 *vol_boxes;    // mode 3: vrt_box_query as two dwordx4 (16-byte aligned, like the results)
     u32x4 *vol_results;        // mode 3: vrt_box_result as two dwordx4
     uint32_t vol_bricks;       // brick_alloc: a loaded cell that names a brick beyond it (no scene an edit or a host grid made) reads as empty
+    // mode 4 (the dense box reads): n items, one per lane.  vol_boxes: the screened boxes, dword 6 of box k = base_k (its first element);
+    // vol_materials: where element read_first_element goes
+    const uint32_t *read_prefix; // read_boxes + 1 exclusive item prefixes: box k owns items [read_prefix[k], read_prefix[k + 1])
+    uint32_t read_boxes;         // boxes of the batch
+    uint32_t read_first_item;    // the first item of this launch
+    uint32_t read_first_element; // the element vol_materials points at (the first element of the launch's first item, or 0)
 };
-constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u, kQueryModeVoxels = 2u, kQueryModeBoxes = 3u;
+constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u, kQueryModeVoxels = 2u, kQueryModeBoxes = 3u, kQueryModeRead = 4u;
 
 constexpr uint32_t kQueryBlock = 256u;             // threads per workgroup: four waves, one ray per lane
 constexpr uint64_t kQueryLaunchRays = 1ull << 24;  // rays per launch (65 536 workgroups); larger batches are launched in pieces
@@ -53,6 +61,10 @@ constexpr uint64_t kQueryHostPieceRays = 1ull << 20; // vrt_cast_rays: rays per 
 constexpr uint64_t kAuxMaxPixels = 1ull << 24;     // first-hit buffer pass: pixels of the camera's image (one launch; pixel indices stay 32-bit)
 constexpr uint32_t kBoxesPerGroup = kQueryBlock / 64u; // box queries: one wave per box
 constexpr uint64_t kQueryLaunchBoxes = 1ull << 22; // boxes per launch (2^20 workgroups)
+constexpr uint64_t kReadLaunchItems = 1ull << 24;  // dense box reads: items per launch (65 536 workgroups)
+constexpr uint64_t kReadHostPieceElements = 1ull << 22; // vrt_read_boxes: elements per round trip through the context's device buffers (8 MiB of the hits' buffer)
+static_assert(kReadHostPieceElements <= kReadLaunchItems, "a piece of the host form is one launch: an item holds at least one element");
+static_assert(kReadHostPieceElements * sizeof(uint16_t) <= kQueryHostPieceRays * sizeof(vrt_ray_hit), "a piece fits the hits' buffer at its full size");
 
 VRT_DI float as_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
 VRT_DI bool finite3(f3 v) { return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z); }
@@ -240,6 +252,117 @@ VRT_DI void box_query(const QueryArgs &a) {
     a.vol_results[2u * box + 1u] = r1;
 }
 
+// Mode 4: one cell row of one box per lane.  An item is (box k, row (y, z) of the box, cell column c), c from floor(lo.x / B) to
+// floor(hi.x / B), and covers x in [cB, cB + B - 1] intersected with [lo.x, hi.x]; items are numbered box-major, then row, then column,
+// which is the order of the output: adjacent lanes write adjacent runs of out.  The lane finds its box by binary search in the item
+// prefixes, its row and column with two divisions and its first element in closed form; then every load happens only where the one
+// before says so: nothing for a row outside the grid, the status bit, the brick index, the one occupancy byte that holds the row, and
+// the row's B material bytes only where that byte has a bit of the run.  The B voxels travel as 16-bit fields of two 64-bit words
+// (one for 4^3 bricks): no array is indexed by a lane's value.
+template <int B>
+VRT_DI void read_query(const QueryArgs &a) {
+    constexpr uint32_t kBits = (uint32_t)(B * B * B), kShift = B == 8 ? 3u : 2u, kMask = (uint32_t)B - 1u;
+    const uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x; // (at most 2^24 items per launch)
+    if (i >= a.n) return;
+    const uint32_t item = a.read_first_item + i;               // (< 2^31)
+    // the last box whose prefix is at or below the item: boxes without items share their prefix with the box that follows them
+    uint32_t k = 0u, end = a.read_boxes;                       // read_prefix[k] <= item < read_prefix[end]
+    while (end - k > 1u) {
+        const uint32_t mid = (k + end) >> 1;
+        if (a.read_prefix[mid] <= item) k = mid;
+        else end = mid;
+    }
+    const u32x4 q0 = a.vol_boxes[2u * k], q1 = a.vol_boxes[2u * k + 1u]; // lo.xyz hi.x | hi.yz base_k 0
+    const int32_t lox = (int32_t)q0.x, loy = (int32_t)q0.y, loz = (int32_t)q0.z, hix = (int32_t)q0.w, hiz = (int32_t)q1.y;
+    // a box with items has sides below 2^31 (its volume is), and floor(x / B) of a signed x is its arithmetic shift
+    const uint32_t sx = (uint32_t)hix - (uint32_t)lox + 1u, sz = (uint32_t)hiz - (uint32_t)loz + 1u;
+    const int32_t c0 = lox >> kShift;
+    const uint32_t columns = (uint32_t)((hix >> kShift) - c0) + 1u;
+    const uint32_t local = item - a.read_prefix[k];
+    const uint32_t row = local / columns, column = local - row * columns;
+    const uint32_t ry = row / sz, rz = row - ry * sz;
+    const uint32_t head = (uint32_t)lox & kMask;                                   // lo.x mod B
+    const uint32_t xl = column == 0u ? head : 0u, xh = column == columns - 1u ? (uint32_t)hix & kMask : kMask; // the run, within the cell
+    uint32_t count = xh - xl + 1u;
+    const uint32_t element = q1.z + row * sx + (column ? column * (uint32_t)B - head : 0u);
+    uint16_t *dst = a.vol_materials + (element - a.read_first_element);
+
+    uint64_t v0 = ~0ull, v1 = ~0ull; // voxel x of the cell row in bits [16x, 16x + 15] of v1:v0; VRT_VOXEL_EMPTY
+    const vrt_grid_state &g = a.p.grid;
+    const int32_t c = c0 + (int32_t)column, y = loy + (int32_t)ry, z = loz + (int32_t)rz; // (within the box: no overflow)
+    if (c >= 0 && (uint32_t)c < g.dim_x && y >= 0 && (uint32_t)y < g.voxel_dim_y && z >= 0 && (uint32_t)z < g.voxel_dim_z) {
+        const uint32_t fy = g.voxel_dim_y - 1u - (uint32_t)y;                                                   // Grid.zig:135
+        const uint32_t cell = (uint32_t)c + g.dim_x * (((uint32_t)z >> kShift) + g.dim_z * (fy >> kShift)); // gridAt
+        if (cell_loaded(a.p, cell)) {
+            const uint32_t brick = a.p.brick_index[cell];
+            const uint32_t row_bit = (uint32_t)B * (((uint32_t)z & kMask) + (uint32_t)B * (fy & kMask)); // voxelAt of the row's x = 0
+            if (brick < a.vol_bricks) {
+                const uint32_t run = ((2u << xh) - 1u) & ~((1u << xl) - 1u);
+                const uint32_t bits = ((uint32_t)a.p.brick_occupancy[brick * (kBits / 8u) + (row_bit >> 3)] >> (row_bit & 7u)) & run;
+                if (bits) {
+                    const uint32_t entry = (a.p.brick_start_index[brick] & 0x7FFFFFFFu) + row_bit; // comp:422-425
+                    const uint32_t limit = a.vol_bricks * kBits;                                    // (brick_alloc * B^3 <= 2^31)
+                    uint64_t bytes = 0ull; // the row's B material bytes
+                    if ((entry & kMask) == 0u && entry + (uint32_t)B <= limit) { // brick starts need not be aligned: one load where they are
+                        if constexpr (B == 8) bytes = *reinterpret_cast<const uint64_t *>(a.p.material_index + entry);
+                        else bytes = *reinterpret_cast<const uint32_t *>(a.p.material_index + entry);
+                    } else {
+#pragma unroll
+                        for (uint32_t x = 0; x < (uint32_t)B; x++)
+                            if (((bits >> x) & 1u) && entry + x < limit) bytes |= (uint64_t)a.p.material_index[entry + x] << (8u * x);
+                    }
+                    uint64_t w[2] = {0ull, 0ull};
+#pragma unroll
+                    for (uint32_t x = 0; x < (uint32_t)B; x++) { // (x is a constant after unrolling)
+                        const bool solid = ((bits >> x) & 1u) && entry + x < limit; // an entry at or beyond the end reads as empty, as in mode 2
+                        const uint64_t value = solid ? (bytes >> (8u * x)) & 0xFFull : (uint64_t)VRT_VOXEL_EMPTY;
+                        w[x >> 2] |= value << (16u * (x & 3u));
+                    }
+                    v0 = w[0];
+                    if constexpr (B == 8) v1 = w[1];
+                }
+            }
+        }
+    }
+    // the run to the front
+    const uint32_t shift = 16u * xl;
+    if constexpr (B == 8) {
+        if (shift >= 64u) v0 = v1 >> (shift - 64u);
+        else if (shift) v0 = (v0 >> shift) | (v1 << (64u - shift)), v1 >>= shift;
+    } else {
+        v0 >>= shift;
+    }
+    // a whole cell row at an aligned place in one store; otherwise one element up to a dword boundary, dwords, and one element
+    const uintptr_t at = reinterpret_cast<uintptr_t>(dst);
+    if constexpr (B == 8) {
+        if (count == 8u && (at & 15u) == 0u) {
+            *reinterpret_cast<u32x4 *>(dst) = u32x4{(uint32_t)v0, (uint32_t)(v0 >> 32), (uint32_t)v1, (uint32_t)(v1 >> 32)};
+            return;
+        }
+    } else {
+        if (count == 4u && (at & 7u) == 0u) {
+            *reinterpret_cast<uint2 *>(dst) = uint2{(uint32_t)v0, (uint32_t)(v0 >> 32)};
+            return;
+        }
+    }
+    if (at & 2u) { // (count >= 1)
+        *dst++ = (uint16_t)v0;
+        v0 = (v0 >> 16) | (v1 << 48);
+        v1 >>= 16;
+        count--;
+    }
+#pragma unroll
+    for (int pair = 0; pair < B / 2; pair++) {
+        if (count < 2u) break;
+        *reinterpret_cast<uint32_t *>(dst) = (uint32_t)v0;
+        v0 = (v0 >> 32) | (v1 << 32);
+        v1 >>= 32;
+        dst += 2;
+        count -= 2u;
+    }
+    if (count) *dst = (uint16_t)v0;
+}
+
 // One GridHit of the frames' own walk per ray, one ray per lane.
 template <int B>
 VRT_DI void ray_query(const QueryArgs &a) {
@@ -253,6 +376,10 @@ VRT_DI void ray_query(const QueryArgs &a) {
     }
     if (a.mode == kQueryModeBoxes) {
         box_query<B>(a);
+        return;
+    }
+    if (a.mode == kQueryModeRead) {
+        read_query<B>(a);
         return;
     }
     const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
@@ -375,6 +502,108 @@ int staged_batch(vrt_ctx *ctx, const QueryKind &k, const void *in, uint64_t n, v
     }
     VRT_HIP(ctx, wait_stream(ctx->stream));
     return VRT_OK;
+}
+
+// ---- The dense box reads (mode 4) ----
+// What the host knows of a screened batch: per box its shape, its first element and its first item, and the two tables the kernels read
+struct ReadBatch {
+    std::vector<vrt::ReadBoxShape> shape;
+    std::vector<uint32_t> base;   // n + 1: base[k] = the first element of box k, base[n] = the total
+    std::vector<uint32_t> prefix; // n + 1: prefix[k] = the first item of box k, prefix[n] = the items
+    uint32_t b;
+    // the first element of item `item` (<= items; the total for item == items): the kernel's closed form
+    uint32_t element_of(const vrt_box_query *boxes, uint32_t item) const {
+        const size_t n = shape.size();
+        if (item >= prefix[n]) return base[n];
+        const size_t k = (size_t)(std::upper_bound(prefix.begin(), prefix.end(), item) - prefix.begin()) - 1u;
+        const uint32_t local = item - prefix[k], columns = (uint32_t)shape[k].columns;
+        const uint32_t row = local / columns, column = local - row * columns;
+        const uint32_t head = (uint32_t)(boxes[k].lo[0] - vrt::floor_div(boxes[k].lo[0], b) * (int64_t)b);
+        return base[k] + row * (uint32_t)shape[k].side[0] + (column ? column * b - head : 0u);
+    }
+};
+
+// Both forms behind their checks: the boxes (dword 6 = the box's first element) and the item prefixes into the query input buffer, then
+// the launches.  device_out: launches of at most kReadLaunchItems items straight into the caller's memory.  Otherwise pieces of
+// contiguous items that hold at most kReadHostPieceElements elements, each one launch into the query output buffer and one copy back,
+// and one wait at the end.
+int read_boxes_run(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint64_t total, uint16_t *out, bool device_out) {
+    ReadBatch t;
+    t.b = (uint32_t)ctx->cfg.brick_dimension;
+    t.shape.resize(n);
+    t.base.resize(n + 1u);
+    t.prefix.resize(n + 1u);
+    std::vector<vrt_box_query> records(boxes, boxes + n);
+    uint64_t elements = 0, items = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        t.shape[k] = vrt::read_box_shape(boxes[k], t.b);
+        t.base[k] = (uint32_t)elements, t.prefix[k] = (uint32_t)items;
+        records[k].flags = (uint32_t)elements; // (screened: it was 0)
+        elements += t.shape[k].volume, items += t.shape[k].items; // (items <= elements < 2^31)
+    }
+    t.base[n] = (uint32_t)elements, t.prefix[n] = (uint32_t)items;
+    // the tables: n records of 32 bytes and n + 1 prefixes behind them, counted in rays like the buffers' capacity
+    const uint64_t table_bytes = n * sizeof(vrt_box_query) + (n + 1u) * sizeof(uint32_t);
+    const uint64_t piece = std::min<uint64_t>(total, vrt::kReadHostPieceElements);
+    uint64_t want = (table_bytes + sizeof(vrt_ray_query) - 1u) / sizeof(vrt_ray_query);
+    if (!device_out) want = std::max<uint64_t>(want, (piece * sizeof(uint16_t) + sizeof(vrt_ray_hit) - 1u) / sizeof(vrt_ray_hit)); // (<= kQueryHostPieceRays)
+    int rc = grow_device(ctx, ctx->query_capacity, want, true, ctx->d_query_rays, want * sizeof(vrt_ray_query), ctx->d_query_hits, want * sizeof(vrt_ray_hit));
+    if (rc != VRT_OK) return rc;
+    uint8_t *d_tables = reinterpret_cast<uint8_t *>(ctx->d_query_rays);
+    rc = staged_copy_h2d(ctx, d_tables, records.data(), n * sizeof(vrt_box_query)); // (through the pinned slots: the tables die with this call)
+    if (rc == VRT_OK) rc = staged_copy_h2d(ctx, d_tables + n * sizeof(vrt_box_query), t.prefix.data(), (n + 1u) * sizeof(uint32_t));
+    if (rc != VRT_OK) return rc;
+
+    vrt::QueryArgs a{};
+    a.p = ctx->params;
+    a.mode = vrt::kQueryModeRead;
+    a.vol_bricks = (uint32_t)ctx->cfg.brick_alloc;
+    a.vol_boxes = reinterpret_cast<const vrt::u32x4 *>(d_tables);
+    a.read_prefix = reinterpret_cast<const uint32_t *>(d_tables + n * sizeof(vrt_box_query));
+    a.read_boxes = (uint32_t)n;
+    uint16_t *d_stage = reinterpret_cast<uint16_t *>(ctx->d_query_hits);
+    for (uint32_t first = 0; first < (uint32_t)items;) {
+        uint32_t last; // one past the launch's last item
+        const uint32_t e0 = t.element_of(boxes, first);
+        if (device_out) {
+            last = (uint32_t)std::min<uint64_t>(items, (uint64_t)first + vrt::kReadLaunchItems);
+        } else { // the most items from `first` on whose elements fit a piece (an item holds at most B of them: at least one item fits)
+            uint32_t lo = first + 1u, hi = (uint32_t)std::min<uint64_t>(items, (uint64_t)first + vrt::kReadHostPieceElements);
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo + 1u) / 2u;
+                if ((uint64_t)t.element_of(boxes, mid) - e0 <= vrt::kReadHostPieceElements) lo = mid;
+                else hi = mid - 1u;
+            }
+            last = lo;
+        }
+        a.read_first_item = first;
+        a.n = last - first;
+        a.vol_materials = device_out ? out : d_stage;
+        a.read_first_element = device_out ? 0u : e0;
+        const dim3 groups((uint32_t)((a.n + vrt::kQueryBlock - 1u) / vrt::kQueryBlock));
+        VRT_HIP(ctx, launch_ray_query(a, ctx->cfg.brick_dimension, ctx->stream, groups));
+        if (!device_out) {
+            const uint32_t e1 = t.element_of(boxes, last);
+            VRT_HIP(ctx, hipMemcpyAsync(out + e0, d_stage, (uint64_t)(e1 - e0) * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        first = last;
+    }
+    if (!device_out) VRT_HIP(ctx, wait_stream(ctx->stream));
+    return VRT_OK;
+}
+
+int read_boxes_entry(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements, bool device_out) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    std::string why;
+    uint64_t total = 0;
+    int rc = vrt::screen_read_boxes(boxes, n, (uint32_t)ctx->cfg.brick_dimension, out, out_elements, &total, &why);
+    if (rc != VRT_OK) return fail(ctx, rc, why);
+    if (device_out && (reinterpret_cast<uintptr_t>(out) & 1u)) return fail(ctx, VRT_E_INVALID_ARG, "out must be 2-byte aligned");
+    if (total == 0) return VRT_OK;
+    DeviceGuard dg(ctx->device);
+    rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    return read_boxes_run(ctx, boxes, n, total, out, device_out);
 }
 
 // What both entry points of the first-hit buffer pass check before they touch the device; *pixels: the camera's image
@@ -532,6 +761,14 @@ int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_bo
     const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
     return staged_batch(ctx, kBoxes, boxes, n, results);
+}
+
+int vrt_read_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements) {
+    return read_boxes_entry(ctx, boxes, n, out, out_elements, false);
+}
+
+int vrt_read_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements) {
+    return read_boxes_entry(ctx, boxes, n, out, out_elements, true);
 }
 
 // CameraGetRay (comp:474-477) for sample 0 (hash12(0) = 0: no jitter), as vrt_trace_kernel forms it: u = x / (w - 1), v = y / (h - 1),

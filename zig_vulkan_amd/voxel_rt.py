@@ -125,6 +125,17 @@ class BrickGrid:
         check(lib.vrt_grid_query_boxes(self._h, q.ctypes.data, q.shape[0], out.ctypes.data))
         return out
 
+    def read_boxes(self, lo, hi) -> list:
+        """vrt_grid_read_boxes: per box of inclusive corners lo, hi (n, 3) in voxels (signed; NOT clipped), a uint16 array indexed
+        [x, y, z] of what get_voxels gives for each of its voxels: the material entry, or VOXEL_EMPTY (outside the grid too).  The
+        arrays are views of one flat buffer."""
+        q = box_queries(lo, hi)
+        bases, shapes = read_box_layout(q)
+        total = int(bases[-1])
+        flat = np.empty(total if total < 1 << 31 else 0, dtype=np.uint16)   # (2^31: the call refuses)
+        check(lib.vrt_grid_read_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data, total))
+        return read_box_views(flat, bases, shapes)
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -300,8 +311,26 @@ def box_queries(lo, hi) -> np.ndarray:
     return q
 
 
+def read_box_layout(q: np.ndarray):
+    """Where vrt_read_boxes puts the boxes of `q` (box_queries records): bases (n + 1,) int64, box k at elements
+    [bases[k], bases[k + 1]), and shapes (n, 3) int64, the sides (sx, sy, sz); a box with lo > hi on any axis has sides 0."""
+    sides = q["hi"].astype(np.int64) - q["lo"].astype(np.int64) + 1
+    sides[np.any(sides <= 0, axis=1)] = 0
+    bases = np.concatenate([[0], np.cumsum(sides[:, 0] * sides[:, 1] * sides[:, 2])]).astype(np.int64)
+    return bases, sides
+
+
+def read_box_views(flat, bases, shapes) -> list:
+    """The boxes of a flat vrt_read_boxes result (x fastest, then z, then y) as views indexed [x, y, z]; flat: numpy or torch."""
+    out = []
+    for k, (sx, sy, sz) in enumerate(np.asarray(shapes).tolist()):
+        box = flat[int(bases[k]):int(bases[k + 1])].reshape(sy, sz, sx)
+        out.append(box.transpose(2, 0, 1) if isinstance(box, np.ndarray) else box.permute(2, 0, 1))
+    return out
+
+
 # vrt_shape (include/vrt_hip.h) as a numpy record
-SHAPE_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("kind", np.uint32), ("material", np.uint32)])
+SHAPE_DTYPE =np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("kind", np.uint32), ("material", np.uint32)])
 assert SHAPE_DTYPE.itemsize == 32
 
 
@@ -709,6 +738,26 @@ class VoxelRT:
         results = np.zeros(q.shape[0], dtype=BOX_RESULT_DTYPE)
         self._check(self._lib.vrt_query_boxes(self._h, q.ctypes.data, q.shape[0], results.ctypes.data))
         return results
+
+    def read_boxes(self, lo, hi, device: bool = False):
+        """The content of each box of inclusive corners lo, hi (n, 3) in voxels (signed; NOT clipped: what lies outside the grid is
+        VOXEL_EMPTY), in the scene the context holds (vrt_read_boxes): a list of uint16 arrays indexed [x, y, z], one per box, views of
+        one flat buffer, each element what get_voxels gives for that voxel.  Sees every edit so far.  device=True: the flat result stays
+        a torch int16 tensor on the GPU (vrt_read_boxes_device, then wait) and is returned as (flat, bases, shapes): box k is
+        flat[bases[k]:bases[k + 1]].reshape(sy, sz, sx) with (sx, sy, sz) = shapes[k] (read_box_views gives the [x, y, z] views)."""
+        q = box_queries(lo, hi)
+        bases, shapes = read_box_layout(q)
+        total = int(bases[-1])
+        if device:
+            import torch
+            flat = torch.empty(total if total < 1 << 31 else 0, dtype=torch.int16, device=f"cuda:{self._device_index()}")   # (2^31: the call refuses)
+            torch.cuda.current_stream(flat.device).synchronize()  # (torch's stream may still use the memory; the library's is another)
+            self._check(self._lib.vrt_read_boxes_device(self._h, q.ctypes.data, q.shape[0], flat.data_ptr() if flat.numel() else None, total))
+            self.wait()
+            return flat, bases, shapes
+        flat = np.empty(total if total < 1 << 31 else 0, dtype=np.uint16)   # (2^31: the call refuses)
+        self._check(self._lib.vrt_read_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data, total))
+        return read_box_views(flat, bases, shapes)
 
     def region_begin(self) -> None:
         self._check(self._lib.vrt_region_begin(self._h))
