@@ -298,6 +298,10 @@ pub const AuxPlanes = extern struct {
 pub const VOXEL_EMPTY: u16 = 0xFFFF;
 /// The most boxes one vrt_read_boxes batch holds (its elements, 2 bytes each, must stay below 2^31 as well).
 pub const READ_BOXES_MAX: u32 = 4096;
+/// An element of vrt_write_boxes that leaves its voxel exactly as it is (0..255: solid with that material; VOXEL_EMPTY: empty).
+pub const VOXEL_KEEP: u16 = 0xFFFE;
+/// The most boxes one vrt_write_boxes batch holds; they must be disjoint inside the grid.
+pub const WRITE_BOXES_MAX: u32 = 4096;
 /// One box of vrt_query_boxes, 32 bytes: inclusive corners in voxels, in the coordinates vrt_grid_insert takes; clipped to the grid.
 pub const BoxQuery = extern struct {
     lo: [3]i32,
@@ -416,6 +420,9 @@ pub extern fn vrt_fill_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int
 pub extern fn vrt_clear_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_paint_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64, only: u32, painted: [*c]u64) c_int;
 pub extern fn vrt_grid_paint_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64, only: u32, painted: [*c]u64) c_int;
+pub extern fn vrt_write_boxes(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, data: [*c]const u16, data_elements: u64) c_int;
+pub extern fn vrt_write_boxes_device(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, data: [*c]const u16, data_elements: u64) c_int;
+pub extern fn vrt_grid_write_boxes(g: ?*Grid, boxes: [*c]const BoxQuery, n: u64, data: [*c]const u16, data_elements: u64) c_int;
 pub extern fn vrt_read_buffer(ctx: ?*Ctx, id: BufferId, byte_offset: u64, dst: ?*anyopaque, nbytes: u64) c_int;
 pub extern fn vrt_scene_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
 pub extern fn vrt_derived_size(ctx: ?*const Ctx, id: DerivedId) u64;

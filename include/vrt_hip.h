@@ -788,6 +788,51 @@ int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n);
 int vrt_paint_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted /* may be NULL */);
 /* the CPU twin on a host grid */
 int vrt_grid_paint_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted /* may be NULL */);
+/* ---- Dense box writes: paste uint16 arrays into boxes of the scene -----------------------------------------------------------
+ * The write-side twin of vrt_read_boxes, for paste, undo, streaming a saved chunk in and terrain generated on the GPU: the same box
+ * records and the same packed layout go in, and the device works per 32-bit occupancy word (the seventh mode of the vrt_edit_*
+ * kernels).  vrt_write_boxes(boxes, what vrt_read_boxes(boxes) gave) leaves every frame unchanged; read, edit, write back is an undo.
+ *
+ * LAYOUT is exactly vrt_read_boxes': boxes in host memory in all three forms; inclusive signed corners; the box is NOT clipped; box
+ * k's elements start at base_k, the sum of the volumes before it, and the element of voxel (x, y, z) is
+ *     base_k + (x - lo.x) + sx * ((z - lo.z) + sz * (y - lo.y)),
+ * y as insert counts it.  A box with lo > hi on any axis has volume 0 and takes no elements.  ELEMENTS OF VOXELS OUTSIDE THE GRID ARE
+ * NEVER READ OR SCREENED (an apron may hold anything).
+ *
+ * ELEMENT VALUES, for voxels inside the grid.  0..255: the voxel becomes solid with that material.  VRT_VOXEL_EMPTY: the voxel becomes
+ * empty.  VRT_VOXEL_KEEP: the voxel stays exactly as it is (a stamp with holes does not erase its surroundings).  Anything else is
+ * refused.
+ *
+ * THE BOXES MUST BE DISJOINT: the parts of the boxes that lie inside the grid are pairwise disjoint, or the call is refused
+ * (VRT_E_INVALID_ARG; the text names the first overlapping pair).  So no voxel has two writers.  The host screens this by a sweep over
+ * the boxes sorted by lo.x.
+ *
+ * DEFINITION BY ENUMERATION, byte for byte on bindings 2-6, and on a vrt_grid's five arrays, active bricks and all five deltas: a
+ * write is vrt_grid_insert_many(I) FOLLOWED BY vrt_grid_remove_many(R).  I: the voxels inside the grid whose element is a material,
+ * each with that material; boxes in array order; within a box the cells that hold a voxel of I in ascending grid index; within a cell
+ * any order.  R: the voxels inside the grid whose element is VRT_VOXEL_EMPTY.  Insert comes first, so a loaded cell keeps its brick
+ * across a paste over itself: pasting one region for ever allocates nothing.  A cell that is not loaded gets a brick only if it holds
+ * a voxel of I; new bricks are numbered box-major, then by cell index.  A loaded cell whose brick ends the call with no bit set loses
+ * its status bit, and its brick is not reused (see vrt_remove_voxels).  Removals in cells that are not loaded are no-ops.  No material
+ * byte of a voxel outside I is written.
+ *
+ * ERRORS, all or nothing, on the twin too (it counts first).  VRT_E_INVALID_ARG: a NULL ctx or grid; NULL boxes with n > 0;
+ * n > VRT_WRITE_BOXES_MAX; a box with non-zero flags or _reserved; overlapping boxes; NULL data while the total is > 0; data_elements
+ * below the total; (device form) data not 2-byte aligned; an element of a voxel inside the grid that is none of the three kinds (the
+ * device form finds it on the device, the host form and the twin on the host).  VRT_E_OUT_OF_RANGE: the total reaches 2^31 elements
+ * (tested before data is looked at), or the work items (one per occupancy word of every cell that a box's part inside the grid
+ * touches) reach 2^31.  VRT_E_OOM: the batch needs more bricks or material entries than are left.  VRT_E_STATE as for vrt_fill_shapes.
+ * n == 0, a total of 0, or no box reaching into the grid: VRT_OK, and the device is not touched.
+ *
+ * ORDERING AND STAGING as for vrt_fill_shapes: one scene write on the context's stream, one small status read-back ends the call; the
+ * derived structures are refreshed for the written ranges, so frames and queries issued right after see the write without a vrt_wait.
+ * The host form stages the records and data as vrt_insert_voxels stages its batch; the device form reads data in place, ordered
+ * behind every earlier write on the context's stream, and no longer once the call has returned. */
+#define VRT_VOXEL_KEEP 0xFFFEu      /* element: leave this voxel exactly as it is */
+#define VRT_WRITE_BOXES_MAX 4096u
+int vrt_write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements);        /* data in host memory */
+int vrt_write_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements); /* data in device memory, 2-byte aligned */
+int vrt_grid_write_boxes(vrt_grid *g, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements);    /* the CPU twin */
 /* Copy of bytes [byte_offset, byte_offset + nbytes) of scene buffer `id` as frames see it after every upload and edit so far
  * (blocking).  VRT_E_INVALID_ARG: bad id or a NULL dst with nbytes > 0; VRT_E_OUT_OF_RANGE: beyond the buffer. */
 int vrt_read_buffer(vrt_ctx *ctx, vrt_buffer_id id, uint64_t byte_offset, void *dst, uint64_t nbytes);

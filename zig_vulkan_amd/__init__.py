@@ -6,8 +6,8 @@ reference's scene / camera / renderer API used by tests and bench.py.
 Importing it loads the shared library and fails loudly if it is absent.
 """
 from . import _lib
-from .voxel_rt import (AUX_PLANES, AUX_PLANE_DTYPES, BOX_QUERY_DTYPE, BOX_RESULT_DTYPE, VOXEL_EMPTY, BrickGrid, Camera, CameraConfig, Config, MATERIAL_DTYPE, RAY_HIT_DTYPE, RAY_QUERY_DTYPE, SHAPE_DTYPE, Sun, SunConfig, VoxelRT,
-                       box, box_queries, default_materials, ray_queries, read_box_layout, read_box_views, shape_records, sphere)
+from .voxel_rt import (AUX_PLANES, AUX_PLANE_DTYPES, BOX_QUERY_DTYPE, BOX_RESULT_DTYPE, VOXEL_EMPTY, VOXEL_KEEP, BrickGrid, Camera, CameraConfig, Config, MATERIAL_DTYPE, RAY_HIT_DTYPE, RAY_QUERY_DTYPE, SHAPE_DTYPE, Sun, SunConfig, VoxelRT,
+                       box, box_queries, default_materials, ray_queries, read_box_layout, read_box_views, shape_records, sphere, write_box_data)
 
-__all__ = ["AUX_PLANES", "AUX_PLANE_DTYPES", "BOX_QUERY_DTYPE", "BOX_RESULT_DTYPE", "VOXEL_EMPTY", "BrickGrid", "Camera", "CameraConfig", "Config", "MATERIAL_DTYPE", "RAY_HIT_DTYPE", "RAY_QUERY_DTYPE", "SHAPE_DTYPE", "Sun", "SunConfig",
-           "VoxelRT", "box", "box_queries", "default_materials", "ray_queries", "read_box_layout", "read_box_views", "shape_records", "sphere", "_lib"]
+__all__ = ["AUX_PLANES", "AUX_PLANE_DTYPES", "BOX_QUERY_DTYPE", "BOX_RESULT_DTYPE", "VOXEL_EMPTY", "VOXEL_KEEP", "BrickGrid", "Camera", "CameraConfig", "Config", "MATERIAL_DTYPE", "RAY_HIT_DTYPE", "RAY_QUERY_DTYPE", "SHAPE_DTYPE", "Sun", "SunConfig",
+           "VoxelRT", "box", "box_queries", "default_materials", "ray_queries", "read_box_layout", "read_box_views", "shape_records", "sphere", "write_box_data", "_lib"]

@@ -189,6 +189,8 @@ PAINT_ANY = 0xFFFFFFFF          # VRT_PAINT_ANY
 RAY_RAW_DIRECTION = 1 << 0  # VRT_RAY_RAW_DIRECTION
 VOXEL_EMPTY = 0xFFFF        # VRT_VOXEL_EMPTY
 READ_BOXES_MAX = 4096       # VRT_READ_BOXES_MAX
+VOXEL_KEEP = 0xFFFE         # VRT_VOXEL_KEEP
+WRITE_BOXES_MAX = 4096      # VRT_WRITE_BOXES_MAX
 
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
@@ -281,6 +283,9 @@ SIGNATURES = {
     "vrt_read_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_read_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_grid_read_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_write_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_write_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_grid_write_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_remove_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

@@ -554,6 +554,140 @@ int BrickGrid::paintShapes(const vrt_shape *shapes, uint64_t n, uint32_t only, u
     return VRT_OK;
 }
 
+bool BrickGrid::writeRows(const WriteBox &w, const uint16_t *data, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t set[64], uint8_t clear[64], bool *has_set,
+                          bool *has_clear) const {
+    const uint32_t b = brick_dimension_;
+    std::fill(set, set + b * b, (uint8_t)0);
+    std::fill(clear, clear + b * b, (uint8_t)0);
+    *has_set = *has_clear = false;
+    const ClippedShape &s = w.c;
+    const uint32_t x0 = std::max(s.lo[0], cx * b), x1 = std::min(s.hi[0], cx * b + (b - 1u));
+    for (uint32_t fy = std::max(s.lo[1], cy * b); fy <= std::min(s.hi[1], cy * b + (b - 1u)); fy++)
+        for (uint32_t z = std::max(s.lo[2], cz * b); z <= std::min(s.hi[2], cz * b + (b - 1u)); z++) {
+            const uint16_t *row = data + write_element(w, x0, fy, z); // the elements of x0..x1 are adjacent
+            uint32_t ms = 0, mc = 0;
+            for (uint32_t x = x0; x <= x1; x++) {
+                const uint32_t v = row[x - x0];
+                if (!write_element_ok(v)) return false;
+                if (v <= 255u) ms |= 1u << (x - cx * b);
+                else if (v == VRT_VOXEL_EMPTY) mc |= 1u << (x - cx * b);
+            }
+            const uint32_t r = (z - cz * b) + b * (fy - cy * b); // voxelAt of the row's x = 0, over B
+            set[r] = (uint8_t)ms, clear[r] = (uint8_t)mc;
+            *has_set = *has_set || ms, *has_clear = *has_clear || mc;
+        }
+    return true;
+}
+
+int BrickGrid::writeBoxes(const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements, std::string *why) {
+    const vrt_grid_state &d = device_state_;
+    const uint32_t b = brick_dimension_;
+    const uint32_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
+    auto refuse = [&](int rc, const std::string &text) {
+        if (why) *why = text;
+        return rc;
+    };
+    std::string reason;
+    uint64_t total = 0;
+    int rc = screen_write_boxes(boxes, n, b, dim, data, data_elements, &total, &reason);
+    if (rc != VRT_OK) return refuse(rc, reason);
+    std::vector<WriteBox> in; // the boxes that reach into the grid
+    uint64_t base = 0, items = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const ReadBoxShape s = read_box_shape(boxes[k], b);
+        WriteBox w;
+        if (clip_write_box(boxes[k], dim, s, base, &w)) {
+            if ((items += shape_items(w.c, b)) >= kShapeItemsEnd) // the device's bound on a batch, so that the twin refuses what the device refuses
+                return refuse(VRT_E_OUT_OF_RANGE, "box " + std::to_string(k) + ": the batch's work items reach 2^31");
+            in.push_back(w);
+        }
+        base += s.volume;
+    }
+    uint8_t set[64], clear[64];
+    bool has_set, has_clear;
+    // all or nothing: every element of a voxel inside the grid screened, and the cells that need a brick counted, before the first write
+    std::vector<size_t> fresh;
+    for (const WriteBox &w : in)
+        for_cells(w.c, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (rc != VRT_OK) return;
+            if (!writeRows(w, data, cx, cy, cz, set, clear, &has_set, &has_clear)) {
+                rc = refuse(VRT_E_INVALID_ARG, "an element of a voxel inside the grid is neither a material 0..255 nor VRT_VOXEL_EMPTY nor VRT_VOXEL_KEEP");
+                return;
+            }
+            if (!((brick_statuses[g / 32] >> (g % 32)) & 1u)) {
+                if (has_set) fresh.push_back(g);
+            } else if ((has_set || has_clear) && (brick_indices[g] >= brick_alloc_ || brick_start_indices[brick_indices[g]] == 0xFFFFFFFFu)) {
+                rc = refuse(VRT_E_STATE, "a loaded cell names a brick without material entries");
+            }
+        });
+    if (rc != VRT_OK) return rc;
+    std::sort(fresh.begin(), fresh.end());
+    const uint64_t need = (uint64_t)(std::unique(fresh.begin(), fresh.end()) - fresh.begin()); // (two boxes may share a cell)
+    if (activeBricks() + need > brick_alloc_ || material_cursor_.load(std::memory_order_relaxed) + need * brick_bits_ > material_capacity_)
+        return refuse(VRT_E_OOM, "the batch needs " + std::to_string(need) + " new bricks: brick_alloc or the material entries are exhausted");
+
+    // vrt_grid_insert_many of the voxels whose element is a material, as fillShapes applies a shape's
+    for (const WriteBox &w : in)
+        for_cells(w.c, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            (void)writeRows(w, data, cx, cy, cz, set, clear, &has_set, &has_clear);
+            if (!has_set) return; // (a cell without a voxel to insert gets no brick)
+            uint32_t brick;
+            if ((brick_statuses[g / 32] >> (g % 32)) & 1u) {
+                brick = brick_indices[g];
+            } else { // Grid.zig:147, 160-168, 188-193
+                brick = active_bricks_.fetch_add(1, std::memory_order_relaxed);
+                brick_start_indices[brick] = material_cursor_.fetch_add(brick_bits_, std::memory_order_relaxed) & 0x7FFFFFFFu;
+                bricks_start_indices_delta.registerDeltaUnlocked(brick);
+                brick_statuses[g / 32] |= 1u << (g % 32);
+                brick_indices[g] = brick;
+            }
+            brick_statuses_delta.registerDeltaUnlocked(g / 32); // (insert registers both for every voxel, loaded cell or not)
+            brick_indices_delta.registerDeltaUnlocked(g);
+            const size_t occupancy_from = (size_t)brick * brick_bytes_, start = brick_start_indices[brick] & 0x7FFFFFFFu;
+            for (uint32_t r = 0; r < b * b; r++) {
+                const uint32_t mask = set[r];
+                if (!mask) continue;
+                const uint32_t bit = r * b; // the row's first voxel within the brick
+                brick_occupancy[occupancy_from + bit / 8] |= (uint8_t)(mask << (bit % 8));
+                bricks_occupancy_delta.registerDeltaUnlocked(occupancy_from + bit / 8);
+                const uint32_t fy = cy * b + r / b, z = cz * b + r % b;
+                for (uint32_t k = 0; k < b; k++)
+                    if ((mask >> k) & 1u) material_indices[start + bit + k] = (uint8_t)data[write_element(w, cx * b + k, fy, z)];
+                material_indices_delta.registerDeltaUnlocked(start + bit + (uint32_t)__builtin_ctz(mask));
+                material_indices_delta.registerDeltaUnlocked(start + bit + 31u - (uint32_t)__builtin_clz(mask));
+            }
+        });
+    // vrt_grid_remove_many of the voxels whose element is VRT_VOXEL_EMPTY, as clearShapes applies a shape's
+    std::vector<size_t> touched; // the loaded cells that hold a voxel to remove
+    for (const WriteBox &w : in)
+        for_cells(w.c, b, d, [&](uint32_t cx, uint32_t cy, uint32_t cz, size_t g) {
+            if (!((brick_statuses[g / 32] >> (g % 32)) & 1u)) return; // not loaded: a no-op
+            (void)writeRows(w, data, cx, cy, cz, set, clear, &has_set, &has_clear);
+            if (!has_clear) return;
+            touched.push_back(g);
+            const size_t occupancy_from = (size_t)brick_indices[g] * brick_bytes_;
+            for (uint32_t r = 0; r < b * b; r++) {
+                const uint32_t bit = r * b;
+                uint8_t &byte = brick_occupancy[occupancy_from + bit / 8];
+                const uint8_t lost = byte & (uint8_t)(clear[r] << (bit % 8));
+                if (!lost) continue; // already empty: a no-op
+                byte &= (uint8_t)~lost;
+                bricks_occupancy_delta.registerDeltaUnlocked(occupancy_from + bit / 8);
+            }
+        });
+    for (const size_t g : touched) { // after the whole batch, as removeImpl does
+        const uint32_t bit = 1u << (g % 32);
+        if (!(brick_statuses[g / 32] & bit)) continue; // (the cell came up twice)
+        const uint8_t *occ = &brick_occupancy[(size_t)brick_indices[g] * brick_bytes_];
+        bool any = false;
+        for (uint32_t k = 0; k < brick_bytes_ && !any; k++) any = occ[k] != 0;
+        if (any) continue;
+        brick_statuses[g / 32] &= ~bit;
+        brick_statuses_delta.registerDeltaUnlocked(g / 32);
+    }
+    return VRT_OK;
+}
+
 DeviceDataDelta *BrickGrid::deltaFor(vrt_buffer_id id) {
     switch (id) {
         case VRT_BUF_BRICK_STATUS: return &brick_statuses_delta;

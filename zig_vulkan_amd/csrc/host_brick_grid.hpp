@@ -99,6 +99,15 @@ public:
     // on the device would reach 2^31.  Delta: material_indices from the first to the last entry written; none where nothing was painted.
     int paintShapes(const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted);
 
+    // Dense box writes (the reference has none: include/vrt_hip.h defines them): readBoxes' boxes and layout taken in.  Of the voxels
+    // inside the grid, those whose element is a material are inserted as insertUnlocked inserts them (boxes in array order, within a box
+    // the cells that hold one in ascending grid index), then those whose element is VRT_VOXEL_EMPTY are removed as removeManyUnlocked
+    // removes them; VRT_VOXEL_KEEP leaves a voxel as it is; elements of voxels outside the grid are not read.  Arrays and deltas are
+    // those of the two calls, worked per cell and row.  All or nothing: the batch is screened (screen_write_boxes; boxes that overlap
+    // inside the grid and elements that are none of the three kinds are VRT_E_INVALID_ARG) and the bricks it needs are counted
+    // (VRT_E_OOM) before the first write; *why (may be null) says why.  Single-threaded.
+    int writeBoxes(const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements, std::string *why = nullptr);
+
     // State.zig:5-11
     uint32_t brickDimension() const { return brick_dimension_; }
     uint32_t brickBits() const { return brick_bits_; }
@@ -128,6 +137,10 @@ private:
     int removeImpl(const uint32_t *xyz, uint64_t n);
     // the shape's voxels in cell (cx, cy, cz) (cy flipped): per row (z % B + B * (fy % B)) its B bits along x; false: none
     bool shapeRows(const ClippedShape &s, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t rows[64]) const;
+    // a write's voxels in cell (cx, cy, cz) (cy flipped), per row as shapeRows gives them: those to insert and those to remove; false:
+    // an element that is none of the three kinds
+    bool writeRows(const WriteBox &w, const uint16_t *data, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t set[64], uint8_t clear[64], bool *has_set,
+                   bool *has_clear) const;
 
     uint32_t brick_dimension_ = 4, brick_bits_ = 64, brick_bytes_ = 8;
     uint64_t brick_alloc_ = 0;

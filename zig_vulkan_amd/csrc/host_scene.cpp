@@ -292,6 +292,11 @@ int vrt_grid_paint_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n, uint
     return reinterpret_cast<vrt::BrickGrid *>(g)->paintShapes(shapes, n, only, painted);
 }
 
+int vrt_grid_write_boxes(vrt_grid *g, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->writeBoxes(boxes, n, data, data_elements);
+}
+
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g) {
     return g ? &reinterpret_cast<const vrt::BrickGrid *>(g)->deviceState() : nullptr;
 }

@@ -1,6 +1,7 @@
 // vrt_edit.hip — batched voxel inserts and removals behind the C ABI (vrt_insert_voxels, vrt_remove_voxels and their _device forms),
-// brick compaction (vrt_compact_bricks), the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene
-// buffer (vrt_read_buffer): their kernels
+// brick compaction (vrt_compact_bricks), the shape, paint and dense box edits (vrt_fill_shapes, vrt_clear_shapes, vrt_paint_shapes,
+// vrt_write_boxes), the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer):
+// their kernels
 // vrt_edit_* and their host side.
 // BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
 // vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
@@ -69,6 +70,24 @@
 //   vrt_edit_finish
 // (vrt_edit_table is not launched: no cell's scratch word is touched.)
 //
+// A dense box write (vrt_write_boxes, vrt_write_boxes_device) is the seventh mode, EditArgs::op = kEditOpWrite, on the
+// work items of the shape edits: one ShapeRec per box that reaches into the grid, its range the box's part inside the grid, and in the
+// sphere's fields where the box's elements lie in EditArgs::data.  An item reads the elements of its word's voxels, row by row, into two
+// masks: set (a material) and clear (VRT_VOXEL_EMPTY); VRT_VOXEL_KEEP and the voxels outside the box are in neither.  It is a fill of
+// `set` with a material per voxel and a clear of `clear` in one chain; the boxes are disjoint, so no voxel has two writers:
+//   vrt_edit_begin (+ the scan of binding 5, as above)
+//   vrt_edit_validate     per item: box, cell, word, the two masks; an element that is none of the three kinds is an error; a zero
+//                         set | clear makes the item inert.  Loaded cells: brick and entry as for a fill and, if clear is not zero, the
+//                         cell's election as for a clear.  Others: if set is not zero, atomicMin for the ranking as for a fill (a cell is
+//                         loaded or not when the call begins, so the one scratch word serves both; bit 31 of vinfo says which)
+//   vrt_edit_count / _scan_groups / _rank / _resolve   unchanged in meaning
+//   vrt_edit_write        phase 0: atomicOr of set, atomicAnd of ~clear; the material bytes of set, read again from the elements (a whole
+//                         row as one 8-byte store, a whole nibble as a dword, the rest as bytes: never an entry the item does not set,
+//                         another box may own it); the first item of a new cell writes the cell's words
+//   vrt_edit_write        phase 1 (a kernel boundary after every bit): as for removals
+//   vrt_edit_table        clears the cells' scratch words (behind phase 1, which reads them)
+//   vrt_edit_finish
+//
 //   mode      op  validate  count scan_groups rank resolve  table  write       finish
 //   insert    0   x         x     x           x    x        x      x           x
 //   remove    1   x                                         x      phases 0, 1 x
@@ -76,6 +95,7 @@
 //   fill      3   x         x     x           x    x        x      x           x
 //   clear     4   x                                         x      phases 0, 1 x
 //   paint     5   x                                                x           x
+//   write     6   x         x     x           x    x        last   phases 0, 1 x
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -83,6 +103,7 @@
 #include <string>
 #include <vector>
 #include "vrt_ctx.h"
+#include "vrt_read_boxes.h"
 #include "vrt_shapes.h"
 
 namespace vrt {
@@ -90,7 +111,8 @@ namespace vrt {
 constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-voxel kernels (four waves)
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
-constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4, kEditOpPaint = 5; // EditArgs::op
+constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4, kEditOpPaint = 5,
+                   kEditOpWrite = 6; // EditArgs::op
 constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
@@ -99,6 +121,7 @@ constexpr uint32_t kEditErrRange = 1u << 1;  // a voxel outside the grid        
 constexpr uint32_t kEditErrCell = 1u << 2;   // a loaded cell names a brick at or beyond the allocated bricks -> VRT_E_STATE
 constexpr uint32_t kEditErrOom = 1u << 3;    // bricks or material entries exhausted                       -> VRT_E_OOM
 constexpr uint32_t kEditErrSlot = 1u << 4;   // compaction: an allocated brick's start is not slot * B^3   -> VRT_E_STATE
+constexpr uint32_t kEditErrValue = 1u << 5;  // write: an element that is no material, not EMPTY and not KEEP -> VRT_E_INVALID_ARG
 
 // The allocation state that binding 5 defines (kept on the device, current across inserts).  While the scan of binding 5 runs,
 // first_unset / last_set_end / type_bits / max_start accumulate; vrt_edit_state turns them into bricks / cursor / ok.
@@ -130,12 +153,12 @@ struct EditStatus {
 // and where its items lie.  Only shapes that hold a voxel of the grid's range are uploaded.
 struct ShapeRec {
     uint32_t lo[3], hi[3];  // the voxels considered
-    uint32_t centre[3];     // sphere: the centre modulo 2^32
-    uint32_t r2;            // sphere: r^2
-    uint32_t kind, material;
+    uint32_t centre[3];     // sphere: the centre modulo 2^32.  A box of a write: WriteBox::origin
+    uint32_t r2;            // sphere: r^2.  A box of a write: its side along x
+    uint32_t kind, material; // (a box of a write: kind VRT_SHAPE_BOX, and in `material` its side along z)
     uint32_t first;         // items of the shapes before this one
     uint32_t ncx, ncxz;     // cells of its clipped cell box along x, and in one layer of y
-    uint32_t _pad;
+    uint32_t base;          // a box of a write: its first element
 };
 static_assert(sizeof(ShapeRec) == 64, "ShapeRec is four dwordx4");
 
@@ -154,7 +177,7 @@ struct EditArgs {
     uint32_t n;
     uint32_t groups;         // ceil(n / kEditBlock)
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
-    uint32_t op;             // kEditOpInsert / kEditOpRemove / kEditOpCompact / kEditOpFill / kEditOpClear / kEditOpPaint (uniform: every kernel of a chain sees the same)
+    uint32_t op;             // kEditOpInsert / ... / kEditOpPaint / kEditOpWrite (uniform: every kernel of a chain sees the same)
     uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks;
                              // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells
     // scratch (the context's, grown on demand)
@@ -177,6 +200,7 @@ struct EditArgs {
     uint64_t material_entries;      // bytes of binding 6 (brick_alloc * B^3)
     uint32_t cells;                 // compaction: cells of the grid (n = max(cells, brick_alloc): the threads of its per-cell kernels)
     uint32_t only;                  // paint: the material an entry must hold to be painted (VRT_PAINT_ANY: whatever it holds)
+    const uint16_t *data;           // write: the boxes' elements (2-byte aligned; behind every older member, whose offsets stay)
 };
 
 } // namespace vrt
@@ -332,6 +356,108 @@ __device__ inline uint32_t shape_mask(const ShapeRec &r, uint32_t b, const Shape
     return word_mask(cell_shape(r, b, it.x, it.y, it.z), b, it.word);
 }
 
+// ---- dense box writes: an item's word as the box's elements give it ----
+struct WordMasks {
+    uint32_t set, clear, bad; // the word's voxels whose element is a material / VRT_VOXEL_EMPTY / none of the three kinds
+};
+constexpr uint32_t kKeepPair = VRT_VOXEL_KEEP | VRT_VOXEL_KEEP << 16; // two elements that leave their voxels alone
+
+// Elements 2 pair, 2 pair + 1 of a row, the first of them in the low half: those of the voxels in box_row, VRT_VOXEL_KEEP for the others,
+// which are not read (they are another row's, another box's or nobody's).  row: the address that the element of the row's voxel 0 has
+// or, outside the box, would have (an integer: up to B - 1 elements before the first one that exists); the pairs' offsets from it are
+// constants.  One dword where both are wanted and the address allows, else 2-byte loads.
+__device__ inline uint32_t load_pair(uintptr_t row, uint32_t box_row, uint32_t pair) {
+    const uint32_t want = (box_row >> (2u * pair)) & 3u;
+    const uint16_t *q = reinterpret_cast<const uint16_t *>(row) + 2u * pair;
+    if (want == 3u && !(row & 3u)) return *reinterpret_cast<const uint32_t *>(q);
+    uint32_t w = kKeepPair;
+    if (want & 1u) w = (w & 0xFFFF0000u) | q[0];
+    if (want & 2u) w = (w & 0x0000FFFFu) | (uint32_t)q[1] << 16;
+    return w;
+}
+
+// the pair's two elements sorted into the masks; bit: the first element's voxel within the word
+__device__ inline void sort_pair(uint32_t w, uint32_t bit, WordMasks &m) {
+    for (uint32_t h = 0; h < 2u; h++) {
+        const uint32_t e = h ? w >> 16 : w & 0xFFFFu, v = 1u << (bit + h);
+        if (e <= 255u) m.set |= v;
+        else if (e == VRT_VOXEL_EMPTY) m.clear |= v;
+        else if (e != VRT_VOXEL_KEEP) m.bad |= v;
+    }
+}
+
+// the material bytes of a pair of elements that are materials
+__device__ inline uint32_t pair_bytes(uint32_t w) { return (w & 0xFFu) | ((w >> 8) & 0xFF00u); }
+
+// entries[j] = byte j of `four` for the bits j of nibble: one dword for a whole nibble on a 4-byte aligned entry `at`, else bytes
+__device__ inline void store_nibble(uint8_t *entries, uint32_t at, uint32_t nibble, uint32_t four) {
+    if (nibble == 15u && !(at & 3u)) {
+        *reinterpret_cast<uint32_t *>(entries) = four;
+        return;
+    }
+    for (uint32_t j = 0; j < 4u; j++)
+        if ((nibble >> j) & 1u) entries[j] = (uint8_t)(four >> (8u * j));
+}
+
+// The item's word of box r of a write: the word's rows that lie in the box's part inside the grid, each row's elements loaded (one
+// 16-byte load, 8 bytes for 4^3 bricks, where the row lies in the box whole and its first element is so aligned; pairs otherwise) and
+// sorted into the masks.  kStore: the material bytes of the row's set bits stored as well; slot is the entry of binding 6 of the word's
+// bit 0 (slot + 31 lies within the brick's B^3 entries).  Every element that is loaded belongs to a voxel of the box inside the grid: it
+// is an element of the batch.  The loop is rolled and holds one row's four pairs in four registers, indexed by constants alone.
+template <bool kStore>
+__device__ inline WordMasks data_word(const EditArgs &a, const ShapeRec &r, const ShapeItem &it, uint32_t slot) {
+    WordMasks m = {0u, 0u, 0u};
+    const uint32_t b = a.b;
+    const CellShape c = cell_shape(r, b, it.x, it.y, it.z);
+    if (c.box_row == 0u) return m;
+    const uint32_t rows = 32u / b, log_b = b == 8u ? 3u : 2u;
+    // WriteBox's element (vrt_read_boxes.h) of the voxel 0 of the cell's row z = 0, fy = 0, modulo 2^32, and what a step in z and in fy
+    // adds to it: the box and the cell are in these three values from here on
+    const uint32_t sx = r.r2, sxz = r.r2 * r.material;
+    const uint32_t e0 = r.base + (it.x - r.centre[0]) + sx * (it.z - r.centre[2]) + sxz * (r.centre[1] - it.y);
+    uint32_t row = it.word * rows; // the word's rows: a multiple of rows, and the rows - 1 behind it
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable) // (rolled, as word_mask's: the kernels' 32 VGPRs)
+    do {
+        const uint32_t z = row & (b - 1u), y = row >> log_b;
+        if (!((c.rows >> z) & (c.rows >> (8u + y)) & 1u)) continue;
+        // the row's voxel 0: an element of the batch, below 2^31, or up to B - 1 before one (so the index is exact as an int32_t)
+        const uintptr_t at0 = reinterpret_cast<uintptr_t>(a.data) + (intptr_t)(int32_t)(e0 + sx * z - sxz * y) * 2;
+        const uint16_t *p = reinterpret_cast<const uint16_t *>(at0);
+        // (the row's bits behind an empty asm: what the pairs test of them is then formed here, per row, in a register or two; left to
+        // itself the compiler forms the dozen tests of this loop-invariant value once, ahead of the loop, and keeps them all)
+        uint32_t box_row = c.box_row;
+        asm volatile("" : "+v"(box_row));
+        uint32_t w0, w1, w2 = kKeepPair, w3 = kKeepPair;
+        if (box_row == (1u << b) - 1u && !(at0 & (2u * b - 1u))) {
+            if (b == 8u) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(p);
+                w0 = v.x, w1 = v.y, w2 = v.z, w3 = v.w;
+            } else {
+                const uint2 v = *reinterpret_cast<const uint2 *>(p);
+                w0 = v.x, w1 = v.y;
+            }
+        } else {
+            w0 = load_pair(at0, box_row, 0u), w1 = load_pair(at0, box_row, 1u);
+            if (b == 8u) w2 = load_pair(at0, box_row, 2u), w3 = load_pair(at0, box_row, 3u);
+        }
+        const uint32_t shift = (row & (rows - 1u)) * b; // the row's first voxel within the word
+        sort_pair(w0, shift, m), sort_pair(w1, shift + 2u, m);
+        if (b == 8u) sort_pair(w2, shift + 4u, m), sort_pair(w3, shift + 6u, m);
+        if (kStore) {
+            const uint32_t row_set = (m.set >> shift) & ((1u << b) - 1u), at = slot + shift;
+            const uint32_t m0 = pair_bytes(w0) | pair_bytes(w1) << 16, m1 = pair_bytes(w2) | pair_bytes(w3) << 16;
+            uint8_t *entries = a.material + at;
+            if (row_set == 0xFFu && !(at & 7u)) {
+                *reinterpret_cast<uint2 *>(entries) = make_uint2(m0, m1);
+            } else if (row_set) {
+                store_nibble(entries, at, row_set & 15u, m0);
+                if (b == 8u) store_nibble(entries + 4u, at + 4u, row_set >> 4, m1);
+            }
+        }
+    } while (++row & (rows - 1u));
+    return m;
+}
+
 } // namespace
 
 extern "C" {
@@ -451,9 +577,54 @@ __device__ inline void shape_validate(const EditArgs &a) {
     wave_atomic_or(&a.out->err, err);
 }
 
+// a write's items (every lane gets to the reduction)
+__device__ inline void box_validate(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool ok = a.state->ok != 0;
+    const uint32_t bricks = a.state->bricks;
+    uint32_t cell = kEditNone, info = 0, err = 0;
+    if (i < a.n && ok) {
+        const ShapeItem it = shape_item(a, i);
+        const WordMasks m = data_word<false>(a, shape_rec(a, it.shape), it, 0u);
+        if (m.bad) {
+            err = kEditErrValue;
+        } else if (m.set | m.clear) { // (neither: the item is inert, cell stays kEditNone)
+            const uint32_t log_b = a.b == 8u ? 3u : 2u;
+            const uint32_t g = (it.x >> log_b) + a.dim_x * ((it.z >> log_b) + a.dim_z * (it.y >> log_b)); // gridAt
+            const uint32_t first_bit = it.word << 5;                                                        // voxelAt of the word's bit 0
+            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
+                const uint32_t brick = a.index[g];
+                if (brick >= bricks) {
+                    err = kEditErrCell;
+                } else {
+                    a.vbrick[i] = brick;
+                    a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + first_bit; // the entry of binding 6 of the word's bit 0
+                    if (m.clear) atomicMin(&a.cell_first[g], i);             // the cell's elected item, for phase 1
+                    cell = g;
+                    info = first_bit;
+                }
+            } else if (m.set) { // (a removal in a cell that is not loaded: a no-op)
+                atomicMin(&a.cell_first[g], i); // the minimum ranks the new cells box-major, then by cell index
+                cell = g;
+                info = 0x80000000u | first_bit;
+            }
+        }
+    }
+    if (i < a.n) {
+        a.vcell[i] = cell;
+        a.vinfo[i] = info;
+    }
+    if (!ok && i == 0) err = kEditErrShape;
+    wave_atomic_or(&a.out->err, err);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
     if (a.op == kEditOpCompact) {
         compact_validate(a);
+        return;
+    }
+    if (a.op == kEditOpWrite) {
+        box_validate(a);
         return;
     }
     if (a.op >= kEditOpFill) { // fill, clear, paint
@@ -600,7 +771,8 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     if (i >= a.n) return;
     const uint32_t cell = a.vcell[i];
-    if (a.op == kEditOpRemove || a.op == kEditOpClear) { // (removal used the words of the loaded cells it touched, and needs no last writer)
+    if (a.op == kEditOpRemove || a.op == kEditOpClear || a.op == kEditOpWrite) { // (removal used the words of the loaded cells it touched, and needs no last
+                                                                                 // writer; a write those and the new cells', and has one writer per entry)
         if (cell != kEditNone) a.cell_first[cell] = kEditNone;
         return;
     }
@@ -800,13 +972,57 @@ __device__ inline void paint_write(const EditArgs &a) {
     if (lane_id() == 0 && count) atomicAdd(reinterpret_cast<unsigned long long *>(&a.out->painted), (unsigned long long)count);
 }
 
+// phase 0 of a write's items (every lane of the wave gets to the three pairs of reductions); phase 1 is removal's
+__device__ inline void box_write(const EditArgs &a) {
+    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+    const bool active = i < a.n && a.vcell[i] != kEditNone;
+    WordMasks m = {0u, 0u, 0u};
+    uint32_t word = 0;
+    if (active) { // the masks again, and the material bytes of `set` on the way
+        const ShapeItem it = shape_item(a, i);
+        word = it.word;
+        m = data_word<true>(a, shape_rec(a, it.shape), it, a.vslot[i]);
+    }
+    uint32_t lo = kEditNone, hi = 0;
+    if (active && (a.vinfo[i] & 0x40000000u)) { // the first item of a cell that was not loaded: Grid.zig:160-168, 188-193
+        const uint32_t cell = a.vcell[i], brick = a.vbrick[i];
+        atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
+        a.index[cell] = brick;
+        a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
+        lo = hi = cell;
+    }
+    wave_atomic_min(&a.out->cell_lo, lo);
+    wave_atomic_max(&a.out->cell_hi, hi);
+    lo = kEditNone, hi = 0;
+    if (active) { // the bytes that gained a bit (Grid.zig:180-185) or lost one
+        word += a.vbrick[i] * (a.brick_bytes >> 2);
+        uint32_t changed = m.set;
+        if (m.set) atomicOr(&a.occupancy[word], m.set);
+        if (m.clear) changed |= atomicAnd(&a.occupancy[word], ~m.clear) & m.clear;
+        if (changed) lo = word * 4u + ((uint32_t)__builtin_ctz(changed) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(changed)) >> 3);
+    }
+    wave_atomic_min(&a.out->occ_lo, lo);
+    wave_atomic_max(&a.out->occ_hi, hi);
+    lo = kEditNone, hi = 0;
+    if (m.set) {
+        const uint32_t slot = a.vslot[i];
+        lo = slot + (uint32_t)__builtin_ctz(m.set), hi = slot + 31u - (uint32_t)__builtin_clz(m.set);
+    }
+    wave_atomic_min(&a.out->mat_lo, lo);
+    wave_atomic_max(&a.out->mat_hi, hi);
+}
+
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     if (a.out->err) return;
+    if (a.op == kEditOpWrite && a.phase == 0) {
+        box_write(a);
+        return;
+    }
     if (a.op == kEditOpPaint) {
         paint_write(a);
         return;
     }
-    if (a.op == kEditOpRemove || a.op == kEditOpClear) {
+    if (a.op == kEditOpRemove || a.op == kEditOpClear || a.op == kEditOpWrite) { // (a write: its phase 1)
         remove_write(a);
         return;
     }
@@ -1026,6 +1242,11 @@ EditSteps insert_steps(uint32_t g) {
 EditSteps remove_steps(uint32_t g) {
     return {{vrt_edit_validate, g}, {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
 }
+// ... a dense box write: a fill's ranking, a clear's two phases, and the scratch words cleared behind the phase that reads them
+EditSteps write_steps(uint32_t g) {
+    return {{vrt_edit_validate, g}, {vrt_edit_count, g}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, g}, {vrt_edit_resolve, g},
+            {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
+}
 // ... a paint:
 EditSteps paint_steps(uint32_t g) { return {{vrt_edit_validate, g}, {vrt_edit_write, g}}; }
 // ... compaction: over the cells (and bricks), over the bricks (also what vrt_edit_scan_groups scans), and its grid-stride passes
@@ -1060,6 +1281,8 @@ int run_edit(vrt_ctx *ctx, vrt::EditArgs &a, const EditSteps &steps, bool drop_c
 int edit_error(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t applies, const char *nothing) {
     const uint32_t err = s.err & applies;
     if (err & vrt::kEditErrShape) return not_shaped(ctx);
+    if (err & vrt::kEditErrValue)
+        return fail(ctx, VRT_E_INVALID_ARG, std::string("an element of a voxel inside the grid is neither a material 0..255 nor VRT_VOXEL_EMPTY nor VRT_VOXEL_KEEP") + nothing);
     if (err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, std::string("a voxel lies outside the grid") + nothing);
     if (err & vrt::kEditErrSlot)
         return fail(ctx, VRT_E_STATE, std::string("an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3") + nothing);
@@ -1075,6 +1298,7 @@ constexpr uint32_t kErrsOfCompact = vrt::kEditErrShape | vrt::kEditErrSlot | vrt
 constexpr uint32_t kErrsOfFill = vrt::kEditErrShape | vrt::kEditErrCell | vrt::kEditErrOom;
 constexpr uint32_t kErrsOfClear = vrt::kEditErrShape | vrt::kEditErrCell;
 constexpr uint32_t kErrsOfPaint = kErrsOfClear;
+constexpr uint32_t kErrsOfWrite = kErrsOfFill | vrt::kEditErrValue;
 
 // The derived structures follow exactly what was written (refresh_derived, before the next frame or query): the status ranges of the
 // buffers the op writes (`writes`: a bit per vrt_buffer_id), marked dirty.  start_first: the first of the s.new_bricks entries of
@@ -1212,10 +1436,80 @@ int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t op, 
     return VRT_OK;
 }
 
+// n boxes (host memory) written from their elements (host: data is host memory, staged into device memory behind the records; else
+// device memory, read in place): the batch screened on the host, one record per box that reaches into the grid, then the chain as one
+// scene write.  The elements are screened on the device in both forms (vrt_edit_validate), before any kernel writes the scene.
+int write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements, bool host) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    const char *nothing = "; nothing was written";
+    if (n == 0) return VRT_OK;
+    const uint32_t b = ctx->cfg.brick_dimension;
+    std::string why;
+    uint64_t total = 0;
+    int rc = vrt::screen_read_boxes(boxes, n, b, data, data_elements, &total, &why, "data", "VRT_WRITE_BOXES_MAX");
+    if (rc != VRT_OK) return fail(ctx, rc, why + nothing);
+    if (!host && (reinterpret_cast<uintptr_t>(data) & 1u)) return fail(ctx, VRT_E_INVALID_ARG, std::string("data must be 2-byte aligned") + nothing);
+    if (total == 0) return VRT_OK;
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, "dense box writes are not available on a context of the multi-GPU pipeline");
+    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    const uint32_t dim[3] = {ctx->cfg.dim_x * b, ctx->cfg.dim_y * b, ctx->cfg.dim_z * b};
+    uint64_t first = 0, second = 0;
+    if (vrt::first_overlap(boxes, n, dim, &first, &second))
+        return fail(ctx, VRT_E_INVALID_ARG, "boxes " + std::to_string(first) + " and " + std::to_string(second) + " overlap inside the grid: the boxes of a write must be disjoint" + nothing);
+    std::vector<vrt::ShapeRec> recs;
+    uint64_t base = 0, items = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const vrt::ReadBoxShape s = vrt::read_box_shape(boxes[k], b);
+        vrt::WriteBox w;
+        if (vrt::clip_write_box(boxes[k], dim, s, base, &w)) {
+            vrt::ShapeRec r{};
+            uint64_t cells[3];
+            for (int j = 0; j < 3; j++) {
+                r.lo[j] = w.c.lo[j], r.hi[j] = w.c.hi[j], r.centre[j] = w.origin[j];
+                cells[j] = (uint64_t)(w.c.hi[j] / b) - w.c.lo[j] / b + 1u;
+            }
+            r.r2 = w.sx, r.kind = VRT_SHAPE_BOX, r.material = w.sz, r.base = w.base;
+            r.first = (uint32_t)items;
+            r.ncx = (uint32_t)cells[0];
+            r.ncxz = (uint32_t)(cells[0] * cells[2]);
+            items += vrt::shape_items(w.c, b); // (the sum is tested before it can wrap: items < 2^31 so far)
+            if (items >= vrt::kShapeItemsEnd)
+                return fail(ctx, VRT_E_OUT_OF_RANGE, "box " + std::to_string(k) + ": the batch's work items (one per occupancy word of every cell that a box's part inside the grid touches) reach 2^31" + nothing);
+            recs.push_back(r);
+        }
+        base += s.volume;
+    }
+    if (recs.empty()) return VRT_OK; // no box reaches into the grid: the device is not touched
+    DeviceGuard dg(ctx->device);
+    rc = edit_prepare(ctx, "dense box writes are");
+    if (rc != VRT_OK) return rc;
+    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
+    const uint64_t rec_bytes = recs.size() * sizeof(vrt::ShapeRec);
+    rc = stage_input(ctx, recs.data(), rec_bytes, host ? data : nullptr, host ? total * sizeof(uint16_t) : 0u);
+    if (rc == VRT_OK) rc = edit_scratch(ctx, items);
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, vrt::kEditOpWrite, nullptr, nullptr, (uint32_t)items);
+    a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
+    a.shape_count = (uint32_t)recs.size();
+    a.data = host ? reinterpret_cast<const uint16_t *>(ctx->d_edit_input + rec_bytes) : data; // (behind records of 64 bytes: aligned)
+    vrt::EditStatus s;
+    rc = run_edit(ctx, a, write_steps(a.groups), true, &s);
+    if (rc == VRT_OK) rc = edit_error(ctx, s, kErrsOfWrite, nothing);
+    if (rc != VRT_OK) return rc;
+    mark_written(ctx, s, kWritesOfInsert, s.bricks - s.new_bricks);
+    return VRT_OK;
+}
+
 } // namespace
 
 extern "C" {
 
+int vrt_write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) {
+    return write_boxes(ctx, boxes, n, data, data_elements, true);
+}
+int vrt_write_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) {
+    return write_boxes(ctx, boxes, n, data, data_elements, false);
+}
 int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, false); }
 int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, true); }
 int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, false); }

@@ -136,6 +136,15 @@ class BrickGrid:
         check(lib.vrt_grid_read_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data, total))
         return read_box_views(flat, bases, shapes)
 
+    def write_boxes(self, lo, hi, data) -> None:
+        """vrt_grid_write_boxes: read_boxes' boxes (which must be disjoint inside the grid) and layout taken in.  data: the list of
+        [x, y, z] arrays read_boxes returns, or one flat uint16 array (x fastest, then z, then y; box after box).  An element 0..255
+        makes its voxel solid with that material, VOXEL_EMPTY empties it, VOXEL_KEEP leaves it as it is; elements of voxels outside
+        the grid are ignored.  As insert_many of the materials followed by remove_many of the empties; all or nothing."""
+        q = box_queries(lo, hi)
+        flat = write_box_data(q, data)
+        check(lib.vrt_grid_write_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data if flat.size else None, flat.size))
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -299,6 +308,7 @@ BOX_QUERY_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("flags", 
 BOX_RESULT_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("count", np.uint64)])
 assert BOX_QUERY_DTYPE.itemsize == 32 and BOX_RESULT_DTYPE.itemsize == 32
 VOXEL_EMPTY = L.VOXEL_EMPTY
+VOXEL_KEEP = L.VOXEL_KEEP   # write_boxes: leave this voxel exactly as it is
 
 
 def box_queries(lo, hi) -> np.ndarray:
@@ -327,6 +337,23 @@ def read_box_views(flat, bases, shapes) -> list:
         box = flat[int(bases[k]):int(bases[k + 1])].reshape(sy, sz, sx)
         out.append(box.transpose(2, 0, 1) if isinstance(box, np.ndarray) else box.permute(2, 0, 1))
     return out
+
+
+def write_box_data(q: np.ndarray, data) -> np.ndarray:
+    """The elements of a write_boxes call as one flat uint16 array in read_boxes' layout.  data: that array already (None: no
+    elements), or per box of `q` an array indexed [x, y, z], as read_boxes returns them."""
+    if data is None:
+        return np.empty(0, dtype=np.uint16)
+    if isinstance(data, (list, tuple)):
+        _, shapes = read_box_layout(q)
+        assert len(data) == q.shape[0], "one array per box"
+        parts = []
+        for k, box in enumerate(data):
+            box = np.asarray(box)
+            assert box.shape == tuple(int(v) for v in shapes[k][[0, 1, 2]]), f"box {k}: the array is not [sx, sy, sz]"
+            parts.append(np.ascontiguousarray(box.transpose(1, 2, 0)).reshape(-1))   # [x, y, z] -> y, z, x with x fastest
+        return np.ascontiguousarray(np.concatenate(parts) if parts else np.empty(0), dtype=np.uint16)
+    return np.ascontiguousarray(data, dtype=np.uint16).reshape(-1)
 
 
 # vrt_shape (include/vrt_hip.h) as a numpy record
@@ -541,6 +568,23 @@ class VoxelRT:
         painted = C.c_uint64(0)
         self._check(self._lib.vrt_paint_shapes(self._h, s.ctypes.data, s.shape[0], L.PAINT_ANY if only is None else only, C.byref(painted)))
         return int(painted.value)
+
+    def write_boxes(self, lo, hi, data) -> None:
+        """BrickGrid.write_boxes on the scene the context holds (vrt_write_boxes): the boxes of read_boxes (disjoint inside the grid)
+        pasted from `data`, the list of [x, y, z] arrays read_boxes returns or one flat uint16 array in its layout; 0..255 a material,
+        VOXEL_EMPTY empty, VOXEL_KEEP untouched.  write_boxes(lo, hi, read_boxes(lo, hi)) changes no frame.  All or nothing.  Given a
+        flat torch int16 / uint16 tensor on the GPU (what read_boxes(device=True) returns), the elements are read in device memory
+        (vrt_write_boxes_device, behind torch's current stream)."""
+        q = box_queries(lo, hi)
+        if getattr(data, "is_cuda", False):
+            import torch
+            assert data.dtype in (torch.int16, torch.uint16), "a tensor of 2-byte elements"
+            flat = data.reshape(-1).contiguous()
+            torch.cuda.current_stream(flat.device).synchronize()  # (the elements are written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_write_boxes_device(self._h, q.ctypes.data, q.shape[0], flat.data_ptr() if flat.numel() else None, flat.numel()))
+            return
+        flat = write_box_data(q, data)
+        self._check(self._lib.vrt_write_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data if flat.size else None, flat.size))
 
     def compact_bricks(self) -> Tuple[int, int]:
         """BrickGrid.compact on the scene the context holds (vrt_compact_bricks): bindings 2-6 afterwards equal the host grid's arrays
