@@ -1,103 +1,65 @@
-// vrt_edit.hip — batched voxel inserts and removals behind the C ABI (vrt_insert_voxels, vrt_remove_voxels and their _device forms),
-// brick compaction (vrt_compact_bricks), the shape, paint and dense box edits (vrt_fill_shapes, vrt_clear_shapes, vrt_paint_shapes,
-// vrt_write_boxes), the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer):
-// their kernels
-// vrt_edit_* and their host side.
+// vrt_edit.hip — the edits of the uploaded scene behind the C ABI: batched voxel inserts and removals (vrt_insert_voxels,
+// vrt_remove_voxels and their _device forms), brick compaction (vrt_compact_bricks), the shape, paint and dense box edits
+// (vrt_fill_shapes, vrt_clear_shapes, vrt_paint_shapes, vrt_write_boxes, vrt_write_boxes_device), the allocation state the inserts
+// continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels vrt_edit_* and their host side.
 // BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
 // vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
 // instructions.  "Binding k" below is buffer id k of vrt_buffer_id (binding 5 = VRT_BUF_BRICK_START_INDEX), as in include/vrt_hip.h's
 // insert block.
 //
-// A batch runs as a chain of kernels on the context's stream:
+// An edit is a chain of kernels on the context's stream, one chain per mode (EditArgs::op).  For an insert:
 //   vrt_edit_begin        clears the batch's status (and, after a write to binding 5, the accumulators of its scan)
 //   vrt_edit_scan_start   binding 5 -> first unset entry, last set entry, type bits, largest start   (only after a write to binding 5)
 //   vrt_edit_state        -> allocated bricks A, material cursor, allocation-shaped or not             (idem)
-//   vrt_edit_validate     per voxel: range, cell, voxel within the brick; loaded cells: brick and entry; others: atomicMin of the
-//                         voxel's index into the cell's scratch word (the cell's first voxel in the batch)
+//   vrt_edit_validate     per voxel: range, cell, voxel within the brick, and what `record` leaves of it in the scratch words: loaded
+//                         cells: brick and entry; others: atomicMin of the voxel's index into the cell's scratch word (its first voxel)
 //   vrt_edit_count        first voxels of new cells, counted per workgroup
 //   vrt_edit_scan_groups  exclusive scan of the workgroup counts; new bricks; brick / material exhaustion
 //   vrt_edit_rank         first voxels: brick A + rank (their order in the batch)
 //   vrt_edit_resolve      the other voxels of new cells: the brick of the cell's first voxel; entry of binding 6
 //   vrt_edit_table        clears the cells' scratch words; last writer of every entry of binding 6 (open addressing, atomicMax)
-//   vrt_edit_write        the scene's bytes, and the written ranges
+//   vrt_edit_write        the scene's bytes (a new cell's words: load_cell), and the written ranges
 //   vrt_edit_finish       A and the cursor move on; the status the host reads back
 // Every kernel after vrt_edit_validate reads the error word first and writes no scene byte when it is set.
 //
-// A removal batch (vrt_grid_remove_many for the batch) is a mode of the same kernels, EditArgs::op = kEditOpRemove:
-//   vrt_edit_begin (+ the scan of binding 5, as above)
-//   vrt_edit_validate     per voxel: range, cell, voxel within the brick; loaded cells: brick, and atomicMin of the voxel's index into
-//                         the cell's scratch word (one voxel elected per touched loaded cell); others: no-ops
-//   vrt_edit_write        phase 0: the occupancy bit cleared (atomicAnd on the word); the range of bytes that lost a bit
-//   vrt_edit_write        phase 1 (a kernel boundary after every clear): the elected voxel of each cell reads its brick's occupancy
-//                         words and, if none is set, clears the cell's status bit; the range of those cells
-//   vrt_edit_table        clears the cells' scratch words
-//   vrt_edit_finish
-//
-// Compaction (vrt_grid_compact on the scene) is the third mode, EditArgs::op = kEditOpCompact.  It has no batch: its
-// kernels run over the cells of the grid or over the entries of binding 5, and its scratch words are the per-voxel words of a batch of
-// brick_alloc voxels (live flags in vinfo, zeroed before the chain; prefix in vcell; holes in vslot; new names in vbrick):
-//   vrt_edit_begin (+ the scan of binding 5, as above)
-//   vrt_edit_validate     per cell: a loaded cell's brick < A, live[brick] = 1; per allocated brick: start == slot * B^3
-//   vrt_edit_count / _scan_groups / _rank   over bricks, the flag is live: the exclusive prefix P[b], and L = the live bricks
-//   vrt_edit_resolve      dead h < L: holes[h - P[h]] = h
-//   vrt_edit_write        phase 0: live b >= L takes holes[P[b] - P[L]]: new_name[b], and its two records copied in 16-byte pieces
-//   vrt_edit_write        phase 1 (a kernel boundary after every copy): occupancy [L bb, A bb) zeroed, binding 5 [L, A) unset, the
-//                         loaded cells naming a brick >= L renamed; the range of those cells
-//   vrt_edit_finish       A = L, cursor = L B^3; the written ranges of bindings 4 and 6 from the first and the last hole
-// (vrt_edit_table is not launched: no cell's scratch word is touched.)
-//
-// Shape edits (vrt_fill_shapes, vrt_clear_shapes) are the fourth and fifth mode, EditArgs::op = kEditOpFill / kEditOpClear.
-// Their work item is not a voxel but one 32-bit occupancy word of one cell of one shape's clipped cell box, ordered shape-major,
-// cell-index-major, word-minor; the host uploads one ShapeRec per shape that holds a voxel of the grid, with the items before it, and a
-// kernel finds its shape by binary search.  The item's mask (the word's voxels inside the shape) stands for the voxel:
-//   vrt_edit_validate     per item: shape, cell, word, mask; a zero mask makes the item inert.  fill: as for inserts, with "first item"
-//                         for "first voxel"; clear: as for removals, the mask kept in the item's slot word
-//   vrt_edit_count / _scan_groups / _rank / _resolve   fill only, unchanged in meaning
-//   vrt_edit_table        clears the cells' scratch words (no last-writer table: see vrt_edit_write)
-//   vrt_edit_write        fill: one atomicOr of the mask; the material bytes of the mask's bits that no later shape of the batch covers,
-//                         whole words of four and whole runs of 32 at once; the first item of a new cell writes the cell's words.
-//                         clear: phase 0 one atomicAnd of ~mask, phase 1 as for removals
-//   vrt_edit_finish
-//
-// A paint (vrt_paint_shapes) is the sixth mode, EditArgs::op = kEditOpPaint, on the work items of the shape edits.  It
-// writes binding 6 alone and needs no brick, no election and no last writer, so its chain is the shortest:
-//   vrt_edit_begin (+ the scan of binding 5, as above)
-//   vrt_edit_validate     per item: shape, cell, word, mask; a zero mask or a cell that is not loaded makes the item inert (the status
-//                         bit is tested before binding 3 is read); loaded cells: brick and the entry of the word's bit 0, as for a fill
-//   vrt_edit_write        keep = mask & the item's occupancy word & ~(the later shapes' masks); with a filter, the bits of keep whose
-//                         entry holds another material dropped; the material bytes of keep, stored as a fill stores them; popcount(keep)
-//                         summed into EditStatus::painted, one atomic per wave
-//   vrt_edit_finish
-// (vrt_edit_table is not launched: no cell's scratch word is touched.)
-//
-// A dense box write (vrt_write_boxes, vrt_write_boxes_device) is the seventh mode, EditArgs::op = kEditOpWrite, on the
-// work items of the shape edits: one ShapeRec per box that reaches into the grid, its range the box's part inside the grid, and in the
-// sphere's fields where the box's elements lie in EditArgs::data.  An item reads the elements of its word's voxels, row by row, into two
-// masks: set (a material) and clear (VRT_VOXEL_EMPTY); VRT_VOXEL_KEEP and the voxels outside the box are in neither.  It is a fill of
-// `set` with a material per voxel and a clear of `clear` in one chain; the boxes are disjoint, so no voxel has two writers:
-//   vrt_edit_begin (+ the scan of binding 5, as above)
-//   vrt_edit_validate     per item: box, cell, word, the two masks; an element that is none of the three kinds is an error; a zero
-//                         set | clear makes the item inert.  Loaded cells: brick and entry as for a fill and, if clear is not zero, the
-//                         cell's election as for a clear.  Others: if set is not zero, atomicMin for the ranking as for a fill (a cell is
-//                         loaded or not when the call begins, so the one scratch word serves both; bit 31 of vinfo says which)
-//   vrt_edit_count / _scan_groups / _rank / _resolve   unchanged in meaning
-//   vrt_edit_write        phase 0: atomicOr of set, atomicAnd of ~clear; the material bytes of set, read again from the elements (a whole
-//                         row as one 8-byte store, a whole nibble as a dword, the rest as bytes: never an entry the item does not set,
-//                         another box may own it); the first item of a new cell writes the cell's words
-//   vrt_edit_write        phase 1 (a kernel boundary after every bit): as for removals
-//   vrt_edit_table        clears the cells' scratch words (behind phase 1, which reads them)
-//   vrt_edit_finish
-//
-//   mode      op  validate  count scan_groups rank resolve  table  write       finish
-//   insert    0   x         x     x           x    x        x      x           x
-//   remove    1   x                                         x      phases 0, 1 x
-//   compact   2   x         x     x           x    x               phases 0, 1 x
-//   fill      3   x         x     x           x    x        x      x           x
-//   clear     4   x                                         x      phases 0, 1 x
-//   paint     5   x                                                x           x
-//   write     6   x         x     x           x    x        last   phases 0, 1 x
+// The modes, as kEditOps on the host side holds them (every chain begins with vrt_edit_begin and, where due, the scan of binding 5):
+//   mode      op  validate  count scan_groups rank resolve  table  write       finish   errors beside "not allocation-shaped"
+//   insert    0   x         x     x           x    x        x      x           x        range, cell, oom
+//   remove    1   x                                         last   phases 0, 1 x        range, cell
+//   compact   2   x         x     x           x    x               phases 0, 1 x        slot, cell
+//   fill      3   x         x     x           x    x        x      x           x        cell, oom
+//   clear     4   x                                         last   phases 0, 1 x        cell
+//   paint     5   x                                                x           x        cell
+//   write     6   x         x     x           x    x        last   phases 0, 1 x        cell, oom, value
+// ("last": vrt_edit_table runs behind the phase that reads the scratch words; only an insert needs its last writers.)  Beyond the table:
+//   remove (vrt_grid_remove_many; §12)  a voxel of a cell that is not loaded is a no-op; validation elects one voxel per touched loaded
+//     cell.  Phase 0 clears the occupancy bits (atomicAnd); phase 1, a kernel boundary after every clear, has the elected voxel read its
+//     brick's occupancy words and, if none is set, clear the cell's status bit.
+//   compact (vrt_grid_compact; §13)  has no batch: its kernels run over the cells of the grid or the entries of binding 5, and its
+//     scratch words are the per-voxel words of a batch of brick_alloc voxels (live flags in vinfo, zeroed before the chain; prefix in
+//     vcell; holes in vslot; new names in vbrick).  validate: a loaded cell's brick < A, live[brick] = 1; an allocated brick's start ==
+//     slot * B^3.  count / scan_groups / rank: the exclusive prefix P[b] of the live flags, and the live bricks L.  resolve: dead h < L:
+//     holes[h - P[h]] = h.  write phase 0: live b >= L takes holes[P[b] - P[L]], and its two records are copied in 16-byte pieces;
+//     phase 1 (a kernel boundary after every copy): occupancy [L, A) zeroed, binding 5 [L, A) unset, the loaded cells naming a brick >= L
+//     renamed.  finish: A = L, cursor = L B^3; the written ranges of bindings 4 and 6 from the first and the last hole.
+//   fill, clear (§16)  the work item is not a voxel but one 32-bit occupancy word of one cell of one shape's clipped cell box, ordered
+//     shape-major, cell-index-major, word-minor; the host uploads one ShapeRec per shape that holds a voxel of the grid, with the items
+//     before it, and a kernel finds its shape by binary search.  The item's mask (the word's voxels inside the shape; zero: inert) stands
+//     for the voxel: a fill is an insert with "first item" for "first voxel", a clear a removal with the mask kept in the item's slot
+//     word.  A fill writes one atomicOr of the mask and the material bytes of the mask's bits that no later shape of the batch covers,
+//     whole words of four and whole runs of 32 at once.
+//   paint (§17)  on the same items, writes binding 6 alone: no brick, no election, no last writer.  An item of a cell that is not loaded
+//     is inert (the status bit is tested before binding 3 is read).  keep = mask & the item's occupancy word & ~(the later shapes'
+//     masks), less, with a filter, the bits whose entry holds another material; popcount(keep) summed into EditStatus::painted.
+//   write (§19)  on the same items, one ShapeRec per box that reaches into the grid (its range the box's part inside the grid; origin,
+//     side_x, side_z and base say where the box's elements lie in EditArgs::data).  An item reads the elements of its word's voxels, row
+//     by row, into two masks: set (a material) and clear (VRT_VOXEL_EMPTY); VRT_VOXEL_KEEP and the voxels outside the box are in neither,
+//     any other element is an error.  It is a fill of `set` with a material per voxel (read again from the elements in phase 0: a whole
+//     row as one 8-byte store, a whole nibble as a dword, the rest as bytes, never an entry the item does not set) and a clear of `clear`
+//     in one chain; the boxes are disjoint, so no voxel has two writers.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -114,6 +76,12 @@ constexpr uint32_t kEditNone = 0xFFFFFFFFu;
 constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4, kEditOpPaint = 5,
                    kEditOpWrite = 6; // EditArgs::op
 constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
+
+// The fields of EditArgs::vinfo[i], voxel or item i as vrt_edit_validate recorded it.  (Compaction keeps its live flags in these words.)
+constexpr uint32_t kInfoNewCell = 0x80000000u; // bit 31: its cell was not loaded when the batch began
+constexpr uint32_t kInfoFirst = 0x40000000u;   // bit 30: the first voxel or item of such a cell in the batch (vrt_edit_count sets it)
+constexpr uint32_t kInfoNth = 0x1FFu;          // bits 0-8: voxelAt, the voxel within the brick; an item's: that of its word's bit 0,
+constexpr uint32_t kInfoWordShift = 5;         //           word << kInfoWordShift
 
 // error bits of EditStatus::err (the host reports the highest-ranked one)
 constexpr uint32_t kEditErrShape = 1u << 0;  // binding 5 is not allocation-shaped                       -> VRT_E_STATE
@@ -153,9 +121,10 @@ struct EditStatus {
 // and where its items lie.  Only shapes that hold a voxel of the grid's range are uploaded.
 struct ShapeRec {
     uint32_t lo[3], hi[3];  // the voxels considered
-    uint32_t centre[3];     // sphere: the centre modulo 2^32.  A box of a write: WriteBox::origin
-    uint32_t r2;            // sphere: r^2.  A box of a write: its side along x
-    uint32_t kind, material; // (a box of a write: kind VRT_SHAPE_BOX, and in `material` its side along z)
+    union { uint32_t centre[3], origin[3]; }; // sphere: the centre modulo 2^32.  A box of a write: WriteBox::origin
+    union { uint32_t r2, side_x; };           // sphere: r^2.  A box of a write: its side along x
+    uint32_t kind;                            // (a box of a write: VRT_SHAPE_BOX)
+    union { uint32_t material, side_z; };     // fill, paint: the material.  A box of a write: its side along z
     uint32_t first;         // items of the shapes before this one
     uint32_t ncx, ncxz;     // cells of its clipped cell box along x, and in one layer of y
     uint32_t base;          // a box of a write: its first element
@@ -183,7 +152,7 @@ struct EditArgs {
     // scratch (the context's, grown on demand)
     uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded (removal: that is loaded); kEditNone between batches
     uint32_t *vcell;         // [n] the voxel's cell (kEditNone: not written)
-    uint32_t *vinfo;         // [n] bit 31: cell not loaded, bit 30: first voxel of that cell, bits 0-8: voxel within the brick
+    uint32_t *vinfo;         // [n] kInfoNewCell | kInfoFirst | kInfoNth
     uint32_t *vbrick;        // [n] brick index
     uint32_t *vslot;         // [n] entry of binding 6
     uint32_t *group_sums;    // [ceil(n / kEditBlock)] first voxels per workgroup, then their exclusive scan
@@ -236,6 +205,40 @@ __device__ inline void wave_atomic_max(uint32_t *p, uint32_t v) {
 __device__ inline void wave_atomic_or(uint32_t *p, uint32_t v) {
     v = wave_or(v);
     if (lane_id() == 0 && v != 0u) atomicOr(p, v);
+}
+// a written range of EditStatus widened by the wave's [lo, hi] (kEditNone, 0: the lane wrote nothing); range: its _lo word, _hi behind it
+__device__ inline void wave_range(uint32_t *range, uint32_t lo, uint32_t hi) {
+    wave_atomic_min(range, lo);
+    wave_atomic_max(range + 1, hi);
+}
+static_assert(offsetof(EditStatus, cell_hi) == offsetof(EditStatus, cell_lo) + 4 && offsetof(EditStatus, occ_hi) == offsetof(EditStatus, occ_lo) + 4 &&
+                  offsetof(EditStatus, mat_hi) == offsetof(EditStatus, mat_lo) + 4,
+              "wave_range: every _hi lies behind its _lo");
+
+// the bytes of binding 4 that mask (not zero) touches in occupancy word `word`
+__device__ inline void touched_bytes(uint32_t word, uint32_t mask, uint32_t &lo, uint32_t &hi) {
+    lo = word * 4u + ((uint32_t)__builtin_ctz(mask) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(mask)) >> 3);
+}
+// the entries of binding 6 that mask (not zero) touches, bit k = entry slot + k
+__device__ inline void touched_entries(uint32_t slot, uint32_t mask, uint32_t &lo, uint32_t &hi) {
+    lo = slot + (uint32_t)__builtin_ctz(mask), hi = slot + 31u - (uint32_t)__builtin_clz(mask);
+}
+
+// Grid.zig:160-168, 188-193: the first voxel or item of a cell that was not loaded makes the cell loaded, with the brick that
+// vrt_edit_rank gave it and that brick's entries of binding 6 (MaterialAllocator.zig:39: cursor + rank * B^3; type bit 0: voxel_start_index)
+__device__ inline void load_cell(const EditArgs &a, uint32_t cell, uint32_t brick) {
+    atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
+    a.index[cell] = brick;
+    a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits);
+}
+// ... for item i of a fill or a write, if it is such a first item, with the range of those cells (every lane of the wave gets here)
+__device__ inline void load_item_cell(const EditArgs &a, uint32_t i, bool active) {
+    uint32_t lo = kEditNone, hi = 0;
+    if (active && (a.vinfo[i] & kInfoFirst)) {
+        lo = hi = a.vcell[i];
+        load_cell(a, lo, a.vbrick[i]);
+    }
+    wave_range(&a.out->cell_lo, lo, hi);
 }
 
 __device__ inline uint32_t table_hash(uint32_t key, uint32_t mask) { return ((key * 2654435761u) ^ (key >> 15)) & mask; }
@@ -413,8 +416,8 @@ __device__ inline WordMasks data_word(const EditArgs &a, const ShapeRec &r, cons
     const uint32_t rows = 32u / b, log_b = b == 8u ? 3u : 2u;
     // WriteBox's element (vrt_read_boxes.h) of the voxel 0 of the cell's row z = 0, fy = 0, modulo 2^32, and what a step in z and in fy
     // adds to it: the box and the cell are in these three values from here on
-    const uint32_t sx = r.r2, sxz = r.r2 * r.material;
-    const uint32_t e0 = r.base + (it.x - r.centre[0]) + sx * (it.z - r.centre[2]) + sxz * (r.centre[1] - it.y);
+    const uint32_t sx = r.side_x, sxz = r.side_x * r.side_z;
+    const uint32_t e0 = r.base + (it.x - r.origin[0]) + sx * (it.z - r.origin[2]) + sxz * (r.origin[1] - it.y);
     uint32_t row = it.word * rows; // the word's rows: a multiple of rows, and the rows - 1 behind it
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable) // (rolled, as word_mask's: the kernels' 32 VGPRs)
     do {
@@ -534,88 +537,70 @@ __device__ inline void compact_validate(const EditArgs &a) {
     wave_atomic_or(&a.out->err, err);
 }
 
-// a fill's, a clear's or a paint's items (every lane gets to the reduction)
-__device__ inline void shape_validate(const EditArgs &a) {
-    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
-    const bool ok = a.state->ok != 0, fill = a.op == kEditOpFill, clear = a.op == kEditOpClear;
-    const uint32_t bricks = a.state->bricks;
-    uint32_t cell = kEditNone, info = 0, err = 0;
-    if (i < a.n && ok) {
-        const ShapeItem it = shape_item(a, i);
-        const uint32_t mask = shape_mask(shape_rec(a, it.shape), a.b, it);
-        if (mask) { // (a zero mask: the item is inert, cell stays kEditNone)
-            const uint32_t log_b = a.b == 8u ? 3u : 2u;
-            const uint32_t g = (it.x >> log_b) + a.dim_x * ((it.z >> log_b) + a.dim_z * (it.y >> log_b)); // gridAt (below the grid's cells, which fit 32 bits)
-            const uint32_t first_bit = it.word << 5;                        // voxelAt of the word's bit 0
-            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
-                const uint32_t brick = a.index[g];
-                if (brick >= bricks) {
-                    err = kEditErrCell;
-                } else {
-                    a.vbrick[i] = brick;
-                    if (!clear) {
-                        a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + first_bit; // the entry of binding 6 of the word's bit 0
-                    } else {
-                        a.vslot[i] = mask;               // (a clear writes no entry of binding 6: the word holds the mask for phase 0)
-                        atomicMin(&a.cell_first[g], i);  // the cell's elected item
-                    }
-                    cell = g;
-                    info = first_bit;
-                }
-            } else if (fill) { // (a clear or a paint of a cell that is not loaded: a no-op; binding 3 may be stale there and is not read)
-                atomicMin(&a.cell_first[g], i); // the minimum ranks the new cells shape-major, then by cell index
-                cell = g;
-                info = 0x80000000u | first_bit;
-            }
+// What vrt_edit_validate leaves of a voxel or item in its scratch words: cell stays kEditNone where it is inert
+struct Recorded {
+    uint32_t cell, info, err;
+};
+
+// Voxel or item i in cell g, nth its voxelAt (an item's: that of its word's bit 0), recorded for the kernels behind vrt_edit_validate.
+// A loaded cell: its brick, tested against the allocated bricks A; with `entry`, the entry of binding 6 of nth (< cursor <= binding 6's
+// size: the state is allocation-shaped); with `elect`, the atomicMin that elects one voxel or item per touched loaded cell, which looks
+// at the brick once every bit is cleared.  A cell that is not loaded: with `rank`, the atomicMin that finds the cell's first voxel or
+// item, which ranks the new cells in the batch's order (items: shape-major, then by cell index); without, inert, and binding 3, which
+// may be stale there, is not read.  (A cell is loaded or not when the call begins, so the one scratch word serves both.)
+__device__ inline Recorded record(const EditArgs &a, uint32_t i, uint32_t g, uint32_t nth, uint32_t bricks, bool entry, bool elect, bool rank) {
+    Recorded r = {kEditNone, 0u, 0u};
+    if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
+        const uint32_t brick = a.index[g];
+        if (brick >= bricks) {
+            r.err = kEditErrCell;
+            return r;
         }
+        a.vbrick[i] = brick;
+        if (entry) a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + nth;
+        if (elect) atomicMin(&a.cell_first[g], i);
+        r.cell = g, r.info = nth;
+    } else if (rank) {
+        atomicMin(&a.cell_first[g], i);
+        r.cell = g, r.info = kInfoNewCell | nth;
     }
-    if (i < a.n) {
-        a.vcell[i] = cell;
-        a.vinfo[i] = info;
-    }
-    if (!ok && i == 0) err = kEditErrShape;
-    wave_atomic_or(&a.out->err, err);
+    return r;
 }
 
-// a write's items (every lane gets to the reduction)
-__device__ inline void box_validate(const EditArgs &a) {
-    const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
-    const bool ok = a.state->ok != 0;
-    const uint32_t bricks = a.state->bricks;
-    uint32_t cell = kEditNone, info = 0, err = 0;
-    if (i < a.n && ok) {
-        const ShapeItem it = shape_item(a, i);
-        const WordMasks m = data_word<false>(a, shape_rec(a, it.shape), it, 0u);
-        if (m.bad) {
-            err = kEditErrValue;
-        } else if (m.set | m.clear) { // (neither: the item is inert, cell stays kEditNone)
-            const uint32_t log_b = a.b == 8u ? 3u : 2u;
-            const uint32_t g = (it.x >> log_b) + a.dim_x * ((it.z >> log_b) + a.dim_z * (it.y >> log_b)); // gridAt
-            const uint32_t first_bit = it.word << 5;                                                        // voxelAt of the word's bit 0
-            if ((a.status[g >> 5] >> (g & 31u)) & 1u) {
-                const uint32_t brick = a.index[g];
-                if (brick >= bricks) {
-                    err = kEditErrCell;
-                } else {
-                    a.vbrick[i] = brick;
-                    a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + first_bit; // the entry of binding 6 of the word's bit 0
-                    if (m.clear) atomicMin(&a.cell_first[g], i);             // the cell's elected item, for phase 1
-                    cell = g;
-                    info = first_bit;
-                }
-            } else if (m.set) { // (a removal in a cell that is not loaded: a no-op)
-                atomicMin(&a.cell_first[g], i); // the minimum ranks the new cells box-major, then by cell index
-                cell = g;
-                info = 0x80000000u | first_bit;
-            }
-        }
+// Item i of a fill, clear, paint or write: the word's voxels that it sets or paints and those that it clears, from its shape or from
+// its box's elements; neither: inert.  A fill ranks, a clear elects, a paint does neither (so a cell that is not loaded is inert to it);
+// a write elects where it clears and ranks where it sets.
+__device__ inline Recorded item_validate(const EditArgs &a, uint32_t i, uint32_t bricks) {
+    const ShapeItem it = shape_item(a, i);
+    const ShapeRec &shape = shape_rec(a, it.shape);
+    const bool clears = a.op == kEditOpClear;
+    uint32_t set = 0, clear = 0;
+    if (a.op == kEditOpWrite) {
+        const WordMasks m = data_word<false>(a, shape, it, 0u);
+        if (m.bad) return {kEditNone, 0u, kEditErrValue};
+        set = m.set, clear = m.clear;
+    } else {
+        const uint32_t mask = shape_mask(shape, a.b, it);
+        set = clears ? 0u : mask, clear = clears ? mask : 0u;
     }
-    if (i < a.n) {
-        a.vcell[i] = cell;
-        a.vinfo[i] = info;
-    }
-    if (!ok && i == 0) err = kEditErrShape;
-    wave_atomic_or(&a.out->err, err);
+    if (!(set | clear)) return {kEditNone, 0u, 0u};
+    const uint32_t log_b = a.b == 8u ? 3u : 2u;
+    const uint32_t g = (it.x >> log_b) + a.dim_x * ((it.z >> log_b) + a.dim_z * (it.y >> log_b)); // gridAt (below the grid's cells, which fit 32 bits)
+    const Recorded r = record(a, i, g, it.word << kInfoWordShift, bricks, !clears, clear != 0u, set != 0u && a.op != kEditOpPaint);
+    if (clears && r.cell != kEditNone) a.vslot[i] = clear; // (a clear writes no entry of binding 6: the word holds the mask for phase 0)
+    return r;
+}
+
+// voxel i of an insert or a removal; a removal in a cell that is not loaded is a no-op
+__device__ inline Recorded voxel_validate(const EditArgs &a, uint32_t i, uint32_t bricks) {
+    const uint32_t *p = a.xyz + 3ull * i; // (64-bit: 3 i passes 2^32 from i = 1 431 655 766, and a batch holds up to 2^31 - 1 voxels)
+    const uint32_t x = p[0], y = p[1], z = p[2];
+    if (x >= a.voxel_dim_x || y >= a.voxel_dim_y || z >= a.voxel_dim_z) return {kEditNone, 0u, kEditErrRange}; // Grid.zig:130-132
+    const uint32_t fy = a.voxel_dim_y - 1u - y; // Grid.zig:135
+    const uint32_t g = (uint32_t)((uint64_t)(x / a.b) + (uint64_t)a.dim_x * ((uint64_t)(z / a.b) + (uint64_t)a.dim_z * (fy / a.b))); // gridAt
+    const uint32_t nth = x % a.b + a.b * (z % a.b + a.b * (fy % a.b));                                                            // voxelAt
+    const bool insert = a.op == kEditOpInsert;
+    return record(a, i, g, nth, bricks, insert, !insert, insert);
 }
 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
@@ -623,63 +608,17 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_validate(EditArgs a) {
         compact_validate(a);
         return;
     }
-    if (a.op == kEditOpWrite) {
-        box_validate(a);
-        return;
-    }
-    if (a.op >= kEditOpFill) { // fill, clear, paint
-        shape_validate(a);
-        return;
-    }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     const bool ok = a.state->ok != 0;
     const uint32_t bricks = a.state->bricks;
-    uint32_t cell = kEditNone, info = 0, err = 0;
-    if (i < a.n && ok) {
-        const uint32_t *p = a.xyz + 3ull * i; // (64-bit: 3 i passes 2^32 from i = 1 431 655 766, and a batch holds up to 2^31 - 1 voxels)
-        const uint32_t x = p[0], y = p[1], z = p[2];
-        if (x >= a.voxel_dim_x || y >= a.voxel_dim_y || z >= a.voxel_dim_z) {
-            err = kEditErrRange; // Grid.zig:130-132
-        } else {
-            const uint32_t fy = a.voxel_dim_y - 1u - y; // Grid.zig:135
-            const uint32_t g = (uint32_t)((uint64_t)(x / a.b) + (uint64_t)a.dim_x * ((uint64_t)(z / a.b) + (uint64_t)a.dim_z * (fy / a.b))); // gridAt
-            const uint32_t nth = x % a.b + a.b * (z % a.b + a.b * (fy % a.b));                                                            // voxelAt
-            const bool loaded = (a.status[g >> 5] >> (g & 31u)) & 1u;
-            if (a.op == kEditOpRemove) {
-                if (loaded) { // (a cell that is not loaded: a no-op, cell stays kEditNone)
-                    const uint32_t brick = a.index[g];
-                    if (brick >= bricks) {
-                        err = kEditErrCell;
-                    } else {
-                        a.vbrick[i] = brick;
-                        atomicMin(&a.cell_first[g], i); // the cell's elected voxel: it looks at the brick once every bit is cleared
-                        cell = g;
-                        info = nth;
-                    }
-                }
-            } else if (loaded) {
-                const uint32_t brick = a.index[g];
-                if (brick >= bricks) {
-                    err = kEditErrCell;
-                } else {
-                    a.vbrick[i] = brick;
-                    a.vslot[i] = (a.start[brick] & 0x7FFFFFFFu) + nth; // (< cursor <= binding 6's size: the state is allocation-shaped)
-                    cell = g;
-                    info = nth;
-                }
-            } else {
-                atomicMin(&a.cell_first[g], i);
-                cell = g;
-                info = 0x80000000u | nth;
-            }
-        }
-    }
+    Recorded r = {kEditNone, 0u, 0u};
+    if (i < a.n && ok) r = a.op >= kEditOpFill ? item_validate(a, i, bricks) : voxel_validate(a, i, bricks); // (fill, clear, paint, write)
     if (i < a.n) {
-        a.vcell[i] = cell;
-        a.vinfo[i] = info;
+        a.vcell[i] = r.cell;
+        a.vinfo[i] = r.info;
     }
-    if (!ok && i == 0) err = kEditErrShape;
-    wave_atomic_or(&a.out->err, err);
+    if (!ok && i == 0) r.err = kEditErrShape;
+    wave_atomic_or(&a.out->err, r.err); // (every lane gets to the reduction)
 }
 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_count(EditArgs a) {
@@ -690,8 +629,8 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_count(EditArgs a) {
         first = i < a.state->bricks && a.vinfo[i] != 0u; // a live brick
     } else if (i < a.n) {
         const uint32_t info = a.vinfo[i];
-        first = (info & 0x80000000u) && a.cell_first[a.vcell[i]] == i;
-        if (first) a.vinfo[i] = info | 0x40000000u;
+        first = (info & kInfoNewCell) && a.cell_first[a.vcell[i]] == i;
+        if (first) a.vinfo[i] = info | kInfoFirst;
     }
     uint32_t total;
     (void)group_prefix(first, &total);
@@ -736,7 +675,7 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_rank(EditArgs a) {
     if (a.out->err) return;
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     const bool compact = a.op == kEditOpCompact;
-    const bool first = compact ? (i < a.state->bricks && a.vinfo[i] != 0u) : (i < a.n && (a.vinfo[i] & 0x40000000u));
+    const bool first = compact ? (i < a.state->bricks && a.vinfo[i] != 0u) : (i < a.n && (a.vinfo[i] & kInfoFirst));
     uint32_t total;
     const uint32_t rank = a.group_sums[blockIdx.x] + group_prefix(first, &total);
     if (compact) {
@@ -755,16 +694,16 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_resolve(EditArgs a) {
     }
     if (i >= a.n) return;
     const uint32_t info = a.vinfo[i];
-    if (!(info & 0x80000000u)) return;
+    if (!(info & kInfoNewCell)) return;
     const uint32_t f = a.cell_first[a.vcell[i]];
-    if (f >= a.n || !(a.vinfo[f] & 0x40000000u)) { // (cannot happen while the scratch words are clean; never write through a stale one)
+    if (f >= a.n || !(a.vinfo[f] & kInfoFirst)) { // (cannot happen while the scratch words are clean; never write through a stale one)
         atomicOr(&a.out->err, kEditErrCell);
         return;
     }
     const uint32_t brick = a.vbrick[f];
-    if (!(info & 0x40000000u)) a.vbrick[i] = brick;
+    if (!(info & kInfoFirst)) a.vbrick[i] = brick;
     // MaterialAllocator.nextSlotIndex (MaterialAllocator.zig:39) for new brick r: cursor + r * B^3; Grid.zig:173
-    a.vslot[i] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits) + (info & 0x1FFu);
+    a.vslot[i] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits) + (info & kInfoNth);
 }
 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
@@ -776,7 +715,7 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_table(EditArgs a) {
         if (cell != kEditNone) a.cell_first[cell] = kEditNone;
         return;
     }
-    if (a.vinfo[i] & 0x80000000u) a.cell_first[cell] = kEditNone; // (whatever the error word says: the scratch is clean for the next batch)
+    if (a.vinfo[i] & kInfoNewCell) a.cell_first[cell] = kEditNone; // (whatever the error word says: the scratch is clean for the next batch)
     if (a.op == kEditOpFill) return; // (no two items write one entry of binding 6: vrt_edit_write tests the later shapes instead)
     if (a.out->err || cell == kEditNone) return;
     const uint32_t key = a.vslot[i] + 1u;
@@ -798,17 +737,16 @@ __device__ inline void remove_write(const EditArgs &a) {
     uint32_t lo = kEditNone, hi = 0;
     if (a.phase == 0) {
         if (cell != kEditNone && a.op == kEditOpClear) { // the item's word at once: the bytes of it that lost a bit
-            const uint32_t mask = a.vslot[i], word = a.vbrick[i] * (a.brick_bytes >> 2) + (a.vinfo[i] >> 5);
+            const uint32_t mask = a.vslot[i], word = a.vbrick[i] * (a.brick_bytes >> 2) + (a.vinfo[i] >> kInfoWordShift);
             const uint32_t lost = atomicAnd(&a.occupancy[word], ~mask) & mask;
-            if (lost) lo = word * 4u + ((uint32_t)__builtin_ctz(lost) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(lost)) >> 3);
+            if (lost) touched_bytes(word, lost, lo, hi);
         } else if (cell != kEditNone) {
-            const uint32_t nth = a.vinfo[i] & 0x1FFu;
+            const uint32_t nth = a.vinfo[i] & kInfoNth;
             const uint32_t byte = a.vbrick[i] * a.brick_bytes + (nth >> 3);
             const uint32_t bit = 1u << ((byte & 3u) * 8u + (nth & 7u));
             if (atomicAnd(&a.occupancy[byte >> 2], ~bit) & bit) lo = hi = byte; // (of duplicates, one finds the bit set)
         }
-        wave_atomic_min(&a.out->occ_lo, lo);
-        wave_atomic_max(&a.out->occ_hi, hi);
+        wave_range(&a.out->occ_lo, lo, hi);
         return;
     }
     if (cell != kEditNone && a.cell_first[cell] == i) {
@@ -821,8 +759,7 @@ __device__ inline void remove_write(const EditArgs &a) {
             lo = hi = cell;
         }
     }
-    wave_atomic_min(&a.out->cell_lo, lo);
-    wave_atomic_max(&a.out->cell_hi, hi);
+    wave_range(&a.out->cell_lo, lo, hi);
 }
 
 // compaction's two passes (every lane of the wave gets to phase 1's reductions)
@@ -860,13 +797,11 @@ __device__ inline void compact_write(const EditArgs &a) {
             }
         }
     }
-    wave_atomic_min(&a.out->cell_lo, lo);
-    wave_atomic_max(&a.out->cell_hi, hi);
+    wave_range(&a.out->cell_lo, lo, hi);
 }
 
 // `material` into the entries of binding 6 that `keep` names, bit k = entries[k], entries = binding 6 + slot (slot + 31 lies within the
-// brick's B^3 entries): a whole run of 32 on a 16-byte aligned slot as two 16-byte stores, otherwise a whole nibble on a 4-byte aligned
-// slot as one dword, the rest as bytes
+// brick's B^3 entries): a whole run of 32 on a 16-byte aligned slot as two 16-byte stores, otherwise nibble by nibble (store_nibble)
 __device__ inline void store_materials(uint8_t *entries, uint32_t slot, uint32_t keep, uint32_t material) {
     const uint32_t four = material * 0x01010101u;
     if (keep == 0xFFFFFFFFu && !(slot & 15u)) {
@@ -875,15 +810,18 @@ __device__ inline void store_materials(uint8_t *entries, uint32_t slot, uint32_t
         return;
     }
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-    for (uint32_t k = 0; k < 32u; k += 4u) {
-        const uint32_t nibble = (keep >> k) & 15u;
-        if (nibble == 15u && !(slot & 3u)) {
-            *reinterpret_cast<uint32_t *>(entries + k) = four;
-        } else {
-            for (uint32_t j = 0; j < 4u; j++)
-                if ((nibble >> j) & 1u) entries[k + j] = (uint8_t)material;
-        }
+    for (uint32_t k = 0; k < 32u; k += 4u) store_nibble(entries + k, slot + k, (keep >> k) & 15u, four);
+}
+
+// ... for the entries of item i (of a fill or a paint) that keep names, with their range (every lane of the wave gets here)
+__device__ inline void store_kept(const EditArgs &a, uint32_t i, uint32_t keep, uint32_t material) {
+    uint32_t lo = kEditNone, hi = 0;
+    if (keep) {
+        const uint32_t slot = a.vslot[i];
+        store_materials(a.material + slot, slot, keep, material);
+        touched_entries(slot, keep, lo, hi);
     }
+    wave_range(&a.out->mat_lo, lo, hi);
 }
 
 // a fill's items (every lane of the wave gets to the three pairs of reductions).  The loop over the later shapes comes first, with little
@@ -903,32 +841,15 @@ __device__ inline void fill_write(const EditArgs &a) {
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (uint32_t t = it.shape + 1u; t < a.shape_count && keep; t++) keep &= ~shape_mask(shape_rec(a, t), a.b, it);
     }
+    load_item_cell(a, i, active);
     uint32_t lo = kEditNone, hi = 0;
-    if (active && (a.vinfo[i] & 0x40000000u)) { // the first item of a cell that was not loaded: Grid.zig:160-168, 188-193
-        const uint32_t cell = a.vcell[i], brick = a.vbrick[i];
-        atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
-        a.index[cell] = brick;
-        a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
-        lo = hi = cell;
-    }
-    wave_atomic_min(&a.out->cell_lo, lo);
-    wave_atomic_max(&a.out->cell_hi, hi);
-    lo = kEditNone, hi = 0;
     if (active) { // Grid.zig:180-185 for the word's voxels at once
         word += a.vbrick[i] * (a.brick_bytes >> 2);
         atomicOr(&a.occupancy[word], mask);
-        lo = word * 4u + ((uint32_t)__builtin_ctz(mask) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(mask)) >> 3);
+        touched_bytes(word, mask, lo, hi);
     }
-    wave_atomic_min(&a.out->occ_lo, lo);
-    wave_atomic_max(&a.out->occ_hi, hi);
-    lo = kEditNone, hi = 0;
-    if (keep) {
-        const uint32_t slot = a.vslot[i];
-        store_materials(a.material + slot, slot, keep, material);
-        lo = slot + (uint32_t)__builtin_ctz(keep), hi = slot + 31u - (uint32_t)__builtin_clz(keep);
-    }
-    wave_atomic_min(&a.out->mat_lo, lo);
-    wave_atomic_max(&a.out->mat_hi, hi);
+    wave_range(&a.out->occ_lo, lo, hi);
+    store_kept(a, i, keep, material);
 }
 
 // a paint's items (every lane of the wave gets to the reductions).  keep: the item's voxels that are solid and that no later shape of
@@ -945,7 +866,6 @@ __device__ inline void paint_write(const EditArgs &a) {
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (uint32_t t = it.shape + 1u; t < a.shape_count && keep; t++) keep &= ~shape_mask(shape_rec(a, t), a.b, it);
     }
-    uint32_t lo = kEditNone, hi = 0;
     if (keep && a.only != VRT_PAINT_ANY) { // the filter: a bit of keep whose old entry differs from `only` goes, four entries at once
         const uint32_t slot = a.vslot[i], only4 = a.only * 0x01010101u;
         const uint8_t *entries = a.material + slot; // (slot + 31 lies within the brick's B^3 entries)
@@ -960,13 +880,7 @@ __device__ inline void paint_write(const EditArgs &a) {
                 if ((old >> (8u * j)) & 0xFFu) keep &= ~(1u << (k + j));
         }
     }
-    if (keep) {
-        const uint32_t slot = a.vslot[i];
-        store_materials(a.material + slot, slot, keep, material);
-        lo = slot + (uint32_t)__builtin_ctz(keep), hi = slot + 31u - (uint32_t)__builtin_clz(keep);
-    }
-    wave_atomic_min(&a.out->mat_lo, lo);
-    wave_atomic_max(&a.out->mat_hi, hi);
+    store_kept(a, i, keep, material);
     uint32_t count = (uint32_t)__popc(keep);
     for (int o = 32; o > 0; o >>= 1) count += (uint32_t)__shfl_xor((int)count, o);
     if (lane_id() == 0 && count) atomicAdd(reinterpret_cast<unsigned long long *>(&a.out->painted), (unsigned long long)count);
@@ -983,33 +897,22 @@ __device__ inline void box_write(const EditArgs &a) {
         word = it.word;
         m = data_word<true>(a, shape_rec(a, it.shape), it, a.vslot[i]);
     }
+    load_item_cell(a, i, active);
     uint32_t lo = kEditNone, hi = 0;
-    if (active && (a.vinfo[i] & 0x40000000u)) { // the first item of a cell that was not loaded: Grid.zig:160-168, 188-193
-        const uint32_t cell = a.vcell[i], brick = a.vbrick[i];
-        atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
-        a.index[cell] = brick;
-        a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
-        lo = hi = cell;
-    }
-    wave_atomic_min(&a.out->cell_lo, lo);
-    wave_atomic_max(&a.out->cell_hi, hi);
-    lo = kEditNone, hi = 0;
     if (active) { // the bytes that gained a bit (Grid.zig:180-185) or lost one
         word += a.vbrick[i] * (a.brick_bytes >> 2);
         uint32_t changed = m.set;
         if (m.set) atomicOr(&a.occupancy[word], m.set);
         if (m.clear) changed |= atomicAnd(&a.occupancy[word], ~m.clear) & m.clear;
-        if (changed) lo = word * 4u + ((uint32_t)__builtin_ctz(changed) >> 3), hi = word * 4u + ((31u - (uint32_t)__builtin_clz(changed)) >> 3);
+        if (changed) touched_bytes(word, changed, lo, hi);
     }
-    wave_atomic_min(&a.out->occ_lo, lo);
-    wave_atomic_max(&a.out->occ_hi, hi);
+    wave_range(&a.out->occ_lo, lo, hi);
     lo = kEditNone, hi = 0;
     if (m.set) {
         const uint32_t slot = a.vslot[i];
-        lo = slot + (uint32_t)__builtin_ctz(m.set), hi = slot + 31u - (uint32_t)__builtin_clz(m.set);
+        touched_entries(slot, m.set, lo, hi);
     }
-    wave_atomic_min(&a.out->mat_lo, lo);
-    wave_atomic_max(&a.out->mat_hi, hi);
+    wave_range(&a.out->mat_lo, lo, hi);
 }
 
 __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
@@ -1038,7 +941,7 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
     uint32_t cell_lo = kEditNone, cell_hi = 0, occ_lo = kEditNone, occ_hi = 0, mat_lo = kEditNone, mat_hi = 0;
     const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
     if (cell != kEditNone) {
-        const uint32_t slot = a.vslot[i], brick = a.vbrick[i], info = a.vinfo[i], nth = info & 0x1FFu;
+        const uint32_t slot = a.vslot[i], brick = a.vbrick[i], info = a.vinfo[i], nth = info & kInfoNth;
         const uint32_t key = slot + 1u;
         uint32_t h = table_hash(key, a.table_mask);
         while (a.table[h].x != key) h = (h + 1u) & a.table_mask;
@@ -1050,19 +953,14 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
         const uint32_t byte = brick * a.brick_bytes + (nth >> 3);
         atomicOr(&a.occupancy[byte >> 2], 1u << ((byte & 3u) * 8u + (nth & 7u)));
         occ_lo = occ_hi = byte;
-        if (info & 0x40000000u) { // the first voxel of a cell that was not loaded: Grid.zig:160-168, 188-193
-            atomicOr(&a.status[cell >> 5], 1u << (cell & 31u));
-            a.index[cell] = brick;
-            a.start[brick] = (uint32_t)(a.state->cursor + (uint64_t)(brick - a.state->bricks) * a.bits); // type bit 0: voxel_start_index
+        if (info & kInfoFirst) {
+            load_cell(a, cell, brick);
             cell_lo = cell_hi = cell;
         }
     }
-    wave_atomic_min(&a.out->cell_lo, cell_lo);
-    wave_atomic_max(&a.out->cell_hi, cell_hi);
-    wave_atomic_min(&a.out->occ_lo, occ_lo);
-    wave_atomic_max(&a.out->occ_hi, occ_hi);
-    wave_atomic_min(&a.out->mat_lo, mat_lo);
-    wave_atomic_max(&a.out->mat_hi, mat_hi);
+    wave_range(&a.out->cell_lo, cell_lo, cell_hi);
+    wave_range(&a.out->occ_lo, occ_lo, occ_hi);
+    wave_range(&a.out->mat_lo, mat_lo, mat_hi);
 }
 
 __global__ void __launch_bounds__(64) vrt_edit_finish(EditArgs a) {
@@ -1106,17 +1004,73 @@ using namespace vrt_impl;
 
 namespace {
 
-// what every entry point checks before it touches the device: the scene is there, this context may edit it, and the small
-// buffers of the allocation state exist
-int edit_prepare(vrt_ctx *ctx, const char *what = "voxel inserts are") {
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, std::string(what) + " not available on a context of the multi-GPU pipeline");
+// One kernel of an op's chain, between launch_state and read_status.  over: which of run_edit's workgroup counts it runs over (0: those
+// of the batch's voxels or items, the only one of every op but compaction), kOverOne: the one workgroup of vrt_edit_scan_groups.
+// phase1: EditArgs::phase becomes 1 before this step.
+constexpr int kOverOne = 3;
+struct EditStep {
+    void (*fn)(vrt::EditArgs);
+    int over;
+    bool phase1;
+};
+constexpr EditStep kValidate{vrt_edit_validate, 0, false}, kCount{vrt_edit_count, 0, false}, kScanGroups{vrt_edit_scan_groups, kOverOne, false},
+    kRank{vrt_edit_rank, 0, false}, kResolve{vrt_edit_resolve, 0, false}, kTable{vrt_edit_table, 0, false}, kWrite{vrt_edit_write, 0, false},
+    kWritePhase1{vrt_edit_write, 0, true};
+constexpr EditStep over(EditStep step, int groups) { return {step.fn, groups, step.phase1}; }
+
+// What defines an op, indexed by EditArgs::op (the header comment's table, and what it cannot say).  A bit per vrt_buffer_id:
+constexpr uint32_t buf_bit(vrt_buffer_id id) { return 1u << id; }
+constexpr uint32_t kB2 = buf_bit(VRT_BUF_BRICK_STATUS), kB3 = buf_bit(VRT_BUF_BRICK_INDEX), kB4 = buf_bit(VRT_BUF_BRICK_OCCUPANCY),
+                   kB5 = buf_bit(VRT_BUF_BRICK_START_INDEX), kB6 = buf_bit(VRT_BUF_MATERIAL_INDEX);
+struct EditOp {
+    EditStep chain[9];    // ends at the first step without a kernel
+    uint32_t errs;        // the bits of EditStatus::err that it reports (edit_error looks at no others)
+    uint32_t writes;      // the bindings it writes (mark_written)
+    const char *nothing;  // the tail of its refusals
+    const char *subject;  // of "... not available on a context of the multi-GPU pipeline"
+    bool last_writer;     // it needs the last-writer table (edit_scratch)
+    bool drop_cell_first; // cut short, its chain may leave the cells' scratch words set: the next batch makes them anew, clean
+};
+constexpr EditOp kEditOps[] = {
+    // insert
+    {{kValidate, kCount, kScanGroups, kRank, kResolve, kTable, kWrite}, kEditErrShape | kEditErrRange | kEditErrCell | kEditErrOom,
+     kB2 | kB3 | kB4 | kB5 | kB6, "; nothing was inserted", "voxel inserts are", true, true},
+    // remove (a batch of no-ops writes nothing)
+    {{kValidate, kWrite, kWritePhase1, kTable}, kEditErrShape | kEditErrRange | kEditErrCell, kB2 | kB4, "; nothing was removed", "voxel removals are", false, true},
+    // compact: validation over the cells (and bricks), 1; the scans over the bricks, 0; its grid-stride passes, 2.  No cell's scratch word is touched
+    {{over(kValidate, 1), kCount, kScanGroups, kRank, kResolve, over(kWrite, 2), over(kWritePhase1, 2)}, kEditErrShape | kEditErrSlot | kEditErrCell,
+     kB3 | kB4 | kB5 | kB6, "; nothing was compacted", "brick compaction is", false, false},
+    // fill: an insert's chain (no two items write one entry of binding 6, so no last writer)
+    {{kValidate, kCount, kScanGroups, kRank, kResolve, kTable, kWrite}, kEditErrShape | kEditErrCell | kEditErrOom, kB2 | kB3 | kB4 | kB5 | kB6,
+     "; nothing was filled", "shape edits are", false, true},
+    // clear: a removal's chain
+    {{kValidate, kWrite, kWritePhase1, kTable}, kEditErrShape | kEditErrCell, kB2 | kB4, "; nothing was cleared", "shape edits are", false, true},
+    // paint: no cell's scratch word is touched
+    {{kValidate, kWrite}, kEditErrShape | kEditErrCell, kB6, "; nothing was painted", "shape edits are", false, false},
+    // write: a fill's ranking, a clear's two phases, and the scratch words cleared behind the phase that reads them
+    {{kValidate, kCount, kScanGroups, kRank, kResolve, kWrite, kWritePhase1, kTable}, kEditErrShape | kEditErrCell | kEditErrOom | kEditErrValue,
+     kB2 | kB3 | kB4 | kB5 | kB6, "; nothing was written", "dense box writes are", false, true},
+};
+static_assert(sizeof(kEditOps) / sizeof(kEditOps[0]) == kEditOpWrite + 1, "one row per op");
+
+// what every entry point checks before it touches the device: the scene is there and this context may edit it ...
+int edit_allowed(vrt_ctx *ctx, uint32_t op) {
+    if (ctx->dist) return fail(ctx, VRT_E_STATE, std::string(kEditOps[op].subject) + " not available on a context of the multi-GPU pipeline");
     if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    return VRT_OK;
+}
+// ... and the small buffers of the allocation state exist
+int edit_buffers(vrt_ctx *ctx) {
     if (!ctx->d_edit_state) {
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_state, sizeof(vrt::EditState)));
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_status, sizeof(vrt::EditStatus)));
         VRT_HIP(ctx, ctx->res.pinned(&ctx->h_edit_status, sizeof(vrt::EditStatus)));
     }
     return VRT_OK;
+}
+int edit_prepare(vrt_ctx *ctx, uint32_t op) {
+    const int rc = edit_allowed(ctx, op);
+    return rc == VRT_OK ? edit_buffers(ctx) : rc;
 }
 
 int not_shaped(vrt_ctx *ctx) {
@@ -1125,9 +1079,10 @@ int not_shaped(vrt_ctx *ctx) {
 }
 
 // scratch for a batch of n voxels: the per-cell words (once, all 0xFFFFFFFF; every batch leaves them so), the per-voxel words, the
-// per-workgroup counts and the last-writer table (a power of two of at least 2n entries; inserts only).  No kernel of an earlier batch
-// is in flight: every batch ends with a wait for its status.  Nothing to launch where the state is known not to be allocation-shaped.
-int edit_scratch(vrt_ctx *ctx, uint64_t n, bool with_table = false) {
+// per-workgroup counts and, for the ops that need it, the last-writer table (a power of two of at least 2n entries, zeroed).  No kernel
+// of an earlier batch is in flight: every batch ends with a wait for its status.  Nothing to launch where the state is known not to be
+// allocation-shaped.
+int edit_scratch(vrt_ctx *ctx, uint64_t n, uint32_t op) {
     if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
     if (!ctx->d_edit_cell_first) {
         const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
@@ -1137,10 +1092,12 @@ int edit_scratch(vrt_ctx *ctx, uint64_t n, bool with_table = false) {
     const uint64_t cap = (n + vrt::kEditBlock - 1u) / vrt::kEditBlock * vrt::kEditBlock;
     int rc = grow_device(ctx, ctx->edit_capacity, cap, false, ctx->d_edit_voxels, 4u * cap * sizeof(uint32_t), ctx->d_edit_groups,
                          cap / vrt::kEditBlock * sizeof(uint32_t));
-    if (rc != VRT_OK || !with_table) return rc;
+    if (rc != VRT_OK || !kEditOps[op].last_writer) return rc;
     uint64_t entries = 1024;
     while (entries < 2u * n) entries <<= 1;
-    return grow_device(ctx, ctx->edit_table_entries, entries, false, ctx->d_edit_table, entries * sizeof(uint2));
+    rc = grow_device(ctx, ctx->edit_table_entries, entries, false, ctx->d_edit_table, entries * sizeof(uint2));
+    if (rc == VRT_OK) VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
+    return rc;
 }
 
 // a batch given in host memory, into d_edit_input through the pinned staging slots: `first`, then `second` behind it
@@ -1223,115 +1180,73 @@ int read_status(vrt_ctx *ctx, vrt::EditArgs &a, vrt::EditStatus *out) {
     return VRT_OK;
 }
 
-// One kernel of an op's chain, between launch_state and read_status.  phase1: EditArgs::phase becomes 1 before this step.
-struct EditStep {
-    void (*fn)(vrt::EditArgs);
-    uint32_t groups;
-    uint32_t threads = vrt::kEditBlock;
-    bool phase1 = false;
-};
-using EditSteps = std::vector<EditStep>;
-
-// The chains of the six ops (the header comment of this file says what each kernel does in each).  Inserts and fills over the g
-// workgroups of the batch's voxels or items:
-EditSteps insert_steps(uint32_t g) {
-    return {{vrt_edit_validate, g}, {vrt_edit_count, g}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, g},
-            {vrt_edit_resolve, g}, {vrt_edit_table, g}, {vrt_edit_write, g}};
-}
-// ... removals and clears:
-EditSteps remove_steps(uint32_t g) {
-    return {{vrt_edit_validate, g}, {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
-}
-// ... a dense box write: a fill's ranking, a clear's two phases, and the scratch words cleared behind the phase that reads them
-EditSteps write_steps(uint32_t g) {
-    return {{vrt_edit_validate, g}, {vrt_edit_count, g}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, g}, {vrt_edit_resolve, g},
-            {vrt_edit_write, g}, {vrt_edit_write, g, vrt::kEditBlock, true}, {vrt_edit_table, g}};
-}
-// ... a paint:
-EditSteps paint_steps(uint32_t g) { return {{vrt_edit_validate, g}, {vrt_edit_write, g}}; }
-// ... compaction: over the cells (and bricks), over the bricks (also what vrt_edit_scan_groups scans), and its grid-stride passes
-EditSteps compact_steps(uint32_t cells, uint32_t bricks, uint32_t copy) {
-    return {{vrt_edit_validate, cells}, {vrt_edit_count, bricks}, {vrt_edit_scan_groups, 1, vrt::kEditScanBlock}, {vrt_edit_rank, bricks},
-            {vrt_edit_resolve, bricks}, {vrt_edit_write, copy}, {vrt_edit_write, copy, vrt::kEditBlock, true}};
-}
-
-// An edit as one scene write: the whole chain on the primary stream, and its status read back into *s.  drop_cell_first: a chain
-// cut short may leave the cells' scratch words set (compaction's touches none), so they are made anew, clean, by the next batch.
-int run_edit(vrt_ctx *ctx, vrt::EditArgs &a, const EditSteps &steps, bool drop_cell_first, vrt::EditStatus *s) {
-    int rc = begin_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    rc = launch_state(ctx, a);
-    for (const EditStep &st : steps) {
-        if (st.phase1) a.phase = 1;
-        if (rc == VRT_OK) rc = launch(ctx, st.fn, a, st.groups, st.threads);
-    }
-    if (rc != VRT_OK) {
-        (void)wait_stream(ctx->stream);
-        if (drop_cell_first) ctx->res.drop(ctx->d_edit_cell_first);
-        ctx->edit_state_valid = false;
-        return rc;
-    }
-    rc = end_scene_write(ctx);
-    if (rc != VRT_OK) return rc;
-    return read_status(ctx, a, s);
-}
-
-// EditStatus::err -> the return code and the message.  `applies`: the errors the op reports (the others are not looked at), in this
-// order of precedence; `nothing`: the op's "; nothing was ..." tail
-int edit_error(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t applies, const char *nothing) {
-    const uint32_t err = s.err & applies;
+// EditStatus::err -> the return code and the message, for the errors the op reports, in this order of precedence
+int edit_error(vrt_ctx *ctx, const vrt::EditStatus &s, const EditOp &op) {
+    const uint32_t err = s.err & op.errs;
+    const std::string nothing = op.nothing;
     if (err & vrt::kEditErrShape) return not_shaped(ctx);
     if (err & vrt::kEditErrValue)
-        return fail(ctx, VRT_E_INVALID_ARG, std::string("an element of a voxel inside the grid is neither a material 0..255 nor VRT_VOXEL_EMPTY nor VRT_VOXEL_KEEP") + nothing);
-    if (err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, std::string("a voxel lies outside the grid") + nothing);
-    if (err & vrt::kEditErrSlot)
-        return fail(ctx, VRT_E_STATE, std::string("an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3") + nothing);
+        return fail(ctx, VRT_E_INVALID_ARG, "an element of a voxel inside the grid is neither a material 0..255 nor VRT_VOXEL_EMPTY nor VRT_VOXEL_KEEP" + nothing);
+    if (err & vrt::kEditErrRange) return fail(ctx, VRT_E_OUT_OF_RANGE, "a voxel lies outside the grid" + nothing);
+    if (err & vrt::kEditErrSlot) return fail(ctx, VRT_E_STATE, "an allocated brick's entry of binding 5 (brick_start_indices) is not slot * B^3" + nothing);
     if (err & vrt::kEditErrCell)
-        return fail(ctx, VRT_E_STATE, std::string("a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5)") + nothing);
+        return fail(ctx, VRT_E_STATE, "a loaded cell names a brick at or beyond the allocated bricks (binding 3 against binding 5)" + nothing);
     if (err & vrt::kEditErrOom)
         return fail(ctx, VRT_E_OOM, "the batch needs " + std::to_string(s.new_bricks) + " new bricks: brick_alloc or the material entries are exhausted" + nothing);
     return VRT_OK;
 }
-constexpr uint32_t kErrsOfInsert = vrt::kEditErrShape | vrt::kEditErrRange | vrt::kEditErrCell | vrt::kEditErrOom;
-constexpr uint32_t kErrsOfRemove = vrt::kEditErrShape | vrt::kEditErrRange | vrt::kEditErrCell;
-constexpr uint32_t kErrsOfCompact = vrt::kEditErrShape | vrt::kEditErrSlot | vrt::kEditErrCell;
-constexpr uint32_t kErrsOfFill = vrt::kEditErrShape | vrt::kEditErrCell | vrt::kEditErrOom;
-constexpr uint32_t kErrsOfClear = vrt::kEditErrShape | vrt::kEditErrCell;
-constexpr uint32_t kErrsOfPaint = kErrsOfClear;
-constexpr uint32_t kErrsOfWrite = kErrsOfFill | vrt::kEditErrValue;
+
+// An edit as one scene write: the chain of a.op on the primary stream, its status read back into *s, and its error reported.
+// Compaction alone has steps over other workgroup counts than a.groups.
+int run_edit(vrt_ctx *ctx, vrt::EditArgs &a, vrt::EditStatus *s, uint32_t cell_groups = 0, uint32_t copy_groups = 0) {
+    const EditOp &op = kEditOps[a.op];
+    const uint32_t groups[3] = {a.groups, cell_groups, copy_groups};
+    int rc = begin_scene_write(ctx);
+    if (rc != VRT_OK) return rc;
+    rc = launch_state(ctx, a);
+    for (const EditStep *st = op.chain; st->fn; st++) {
+        if (st->phase1) a.phase = 1;
+        if (rc != VRT_OK) continue;
+        rc = st->over == kOverOne ? launch(ctx, st->fn, a, 1, vrt::kEditScanBlock) : launch(ctx, st->fn, a, groups[st->over], vrt::kEditBlock);
+    }
+    if (rc != VRT_OK) {
+        (void)wait_stream(ctx->stream);
+        if (op.drop_cell_first) ctx->res.drop(ctx->d_edit_cell_first);
+        ctx->edit_state_valid = false;
+        return rc;
+    }
+    rc = end_scene_write(ctx);
+    if (rc == VRT_OK) rc = read_status(ctx, a, s);
+    return rc == VRT_OK ? edit_error(ctx, *s, op) : rc;
+}
 
 // The derived structures follow exactly what was written (refresh_derived, before the next frame or query): the status ranges of the
-// buffers the op writes (`writes`: a bit per vrt_buffer_id), marked dirty.  start_first: the first of the s.new_bricks entries of
-// binding 5 that the op wrote; the device state already accounts for them, so that write, the op's own, leaves the state valid.
-constexpr uint32_t buf_bit(vrt_buffer_id id) { return 1u << id; }
-constexpr uint32_t kWritesOfRemove = buf_bit(VRT_BUF_BRICK_STATUS) | buf_bit(VRT_BUF_BRICK_OCCUPANCY); // (a batch of no-ops: nothing)
-constexpr uint32_t kWritesOfInsert = kWritesOfRemove | buf_bit(VRT_BUF_BRICK_INDEX) | buf_bit(VRT_BUF_BRICK_START_INDEX) | buf_bit(VRT_BUF_MATERIAL_INDEX);
-constexpr uint32_t kWritesOfCompact = kWritesOfInsert & ~buf_bit(VRT_BUF_BRICK_STATUS);
-constexpr uint32_t kWritesOfPaint = buf_bit(VRT_BUF_MATERIAL_INDEX);
+// buffers the op writes, marked dirty.  start_first: the first of the s.new_bricks entries of binding 5 that the op wrote; the device
+// state already accounts for them, so that write, the op's own, leaves the state valid.
 void mark_written(vrt_ctx *ctx, const vrt::EditStatus &s, uint32_t writes, uint32_t start_first) {
     if (s.cell_lo <= s.cell_hi) {
-        if (writes & buf_bit(VRT_BUF_BRICK_STATUS))
-            mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
-        if (writes & buf_bit(VRT_BUF_BRICK_INDEX)) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
+        if (writes & kB2) mark_dirty(ctx, VRT_BUF_BRICK_STATUS, (uint64_t)(s.cell_lo >> 5) * 4u, (uint64_t)((s.cell_hi >> 5) - (s.cell_lo >> 5) + 1u) * 4u);
+        if (writes & kB3) mark_dirty(ctx, VRT_BUF_BRICK_INDEX, (uint64_t)s.cell_lo * 4u, ((uint64_t)s.cell_hi - s.cell_lo + 1u) * 4u);
     }
-    if ((writes & buf_bit(VRT_BUF_BRICK_OCCUPANCY)) && s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
-    if ((writes & buf_bit(VRT_BUF_BRICK_START_INDEX)) && s.new_bricks) {
+    if ((writes & kB4) && s.occ_lo <= s.occ_hi) mark_dirty(ctx, VRT_BUF_BRICK_OCCUPANCY, s.occ_lo, (uint64_t)s.occ_hi - s.occ_lo + 1u);
+    if ((writes & kB5) && s.new_bricks) {
         mark_dirty(ctx, VRT_BUF_BRICK_START_INDEX, (uint64_t)start_first * 4u, (uint64_t)s.new_bricks * 4u);
         ctx->edit_state_valid = true;
     }
-    if ((writes & buf_bit(VRT_BUF_MATERIAL_INDEX)) && s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
+    if ((writes & kB6) && s.mat_lo <= s.mat_hi) mark_dirty(ctx, VRT_BUF_MATERIAL_INDEX, s.mat_lo, (uint64_t)s.mat_hi - s.mat_lo + 1u);
 }
 
 // What vrt_insert_voxels / vrt_remove_voxels and their _device forms (host: xyz and materials are host memory, staged into device
-// memory first) check and do; insert false: a removal, which has no materials.  The batch's subset of the chain runs as one scene write.
-int edit_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n, bool insert, bool host) {
+// memory first) check and do; a removal has no materials.  The batch's chain runs as one scene write.
+int edit_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n, uint32_t op, bool host) {
     if (!ctx) return VRT_E_INVALID_ARG;
     if (n == 0) return VRT_OK;
+    const bool insert = op == vrt::kEditOpInsert;
     if (insert && (!xyz || !materials)) return fail(ctx, VRT_E_INVALID_ARG, "xyz or materials is NULL");
     if (!xyz) return fail(ctx, VRT_E_INVALID_ARG, "xyz is NULL");
     if (n >= (1ull << 31)) return fail(ctx, VRT_E_OUT_OF_RANGE, "a batch holds fewer than 2^31 voxels");
     DeviceGuard dg(ctx->device);
-    int rc = edit_prepare(ctx, insert ? "voxel inserts are" : "voxel removals are");
+    int rc = edit_prepare(ctx, op);
     if (rc != VRT_OK) return rc;
     if (host) { // xyz, then the material bytes behind it
         const uint64_t xyz_bytes = 12u * n;
@@ -1340,56 +1255,89 @@ int edit_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uin
         xyz = reinterpret_cast<const uint32_t *>(ctx->d_edit_input);
         materials = insert ? ctx->d_edit_input + xyz_bytes : nullptr;
     }
-    rc = edit_scratch(ctx, n, insert);
+    rc = edit_scratch(ctx, n, op);
     if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, insert ? vrt::kEditOpInsert : vrt::kEditOpRemove, xyz, materials, (uint32_t)n);
-    if (insert) VRT_HIP(ctx, hipMemsetAsync(ctx->d_edit_table, 0, ctx->edit_table_entries * sizeof(uint2), ctx->stream));
+    vrt::EditArgs a = edit_args(ctx, op, xyz, materials, (uint32_t)n);
     vrt::EditStatus s;
-    rc = run_edit(ctx, a, insert ? insert_steps(a.groups) : remove_steps(a.groups), true, &s);
-    if (rc == VRT_OK) rc = insert ? edit_error(ctx, s, kErrsOfInsert, "; nothing was inserted") : edit_error(ctx, s, kErrsOfRemove, "; nothing was removed");
-    if (rc != VRT_OK) return rc;
-    mark_written(ctx, s, insert ? kWritesOfInsert : kWritesOfRemove, s.bricks - s.new_bricks);
-    return VRT_OK;
+    rc = run_edit(ctx, a, &s);
+    if (rc == VRT_OK) mark_written(ctx, s, kEditOps[op].writes, s.bricks - s.new_bricks);
+    return rc;
 }
 
 // the scene's dead bricks given back: the chain over cells and bricks, as one scene write
 int compact(vrt_ctx *ctx, uint32_t out[2]) {
     const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
     const uint32_t brick_alloc = (uint32_t)(ctx->dsize[VRT_BUF_BRICK_START_INDEX] / 4u);
-    int rc = edit_scratch(ctx, std::max<uint64_t>(brick_alloc, 1u)); // its scratch: the per-voxel words of a batch of brick_alloc voxels
+    int rc = edit_scratch(ctx, std::max<uint64_t>(brick_alloc, 1u), vrt::kEditOpCompact); // its scratch: the per-voxel words of a batch of brick_alloc voxels
     if (rc != VRT_OK) return rc;
     vrt::EditArgs a = edit_args(ctx, vrt::kEditOpCompact, nullptr, nullptr, brick_alloc);
     a.cells = (uint32_t)cells;
     const uint32_t cell_groups = (uint32_t)((std::max<uint64_t>(cells, brick_alloc) + vrt::kEditBlock - 1u) / vrt::kEditBlock);
     VRT_HIP(ctx, hipMemsetAsync(a.vinfo, 0, (size_t)brick_alloc * sizeof(uint32_t), ctx->stream)); // no brick is live yet
     vrt::EditStatus s;
-    rc = run_edit(ctx, a, compact_steps(cell_groups, a.groups, std::min<uint32_t>(cell_groups, vrt::kEditCopyGroups)), false, &s);
-    if (rc == VRT_OK) rc = edit_error(ctx, s, kErrsOfCompact, "; nothing was compacted");
+    rc = run_edit(ctx, a, &s, cell_groups, std::min<uint32_t>(cell_groups, vrt::kEditCopyGroups));
     if (rc != VRT_OK) return rc;
     if (out) out[0] = s.bricks + s.new_bricks, out[1] = s.bricks;
     // the renamed cells, the filled holes and the cleared tail (a range whenever a brick was freed), the entries of binding 5 that were
     // unset; no dead brick: nothing was written
-    if (s.new_bricks) mark_written(ctx, s, kWritesOfCompact, s.bricks);
+    if (s.new_bricks) mark_written(ctx, s, kEditOps[vrt::kEditOpCompact].writes, s.bricks);
+    return VRT_OK;
+}
+
+// What the records of the item modes have in common: the shape's clipped range, and where its items lie, behind the *items of the
+// shapes before it.  false: the batch's items reach 2^31 (the sum is tested before it can wrap: *items < 2^31 on entry).
+bool place_items(const vrt::ClippedShape &c, uint32_t b, uint64_t *items, vrt::ShapeRec *r) {
+    uint64_t cells[3];
+    for (int k = 0; k < 3; k++) {
+        r->lo[k] = c.lo[k], r->hi[k] = c.hi[k];
+        cells[k] = (uint64_t)(c.hi[k] / b) - c.lo[k] / b + 1u;
+    }
+    r->first = (uint32_t)*items;
+    r->ncx = (uint32_t)cells[0];
+    r->ncxz = (uint32_t)(cells[0] * cells[2]); // (below the grid's cells, which fit 32 bits)
+    *items += vrt::shape_items(c, b);
+    return *items < vrt::kShapeItemsEnd;
+}
+
+// The item modes from their records on (at least one; the batch is screened, and edit_allowed has passed): the records staged into
+// device memory, with the elements of a write behind them where they are host memory (staged_elements of them; else data is device
+// memory, read in place), then the op's chain as one scene write.  A paint: `only` is its filter, *painted (may be NULL) its count.
+int edit_items(vrt_ctx *ctx, uint32_t op, const std::vector<vrt::ShapeRec> &recs, uint64_t items, uint32_t only = VRT_PAINT_ANY,
+               uint64_t *painted = nullptr, const uint16_t *data = nullptr, uint64_t staged_elements = 0) {
+    DeviceGuard dg(ctx->device);
+    const uint64_t rec_bytes = recs.size() * sizeof(vrt::ShapeRec);
+    int rc = edit_buffers(ctx);
+    if (rc == VRT_OK) rc = edit_scratch(ctx, items, op);
+    if (rc == VRT_OK) rc = stage_input(ctx, recs.data(), rec_bytes, staged_elements ? data : nullptr, staged_elements * sizeof(uint16_t));
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, op, nullptr, nullptr, (uint32_t)items);
+    a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
+    a.shape_count = (uint32_t)recs.size();
+    a.only = only;
+    a.data = staged_elements ? reinterpret_cast<const uint16_t *>(ctx->d_edit_input + rec_bytes) : data; // (behind records of 64 bytes: aligned)
+    vrt::EditStatus s;
+    rc = run_edit(ctx, a, &s);
+    if (rc != VRT_OK) return rc;
+    mark_written(ctx, s, kEditOps[op].writes, s.bricks - s.new_bricks);
+    if (painted) *painted = s.painted;
     return VRT_OK;
 }
 
 // n shapes (host memory) filled into, cleared from or painted on the scene (op: kEditOpFill / kEditOpClear / kEditOpPaint): the batch
-// screened and clipped on the host, one record per shape that holds a voxel of the grid's range staged into device memory, then the
-// op's part of the chain as one scene write.  A paint: `only` is its filter, *painted (may be NULL) the voxels it painted.
+// screened and clipped on the host, one record per shape that holds a voxel of the grid's range.
 int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t op, uint32_t only = VRT_PAINT_ANY, uint64_t *painted = nullptr) {
     if (!ctx) return VRT_E_INVALID_ARG;
-    const bool fill = op == vrt::kEditOpFill, paint = op == vrt::kEditOpPaint;
-    const char *nothing = fill ? "; nothing was filled" : paint ? "; nothing was painted" : "; nothing was cleared";
+    const char *nothing = kEditOps[op].nothing;
     if (only != VRT_PAINT_ANY && only > 255u) return fail(ctx, VRT_E_INVALID_ARG, std::string("only is neither VRT_PAINT_ANY nor a material 0..255") + nothing);
     if (n == 0) {
         if (painted) *painted = 0;
         return VRT_OK;
     }
     std::string why;
-    int rc = vrt::screen_shapes(shapes, n, fill || paint, &why); // (a paint's material is screened as a fill's)
+    int rc = vrt::screen_shapes(shapes, n, op != vrt::kEditOpClear, &why); // (a paint's material is screened as a fill's)
     if (rc != VRT_OK) return fail(ctx, rc, why + nothing);
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, "shape edits are not available on a context of the multi-GPU pipeline");
-    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    rc = edit_allowed(ctx, op);
+    if (rc != VRT_OK) return rc;
     const uint32_t b = ctx->cfg.brick_dimension;
     const uint32_t dim[3] = {ctx->cfg.dim_x * b, ctx->cfg.dim_y * b, ctx->cfg.dim_z * b};
     std::vector<vrt::ShapeRec> recs;
@@ -1398,50 +1346,25 @@ int edit_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t op, 
         vrt::ClippedShape c;
         if (!vrt::clip_shape(shapes[i], dim, &c)) continue;
         vrt::ShapeRec r{};
-        uint64_t cells[3];
-        for (int k = 0; k < 3; k++) {
-            r.lo[k] = c.lo[k], r.hi[k] = c.hi[k], r.centre[k] = c.centre[k];
-            cells[k] = (uint64_t)(c.hi[k] / b) - c.lo[k] / b + 1u;
-        }
-        r.r2 = c.r2, r.kind = c.kind, r.material = c.material;
-        r.first = (uint32_t)items;
-        r.ncx = (uint32_t)cells[0];
-        r.ncxz = (uint32_t)(cells[0] * cells[2]); // (below the grid's cells, which fit 32 bits)
-        items += vrt::shape_items(c, b); // (the sum is tested before it can wrap: items < 2^31 so far)
-        if (items >= vrt::kShapeItemsEnd)
+        if (!place_items(c, b, &items, &r))
             return fail(ctx, VRT_E_OUT_OF_RANGE, "shape " + std::to_string(i) + ": the batch's work items (one per occupancy word of every cell of every shape's clipped cell box) reach 2^31");
+        for (int k = 0; k < 3; k++) r.centre[k] = c.centre[k];
+        r.r2 = c.r2, r.kind = c.kind, r.material = c.material;
         recs.push_back(r);
     }
     if (recs.empty()) { // every shape empty after clipping: the device is not touched
         if (painted) *painted = 0;
         return VRT_OK;
     }
-    DeviceGuard dg(ctx->device);
-    rc = edit_prepare(ctx, "shape edits are");
-    if (rc != VRT_OK) return rc;
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
-    rc = stage_input(ctx, recs.data(), recs.size() * sizeof(vrt::ShapeRec));
-    if (rc == VRT_OK) rc = edit_scratch(ctx, items);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, op, nullptr, nullptr, (uint32_t)items);
-    a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
-    a.shape_count = (uint32_t)recs.size();
-    a.only = only;
-    vrt::EditStatus s;
-    rc = run_edit(ctx, a, fill ? insert_steps(a.groups) : paint ? paint_steps(a.groups) : remove_steps(a.groups), !paint, &s);
-    if (rc == VRT_OK) rc = edit_error(ctx, s, fill ? kErrsOfFill : paint ? kErrsOfPaint : kErrsOfClear, nothing);
-    if (rc != VRT_OK) return rc;
-    mark_written(ctx, s, fill ? kWritesOfInsert : paint ? kWritesOfPaint : kWritesOfRemove, s.bricks - s.new_bricks);
-    if (painted) *painted = s.painted;
-    return VRT_OK;
+    return edit_items(ctx, op, recs, items, only, painted);
 }
 
-// n boxes (host memory) written from their elements (host: data is host memory, staged into device memory behind the records; else
-// device memory, read in place): the batch screened on the host, one record per box that reaches into the grid, then the chain as one
-// scene write.  The elements are screened on the device in both forms (vrt_edit_validate), before any kernel writes the scene.
+// n boxes (host memory) written from their elements (host: data is host memory; else device memory): the batch screened on the host,
+// one record per box that reaches into the grid.  The elements are screened on the device in both forms (vrt_edit_validate), before
+// any kernel writes the scene.
 int write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements, bool host) {
     if (!ctx) return VRT_E_INVALID_ARG;
-    const char *nothing = "; nothing was written";
+    const char *nothing = kEditOps[vrt::kEditOpWrite].nothing;
     if (n == 0) return VRT_OK;
     const uint32_t b = ctx->cfg.brick_dimension;
     std::string why;
@@ -1450,8 +1373,8 @@ int write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint
     if (rc != VRT_OK) return fail(ctx, rc, why + nothing);
     if (!host && (reinterpret_cast<uintptr_t>(data) & 1u)) return fail(ctx, VRT_E_INVALID_ARG, std::string("data must be 2-byte aligned") + nothing);
     if (total == 0) return VRT_OK;
-    if (ctx->dist) return fail(ctx, VRT_E_STATE, "dense box writes are not available on a context of the multi-GPU pipeline");
-    if (!ctx->grid_uploaded) return fail(ctx, VRT_E_STATE, "no grid state uploaded yet (vrt_upload_grid)");
+    rc = edit_allowed(ctx, vrt::kEditOpWrite);
+    if (rc != VRT_OK) return rc;
     const uint32_t dim[3] = {ctx->cfg.dim_x * b, ctx->cfg.dim_y * b, ctx->cfg.dim_z * b};
     uint64_t first = 0, second = 0;
     if (vrt::first_overlap(boxes, n, dim, &first, &second))
@@ -1463,57 +1386,28 @@ int write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint
         vrt::WriteBox w;
         if (vrt::clip_write_box(boxes[k], dim, s, base, &w)) {
             vrt::ShapeRec r{};
-            uint64_t cells[3];
-            for (int j = 0; j < 3; j++) {
-                r.lo[j] = w.c.lo[j], r.hi[j] = w.c.hi[j], r.centre[j] = w.origin[j];
-                cells[j] = (uint64_t)(w.c.hi[j] / b) - w.c.lo[j] / b + 1u;
-            }
-            r.r2 = w.sx, r.kind = VRT_SHAPE_BOX, r.material = w.sz, r.base = w.base;
-            r.first = (uint32_t)items;
-            r.ncx = (uint32_t)cells[0];
-            r.ncxz = (uint32_t)(cells[0] * cells[2]);
-            items += vrt::shape_items(w.c, b); // (the sum is tested before it can wrap: items < 2^31 so far)
-            if (items >= vrt::kShapeItemsEnd)
+            if (!place_items(w.c, b, &items, &r))
                 return fail(ctx, VRT_E_OUT_OF_RANGE, "box " + std::to_string(k) + ": the batch's work items (one per occupancy word of every cell that a box's part inside the grid touches) reach 2^31" + nothing);
+            for (int j = 0; j < 3; j++) r.origin[j] = w.origin[j];
+            r.side_x = w.sx, r.kind = VRT_SHAPE_BOX, r.side_z = w.sz, r.base = w.base;
             recs.push_back(r);
         }
         base += s.volume;
     }
     if (recs.empty()) return VRT_OK; // no box reaches into the grid: the device is not touched
-    DeviceGuard dg(ctx->device);
-    rc = edit_prepare(ctx, "dense box writes are");
-    if (rc != VRT_OK) return rc;
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
-    const uint64_t rec_bytes = recs.size() * sizeof(vrt::ShapeRec);
-    rc = stage_input(ctx, recs.data(), rec_bytes, host ? data : nullptr, host ? total * sizeof(uint16_t) : 0u);
-    if (rc == VRT_OK) rc = edit_scratch(ctx, items);
-    if (rc != VRT_OK) return rc;
-    vrt::EditArgs a = edit_args(ctx, vrt::kEditOpWrite, nullptr, nullptr, (uint32_t)items);
-    a.shapes = reinterpret_cast<const vrt::ShapeRec *>(ctx->d_edit_input);
-    a.shape_count = (uint32_t)recs.size();
-    a.data = host ? reinterpret_cast<const uint16_t *>(ctx->d_edit_input + rec_bytes) : data; // (behind records of 64 bytes: aligned)
-    vrt::EditStatus s;
-    rc = run_edit(ctx, a, write_steps(a.groups), true, &s);
-    if (rc == VRT_OK) rc = edit_error(ctx, s, kErrsOfWrite, nothing);
-    if (rc != VRT_OK) return rc;
-    mark_written(ctx, s, kWritesOfInsert, s.bricks - s.new_bricks);
-    return VRT_OK;
+    return edit_items(ctx, vrt::kEditOpWrite, recs, items, VRT_PAINT_ANY, nullptr, data, host ? total : 0u);
 }
 
 } // namespace
 
 extern "C" {
 
-int vrt_write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) {
-    return write_boxes(ctx, boxes, n, data, data_elements, true);
-}
-int vrt_write_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) {
-    return write_boxes(ctx, boxes, n, data, data_elements, false);
-}
-int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, false); }
-int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, true, true); }
-int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, false); }
-int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, false, true); }
+int vrt_write_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) { return write_boxes(ctx, boxes, n, data, data_elements, true); }
+int vrt_write_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, const uint16_t *data, uint64_t data_elements) { return write_boxes(ctx, boxes, n, data, data_elements, false); }
+int vrt_insert_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, vrt::kEditOpInsert, false); }
+int vrt_insert_voxels(vrt_ctx *ctx, const uint32_t *xyz, const uint8_t *materials, uint64_t n) { return edit_voxels(ctx, xyz, materials, n, vrt::kEditOpInsert, true); }
+int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, vrt::kEditOpRemove, false); }
+int vrt_remove_voxels(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n) { return edit_voxels(ctx, xyz, nullptr, n, vrt::kEditOpRemove, true); }
 int vrt_fill_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, vrt::kEditOpFill); }
 int vrt_clear_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n) { return edit_shapes(ctx, shapes, n, vrt::kEditOpClear); }
 int vrt_paint_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t only, uint64_t *painted) {
@@ -1523,7 +1417,7 @@ int vrt_paint_shapes(vrt_ctx *ctx, const vrt_shape *shapes, uint64_t n, uint32_t
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     if (!ctx) return VRT_E_INVALID_ARG;
     DeviceGuard dg(ctx->device);
-    const int rc = edit_prepare(ctx, "brick compaction is");
+    const int rc = edit_prepare(ctx, vrt::kEditOpCompact);
     if (rc != VRT_OK) return rc;
     return compact(ctx, out);
 }
@@ -1532,7 +1426,7 @@ int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     if (!ctx) return VRT_E_INVALID_ARG;
     if (!out) return fail(ctx, VRT_E_INVALID_ARG, "out is NULL");
     DeviceGuard dg(ctx->device);
-    int rc = edit_prepare(ctx);
+    int rc = edit_prepare(ctx, vrt::kEditOpInsert);
     if (rc != VRT_OK) return rc;
     if (!ctx->edit_state_valid) {
         vrt::EditArgs a = edit_args(ctx, vrt::kEditOpInsert, nullptr, nullptr, 0);
