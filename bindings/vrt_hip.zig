@@ -315,6 +315,33 @@ pub const BoxResult = extern struct {
     hi: [3]i32,
     count: u64,
 };
+/// One sweep of vrt_sweep_boxes, 48 bytes: the box lo..hi in the continuous space of vrt_grid_insert's coordinates and the displacement
+/// of the whole box.
+pub const BoxSweep = extern struct {
+    lo: [3]f32,
+    flags: u32 = 0,
+    hi: [3]f32,
+    _reserved: u32 = 0,
+    move: [3]f32,
+    _reserved2: u32 = 0,
+};
+/// Its answer, 32 bytes: the fraction of `move` travelled (1 for a free move), the status bits, and the voxel that stops the box with
+/// its material (VOXEL_EMPTY without a hit) and the face that was touched (0 none; +-1 x, +-2 y, +-3 z).
+pub const SweepHit = extern struct {
+    t: f32,
+    status: u32,
+    material: u32,
+    normal: i32,
+    voxel: [3]i32,
+    _reserved: u32,
+};
+pub const SWEEP_HIT: u32 = 1;
+pub const SWEEP_START_SOLID: u32 = 2;
+pub const SWEEP_INVALID: u32 = 4;
+/// The limits of a sweep, per axis: hi - lo, |move|, and |lo|, |hi|.
+pub const SWEEP_MAX_EXTENT: f32 = 32.0;
+pub const SWEEP_MAX_MOVE: f32 = 256.0;
+pub const SWEEP_MAX_COORD: f32 = 4194304.0;
 /// One shape of vrt_fill_shapes / vrt_clear_shapes, 32 bytes, in the coordinates vrt_grid_insert takes; clipped to the grid.
 /// Box: lo / hi are the inclusive corners.  Sphere: lo is the centre, hi[0] the radius (0..SHAPE_MAX_RADIUS), hi[1] = hi[2] = 0.
 pub const SHAPE_BOX: u32 = 0;
@@ -409,6 +436,9 @@ pub extern fn vrt_grid_query_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n
 pub extern fn vrt_read_boxes(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
 pub extern fn vrt_read_boxes_device(ctx: ?*Ctx, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
 pub extern fn vrt_grid_read_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n: u64, out: [*c]u16, out_elements: u64) c_int;
+pub extern fn vrt_sweep_boxes(ctx: ?*Ctx, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
+pub extern fn vrt_sweep_boxes_device(ctx: ?*Ctx, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
+pub extern fn vrt_grid_sweep_boxes(g: ?*const Grid, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
 pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;

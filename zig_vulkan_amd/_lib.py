@@ -182,6 +182,16 @@ class Shape(C.Structure):  # vrt_shape (32 bytes)
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("kind", C.c_uint32), ("material", C.c_uint32)]
 
 
+class BoxSweep(C.Structure):  # vrt_box_sweep (48 bytes)
+    _fields_ = [("lo", C.c_float * 3), ("flags", C.c_uint32), ("hi", C.c_float * 3), ("_reserved", C.c_uint32),
+                ("move", C.c_float * 3), ("_reserved2", C.c_uint32)]
+
+
+class SweepHit(C.Structure):  # vrt_sweep_hit (32 bytes)
+    _fields_ = [("t", C.c_float), ("status", C.c_uint32), ("material", C.c_uint32), ("normal", C.c_int32),
+                ("voxel", C.c_int32 * 3), ("_reserved", C.c_uint32)]
+
+
 SHAPE_BOX, SHAPE_SPHERE = 0, 1  # VRT_SHAPE_BOX, VRT_SHAPE_SPHERE
 SHAPE_MAX_RADIUS = 16384        # VRT_SHAPE_MAX_RADIUS
 SHAPES_MAX = 4096               # VRT_SHAPES_MAX
@@ -191,10 +201,15 @@ VOXEL_EMPTY = 0xFFFF        # VRT_VOXEL_EMPTY
 READ_BOXES_MAX = 4096       # VRT_READ_BOXES_MAX
 VOXEL_KEEP = 0xFFFE         # VRT_VOXEL_KEEP
 WRITE_BOXES_MAX = 4096      # VRT_WRITE_BOXES_MAX
+SWEEP_HIT, SWEEP_START_SOLID, SWEEP_INVALID = 1, 2, 4  # VRT_SWEEP_HIT, VRT_SWEEP_START_SOLID, VRT_SWEEP_INVALID
+SWEEP_MAX_EXTENT = 32.0       # VRT_SWEEP_MAX_EXTENT
+SWEEP_MAX_MOVE = 256.0        # VRT_SWEEP_MAX_MOVE
+SWEEP_MAX_COORD = 4194304.0   # VRT_SWEEP_MAX_COORD
 
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
 assert C.sizeof(BoxQuery) == 32 and C.sizeof(BoxResult) == 32 and C.sizeof(Shape) == 32
+assert C.sizeof(BoxSweep) == 48 and C.sizeof(SweepHit) == 32
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -286,6 +301,9 @@ SIGNATURES = {
     "vrt_write_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_write_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "vrt_grid_write_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "vrt_sweep_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_sweep_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_grid_sweep_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_remove_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

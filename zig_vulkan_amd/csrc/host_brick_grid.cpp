@@ -362,6 +362,63 @@ int BrickGrid::readBoxes(const vrt_box_query *boxes, uint64_t n, uint16_t *out, 
     return VRT_OK;
 }
 
+int BrickGrid::sweepBoxes(const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits, std::string *why) const {
+    if (n && (!sweeps || !hits)) {
+        if (why) *why = "sweeps or hits is NULL";
+        return VRT_E_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n; i++)
+        if (sweeps[i].flags | sweeps[i]._reserved | sweeps[i]._reserved2) {
+            if (why) *why = "sweep " + std::to_string(i) + " has unknown flag bits or a non-zero _reserved";
+            return VRT_E_INVALID_ARG;
+        }
+    const vrt_grid_state &d = device_state_;
+    const int64_t b = brick_dimension_;
+    const int64_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
+    // the slab clipped to the grid, its voxels in the order y, z, x of the caller's count: the first solid one is the contact
+    const auto solid = [&](const SweepSlabRange &s, SweepContact &c) {
+        const int32_t lo[3] = {s.x0, s.y0, s.z0}, hi[3] = {s.x1, s.y1, s.z1};
+        int64_t l[3], h[3];
+        for (int k = 0; k < 3; k++) {
+            l[k] = std::max<int64_t>(lo[k], 0);
+            h[k] = std::min<int64_t>(hi[k], dim[k] - 1);
+            if (l[k] > h[k]) return false;
+        }
+        bool any = false; // a slab in the air is told by its cells' status bits alone
+        for (int64_t cy = (dim[1] - 1 - h[1]) / b; cy <= (dim[1] - 1 - l[1]) / b && !any; cy++)
+            for (int64_t cz = l[2] / b; cz <= h[2] / b && !any; cz++)
+                for (int64_t cx = l[0] / b; cx <= h[0] / b && !any; cx++) {
+                    const size_t grid_index = (size_t)cx + (size_t)d.dim_x * ((size_t)cz + (size_t)d.dim_z * (size_t)cy);
+                    any = (brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u;
+                }
+        if (!any) return false;
+        for (int64_t y = l[1]; y <= h[1]; y++) {
+            const int64_t fy = dim[1] - 1 - y; // Grid.zig:135
+            for (int64_t z = l[2]; z <= h[2]; z++)
+                for (int64_t cx = l[0] / b; cx <= h[0] / b; cx++) {
+                    const size_t grid_index = (size_t)cx + (size_t)d.dim_x * ((size_t)(z / b) + (size_t)d.dim_z * (size_t)(fy / b)); // gridAt
+                    if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue;
+                    const uint32_t brick_index = brick_indices[grid_index];
+                    const int64_t x0 = std::max(l[0], cx * b), x1 = std::min(h[0], cx * b + b - 1);
+                    const uint32_t row_mask = ((1u << (x1 - x0 + 1)) - 1u) << (x0 - cx * b);
+                    const uint32_t row_bit = (uint32_t)(b * (z % b + b * (fy % b))); // voxelAt of the row's x = 0
+                    const uint32_t row = (brick_occupancy[(size_t)brick_index * brick_bytes_ + row_bit / 8] >> (row_bit % 8)) & row_mask;
+                    if (!row) continue;
+                    const uint32_t x = (uint32_t)__builtin_ctz(row);
+                    c.x = (int32_t)(cx * b + x), c.y = (int32_t)y, c.z = (int32_t)z;
+                    c.material = material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu) + row_bit + x]; // comp:422-425
+                    return true;
+                }
+        }
+        return false;
+    };
+    for (uint64_t i = 0; i < n; i++) {
+        const vrt_box_sweep &s = sweeps[i];
+        sweep_box(s.lo, s.hi, s.move, 0u, solid, &hits[i]);
+    }
+    return VRT_OK;
+}
+
 bool BrickGrid::shapeRows(const ClippedShape &s, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t rows[64]) const {
     const uint32_t b = brick_dimension_;
     std::fill(rows, rows + b * b, (uint8_t)0);

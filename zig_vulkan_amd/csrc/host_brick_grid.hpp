@@ -14,6 +14,7 @@
 #include "../../include/vrt_hip.h"
 #include "vrt_read_boxes.h"
 #include "vrt_shapes.h"
+#include "vrt_sweep.h"
 
 namespace vrt {
 
@@ -85,6 +86,9 @@ public:
     // the voxels of every box as getVoxels answers them, packed box after box, x fastest, then z, then y; the box is not clipped, and
     // what lies outside the grid is VRT_VOXEL_EMPTY.  A batch that is refused (screen_read_boxes) writes nothing; *why (may be null) says why.
     int readBoxes(const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements, std::string *why = nullptr) const;
+    // per sweep: how far the box gets along its move and the voxel that stops it (include/vrt_hip.h, the box-sweep block; the walk is
+    // vrt_sweep.h's).  A batch that holds a non-zero flags / _reserved / _reserved2 is refused and writes nothing; *why (may be null) names the item.
+    int sweepBoxes(const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits, std::string *why = nullptr) const;
 
     // Shape edits (the reference has none: include/vrt_hip.h defines them).  The arrays and the deltas that insertUnlocked /
     // removeManyUnlocked give on the shapes' voxels (shapes in array order, within a shape the cells that hold a voxel of it in

@@ -5,6 +5,10 @@
 #include <cstring>
 #include "host_brick_grid.hpp"
 
+namespace vrt_impl {
+int fail(vrt_ctx *ctx, int code, const std::string &msg); // vrt_api.hip; ctx == nullptr: the thread's text behind vrt_last_error(NULL)
+}
+
 namespace {
 
 struct V3 {
@@ -275,6 +279,13 @@ int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t
 int vrt_grid_read_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements) {
     if (!g) return VRT_E_INVALID_ARG;
     return reinterpret_cast<const vrt::BrickGrid *>(g)->readBoxes(boxes, n, out, out_elements);
+}
+
+int vrt_grid_sweep_boxes(const vrt_grid *g, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits) {
+    if (!g) return VRT_E_INVALID_ARG;
+    std::string why;
+    const int rc = reinterpret_cast<const vrt::BrickGrid *>(g)->sweepBoxes(sweeps, n, hits, &why);
+    return rc == VRT_OK ? rc : vrt_impl::fail(nullptr, rc, why); // (a grid keeps no error text: vrt_last_error(NULL) has it)
 }
 
 int vrt_grid_fill_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {

@@ -2,7 +2,8 @@
 // their host side; the first-hit buffer pass (vrt_trace_aux, vrt_trace_aux_device), a second mode of the same two kernels: the
 // camera ray of every pixel, formed in the kernel, and only the planes of its hit record that were asked for; and the camera ray of a
 // pixel (vrt_camera_pixel_ray); and the volume queries (vrt_get_voxels, vrt_query_boxes and their _device forms), modes 2 and 3 of the
-// same two kernels, which read bindings 2-6 only, and the dense box reads (vrt_read_boxes, vrt_read_boxes_device), their mode 4.
+// same two kernels, which read bindings 2-6 only, and the dense box reads (vrt_read_boxes, vrt_read_boxes_device), their mode 4, and
+// the box sweeps (vrt_sweep_boxes, vrt_sweep_boxes_device), their mode 5.
 // A ray query sees the scene as the next frame would: the structures derived from the scene buffers are refreshed through the frames'
 // own path (refresh_derived) on the primary stream, after every upload so far.  The kernels are compiled with the product's
 // arithmetic flags, so that a query is bit-equal to the shader's GridHit (vrt_math.h's contract).
@@ -15,6 +16,7 @@
 #include <vector>
 #include "vrt_ctx.h"
 #include "vrt_read_boxes.h"
+#include "vrt_sweep.h"
 #include "vrt_trace_kernels.h" // (after vrt_ctx.h: behind its <chrono>, the host pass rejects the walk's gfx950 inline assembly)
 
 namespace vrt {
@@ -22,6 +24,8 @@ namespace vrt {
 static_assert(sizeof(vrt_ray_query) == 32, "vrt_ray_query is two dwordx4");
 static_assert(sizeof(vrt_ray_hit) == 48, "vrt_ray_hit is three dwordx4");
 static_assert(sizeof(vrt_box_query) == 32 && sizeof(vrt_box_result) == 32, "vrt_box_query and vrt_box_result are two dwordx4 each");
+static_assert(sizeof(vrt_box_sweep) == 48 && sizeof(vrt_sweep_hit) == 32, "vrt_box_sweep is three dwordx4 and vrt_sweep_hit two");
+static_assert(offsetof(vrt_box_sweep, hi) == 16 && offsetof(vrt_box_sweep, move) == 32 && offsetof(vrt_sweep_hit, voxel) == 16, "the kernel reads and writes the records as dwordx4");
 static_assert(offsetof(vrt_box_query, flags) == 24 && offsetof(vrt_box_result, count) == 24, "the kernel reads flags and writes count at dword 6");
 
 // The one kernel argument of vrt_ray_query_b4 / _b8: the scene as the frames see it, and one launch's share of the batch.
@@ -52,8 +56,11 @@ struct QueryArgs {
     uint32_t read_boxes;         // boxes of the batch
     uint32_t read_first_item;    // the first item of this launch
     uint32_t read_first_element; // the element vol_materials points at (the first element of the launch's first item, or 0)
+    // mode 5 (the box sweeps): n sweeps, one per lane
+    const u32x4 *sweep_boxes;    // vrt_box_sweep as three dwordx4 (16-byte aligned, like the hits)
+    u32x4 *sweep_hits;           // vrt_sweep_hit as two dwordx4
 };
-constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u, kQueryModeVoxels = 2u, kQueryModeBoxes = 3u, kQueryModeRead = 4u;
+constexpr uint32_t kQueryModeRays = 0u, kQueryModeAux = 1u, kQueryModeVoxels = 2u, kQueryModeBoxes = 3u, kQueryModeRead = 4u, kQueryModeSweep = 5u;
 
 constexpr uint32_t kQueryBlock = 256u;             // threads per workgroup: four waves, one ray per lane
 constexpr uint64_t kQueryLaunchRays = 1ull << 24;  // rays per launch (65 536 workgroups); larger batches are launched in pieces
@@ -363,6 +370,94 @@ VRT_DI void read_query(const QueryArgs &a) {
     if (count) *dst = (uint16_t)v0;
 }
 
+// Mode 5: one sweep per lane.  The walk over the plane crossings is vrt_sweep.h's, shared with BrickGrid::sweepBoxes; this is the test of
+// a slab of voxels.  The slab is clipped to the grid and runs over the cells it covers, the rows of cells with the smallest y (the
+// largest flipped y) first: the status bit before any other load, then the brick index, then the occupancy words masked with slab
+// intersected with cell, as mode 3 builds its masks.  With y flipped the first voxel of a cell by (y, z, x) is the lowest set bit of its
+// highest layer that has one; a cell's candidate is packed, relative to the slab's corner, into one key (a slab has fewer than 64 layers
+// on every axis), the smallest key wins, and a row of cells that gave one ends the search.  Only the winner's material is loaded.
+template <int B>
+struct SweepSlab {
+    const QueryArgs &a;
+    VRT_DI bool operator()(const SweepSlabRange &s, SweepContact &c) const {
+        constexpr uint32_t kBits = (uint32_t)(B * B * B), kShift = B == 8 ? 3u : 2u, kMask = (uint32_t)B - 1u;
+        const vrt_grid_state &g = a.p.grid;
+        // clipped to the grid (a voxel dimension may exceed 2^31; a sweep's layers stay below 2^23 in magnitude)
+        const int32_t x0 = std::max(s.x0, 0), y0 = std::max(s.y0, 0), z0 = std::max(s.z0, 0);
+        const int32_t x1 = (int32_t)std::min<int64_t>(s.x1, (int64_t)g.voxel_dim_x - 1), y1 = (int32_t)std::min<int64_t>(s.y1, (int64_t)g.voxel_dim_y - 1);
+        const int32_t z1 = (int32_t)std::min<int64_t>(s.z1, (int64_t)g.voxel_dim_z - 1);
+        if (x0 > x1 || y0 > y1 || z0 > z1) return false;
+        const uint32_t top = g.voxel_dim_y - 1u;
+        const uint32_t fy0 = top - (uint32_t)y1, fy1 = top - (uint32_t)y0; // Grid.zig:135
+        const uint64_t *occupancy = reinterpret_cast<const uint64_t *>(a.p.brick_occupancy);
+        uint32_t best = ~0u, best_brick = 0u; // the key: (y - y0) << 12 | (z - z0) << 6 | (x - x0)
+        const uint32_t cx0 = (uint32_t)x0 >> kShift, cx1 = (uint32_t)x1 >> kShift, cz0 = (uint32_t)z0 >> kShift, cz1 = (uint32_t)z1 >> kShift;
+        const uint32_t cy0 = fy0 >> kShift;
+        for (uint32_t cy = fy1 >> kShift;; cy--) {
+            const uint32_t by = cy << kShift;
+            const uint32_t yl = fy0 > by ? fy0 - by : 0u, yh = std::min(fy1 - by, kMask); // the slab's flipped layers within the row
+            for (uint32_t cz = cz0; cz <= cz1; cz++) {
+                const uint32_t bz = cz << kShift;
+                const uint32_t zl = (uint32_t)z0 > bz ? (uint32_t)z0 - bz : 0u, zh = std::min((uint32_t)z1 - bz, kMask);
+                for (uint32_t cx = cx0; cx <= cx1; cx++) {
+                    const uint32_t cell = cx + g.dim_x * (cz + g.dim_z * cy); // gridAt
+                    if (!cell_loaded(a.p, cell)) continue;
+                    const uint32_t brick = a.p.brick_index[cell];
+                    if (brick >= a.vol_bricks) continue;
+                    const uint32_t bx = cx << kShift;
+                    const uint32_t xl = (uint32_t)x0 > bx ? (uint32_t)x0 - bx : 0u, xh = std::min((uint32_t)x1 - bx, kMask);
+                    uint32_t layer = 0u, bit = 0u; // the cell's first voxel: its flipped layer, and its bit x + B z within the layer
+                    bool found = false;
+                    if constexpr (B == 8) {
+                        const uint64_t mask = group_bits(xl, xh, 0x0101010101010101ull) & group_range(zl, zh, 8u);
+                        for (uint32_t l = yh + 1u; l-- > yl;) {
+                            const uint64_t m = occupancy[(uint64_t)brick * 8u + l] & mask;
+                            if (m) {
+                                layer = l, bit = (uint32_t)__builtin_ctzll(m), found = true;
+                                break;
+                            }
+                        }
+                    } else {
+                        const uint64_t mask = group_bits(xl, xh, 0x1111111111111111ull) & (0x0001000100010001ull * (group_range(zl, zh, 4u) & 0xFFFFull)) & group_range(yl, yh, 16u);
+                        const uint64_t m = occupancy[brick] & mask;
+                        if (m) {
+                            layer = (63u - (uint32_t)__builtin_clzll(m)) >> 4;
+                            bit = (uint32_t)__builtin_ctz((uint32_t)(m >> (16u * layer)) & 0xFFFFu), found = true;
+                        }
+                    }
+                    if (!found) continue;
+                    const uint32_t key = ((fy1 - (by + layer)) << 12) | ((bz + (bit >> kShift) - (uint32_t)z0) << 6) | (bx + (bit & kMask) - (uint32_t)x0);
+                    if (key < best) best = key, best_brick = brick;
+                }
+            }
+            if (best != ~0u || cy == cy0) break;
+        }
+        if (best == ~0u) return false;
+        const uint32_t x = (uint32_t)x0 + (best & 63u), z = (uint32_t)z0 + ((best >> 6) & 63u), fy = fy1 - (best >> 12);
+        const uint32_t nth_bit = (x & kMask) + (uint32_t)B * ((z & kMask) + (uint32_t)B * (fy & kMask)); // voxelAt
+        const uint32_t entry = (a.p.brick_start_index[best_brick] & 0x7FFFFFFFu) + nth_bit;           // comp:422-425
+        c.material = entry < a.vol_bricks * kBits ? (uint32_t)a.p.material_index[entry] : (uint32_t)VRT_VOXEL_EMPTY; // (as mode 2)
+        c.x = (int32_t)x, c.y = y0 + (int32_t)(best >> 12), c.z = (int32_t)z;
+        return true;
+    }
+};
+
+// a wave reads 3 KiB of sweeps and stores 2 KiB of hits, both contiguous
+template <int B>
+VRT_DI void sweep_query(const QueryArgs &a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const u32x4 *src = a.sweep_boxes + 3u * i;
+    const u32x4 q0 = src[0], q1 = src[1], q2 = src[2]; // lo flags | hi _reserved | move _reserved2
+    const float lo[3] = {as_f32(q0.x), as_f32(q0.y), as_f32(q0.z)}, hi[3] = {as_f32(q1.x), as_f32(q1.y), as_f32(q1.z)};
+    const float move[3] = {as_f32(q2.x), as_f32(q2.y), as_f32(q2.z)};
+    vrt_sweep_hit h;
+    sweep_box(lo, hi, move, q0.w | q1.w | q2.w, SweepSlab<B>{a}, &h);
+    u32x4 *dst = a.sweep_hits + 2u * i;
+    dst[0] = u32x4{__builtin_bit_cast(uint32_t, h.t), h.status, h.material, (uint32_t)h.normal};
+    dst[1] = u32x4{(uint32_t)h.voxel[0], (uint32_t)h.voxel[1], (uint32_t)h.voxel[2], 0u};
+}
+
 // One GridHit of the frames' own walk per ray, one ray per lane.
 template <int B>
 VRT_DI void ray_query(const QueryArgs &a) {
@@ -380,6 +475,10 @@ VRT_DI void ray_query(const QueryArgs &a) {
     }
     if (a.mode == kQueryModeRead) {
         read_query<B>(a);
+        return;
+    }
+    if (a.mode == kQueryModeSweep) {
+        sweep_query<B>(a);
         return;
     }
     const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
@@ -453,17 +552,21 @@ int volume_begin(vrt_ctx *ctx) {
     return VRT_OK;
 }
 
-// The three batched queries: the kernels' mode, the elements one launch takes at most and one workgroup takes, and the bytes of an
-// element going in and coming out
+// The four batched queries: the kernels' mode, the elements one launch takes at most and one workgroup takes, and the bytes of an
+// element going in and coming out.  swap: the host form stages the elements in through the hits' buffer and out through the rays'
+// (a sweep goes in as 48 bytes and comes out as 32, the other way round from a ray)
 struct QueryKind {
     uint32_t mode;
     uint64_t per_launch;
     uint32_t per_group;
     uint32_t in_bytes, out_bytes;
+    bool swap = false;
 };
 constexpr QueryKind kRays = {vrt::kQueryModeRays, vrt::kQueryLaunchRays, vrt::kQueryBlock, sizeof(vrt_ray_query), sizeof(vrt_ray_hit)};
 constexpr QueryKind kVoxels = {vrt::kQueryModeVoxels, vrt::kQueryLaunchRays, vrt::kQueryBlock, 3u * sizeof(uint32_t), sizeof(uint16_t)};
 constexpr QueryKind kBoxes = {vrt::kQueryModeBoxes, vrt::kQueryLaunchBoxes, vrt::kBoxesPerGroup, sizeof(vrt_box_query), sizeof(vrt_box_result)};
+constexpr QueryKind kSweeps = {vrt::kQueryModeSweep, vrt::kQueryLaunchRays, vrt::kQueryBlock, sizeof(vrt_box_sweep), sizeof(vrt_sweep_hit), true};
+static_assert(kSweeps.in_bytes <= kRays.out_bytes && kSweeps.out_bytes <= kRays.in_bytes, "a sweep goes in through a ray's hit and comes out through its query");
 static_assert(kVoxels.in_bytes <= kRays.in_bytes && kBoxes.in_bytes <= kRays.in_bytes && kVoxels.out_bytes <= kRays.out_bytes && kBoxes.out_bytes <= kRays.out_bytes,
               "a ray's share of the host forms' device buffers holds an element of any kind");
 
@@ -478,6 +581,7 @@ int launch_batch(vrt_ctx *ctx, const QueryKind &k, const void *in, uint64_t n, v
         void *dst = static_cast<uint8_t *>(out) + first * k.out_bytes;
         if (k.mode == vrt::kQueryModeRays) a.rays = static_cast<const vrt_ray_query *>(src), a.hits = static_cast<vrt_ray_hit *>(dst);
         else if (k.mode == vrt::kQueryModeVoxels) a.vol_xyz = static_cast<const uint32_t *>(src), a.vol_materials = static_cast<uint16_t *>(dst);
+        else if (k.mode == vrt::kQueryModeSweep) a.sweep_boxes = static_cast<const vrt::u32x4 *>(src), a.sweep_hits = static_cast<vrt::u32x4 *>(dst);
         else a.vol_boxes = static_cast<const vrt::u32x4 *>(src), a.vol_results = static_cast<vrt::u32x4 *>(dst);
         a.n = std::min<uint64_t>(n - first, k.per_launch);
         const dim3 groups((uint32_t)((a.n + k.per_group - 1u) / k.per_group));
@@ -493,12 +597,14 @@ int staged_batch(vrt_ctx *ctx, const QueryKind &k, const void *in, uint64_t n, v
     const uint64_t want = std::min<uint64_t>(n, vrt::kQueryHostPieceRays);
     int rc = grow_device(ctx, ctx->query_capacity, want, true, ctx->d_query_rays, want * sizeof(vrt_ray_query), ctx->d_query_hits, want * sizeof(vrt_ray_hit));
     if (rc != VRT_OK) return rc;
+    void *const d_in = k.swap ? static_cast<void *>(ctx->d_query_hits) : static_cast<void *>(ctx->d_query_rays);
+    void *const d_out = k.swap ? static_cast<void *>(ctx->d_query_rays) : static_cast<void *>(ctx->d_query_hits);
     for (uint64_t first = 0; first < n; first += want) {
         const uint64_t m = std::min(n - first, want);
-        VRT_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, static_cast<const uint8_t *>(in) + first * k.in_bytes, m * k.in_bytes, hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_batch(ctx, k, ctx->d_query_rays, m, ctx->d_query_hits);
+        VRT_HIP(ctx, hipMemcpyAsync(d_in, static_cast<const uint8_t *>(in) + first * k.in_bytes, m * k.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_batch(ctx, k, d_in, m, d_out);
         if (rc != VRT_OK) return rc;
-        VRT_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(out) + first * k.out_bytes, ctx->d_query_hits, m * k.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VRT_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(out) + first * k.out_bytes, d_out, m * k.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     VRT_HIP(ctx, wait_stream(ctx->stream));
     return VRT_OK;
@@ -761,6 +867,30 @@ int vrt_query_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, vrt_bo
     const int rc = volume_begin(ctx);
     if (rc != VRT_OK) return rc;
     return staged_batch(ctx, kBoxes, boxes, n, results);
+}
+
+int vrt_sweep_boxes_device(vrt_ctx *ctx, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!sweeps || !hits) return fail(ctx, VRT_E_INVALID_ARG, "sweeps or hits is NULL");
+    if ((reinterpret_cast<uintptr_t>(sweeps) | reinterpret_cast<uintptr_t>(hits)) & 15u) return fail(ctx, VRT_E_INVALID_ARG, "sweeps and hits must be 16-byte aligned");
+    DeviceGuard dg(ctx->device);
+    const int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    return launch_batch(ctx, kSweeps, sweeps, n, hits);
+}
+
+int vrt_sweep_boxes(vrt_ctx *ctx, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    if (n == 0) return VRT_OK;
+    if (!sweeps || !hits) return fail(ctx, VRT_E_INVALID_ARG, "sweeps or hits is NULL");
+    for (uint64_t i = 0; i < n; i++)
+        if (sweeps[i].flags | sweeps[i]._reserved | sweeps[i]._reserved2)
+            return fail(ctx, VRT_E_INVALID_ARG, "sweep " + std::to_string(i) + " has unknown flag bits or a non-zero _reserved");
+    DeviceGuard dg(ctx->device);
+    const int rc = volume_begin(ctx);
+    if (rc != VRT_OK) return rc;
+    return staged_batch(ctx, kSweeps, sweeps, n, hits);
 }
 
 int vrt_read_boxes(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements) {

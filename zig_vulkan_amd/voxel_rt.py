@@ -145,6 +145,17 @@ class BrickGrid:
         flat = write_box_data(q, data)
         check(lib.vrt_grid_write_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data if flat.size else None, flat.size))
 
+    def sweep_boxes(self, lo, hi, move) -> np.ndarray:
+        """vrt_grid_sweep_boxes: per box of corners lo, hi (n, 3) moved by move (n, 3), all float32 in the continuous space of insert's
+        coordinates, a SWEEP_HIT_DTYPE record: the fraction t of the move the box travels before its first contact with a solid voxel,
+        the status bits, and the voxel that stops it with its material and the face that was touched."""
+        q = box_sweeps(lo, hi, move)
+        out = np.zeros(q.shape[0], dtype=SWEEP_HIT_DTYPE)
+        rc = lib.vrt_grid_sweep_boxes(self._h, q.ctypes.data, q.shape[0], out.ctypes.data)
+        if rc != L.VRT_OK:
+            raise L.VrtError(rc, (lib.vrt_last_error(None) or b"").decode())
+        return out
+
     @property
     def device_state(self) -> L.GridState:
         return lib.vrt_grid_device_state(self._h).contents
@@ -318,6 +329,27 @@ def box_queries(lo, hi) -> np.ndarray:
     assert lo.shape == hi.shape
     q = np.zeros(lo.shape[0], dtype=BOX_QUERY_DTYPE)
     q["lo"], q["hi"] = lo, hi
+    return q
+
+
+# vrt_box_sweep / vrt_sweep_hit (include/vrt_hip.h) as numpy records, the status bits and the limits of a sweep
+BOX_SWEEP_DTYPE = np.dtype([("lo", np.float32, 3), ("flags", np.uint32), ("hi", np.float32, 3), ("_reserved", np.uint32),
+                            ("move", np.float32, 3), ("_reserved2", np.uint32)])
+SWEEP_HIT_DTYPE = np.dtype([("t", np.float32), ("status", np.uint32), ("material", np.uint32), ("normal", np.int32),
+                            ("voxel", np.int32, 3), ("_reserved", np.uint32)])
+assert BOX_SWEEP_DTYPE.itemsize == 48 and SWEEP_HIT_DTYPE.itemsize == 32
+SWEEP_HIT, SWEEP_START_SOLID, SWEEP_INVALID = L.SWEEP_HIT, L.SWEEP_START_SOLID, L.SWEEP_INVALID
+SWEEP_MAX_EXTENT, SWEEP_MAX_MOVE, SWEEP_MAX_COORD = L.SWEEP_MAX_EXTENT, L.SWEEP_MAX_MOVE, L.SWEEP_MAX_COORD
+
+
+def box_sweeps(lo, hi, move) -> np.ndarray:
+    """Host records of vrt_box_sweep: corners lo, hi (n, 3) and displacements move (n, 3), float32."""
+    lo = np.asarray(lo, dtype=np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, dtype=np.float32).reshape(-1, 3)
+    move = np.asarray(move, dtype=np.float32).reshape(-1, 3)
+    assert lo.shape == hi.shape == move.shape
+    q = np.zeros(lo.shape[0], dtype=BOX_SWEEP_DTYPE)
+    q["lo"], q["hi"], q["move"] = lo, hi, move
     return q
 
 
@@ -802,6 +834,28 @@ class VoxelRT:
         flat = np.empty(total if total < 1 << 31 else 0, dtype=np.uint16)   # (2^31: the call refuses)
         self._check(self._lib.vrt_read_boxes(self._h, q.ctypes.data, q.shape[0], flat.ctypes.data, total))
         return read_box_views(flat, bases, shapes)
+
+    def sweep_boxes(self, lo, hi, move, device: bool = False):
+        """Per box of corners lo, hi (n, 3) moved by move (n, 3), float32 in the continuous space of insert_voxels' coordinates, a
+        SWEEP_HIT_DTYPE record (vrt_sweep_boxes): the fraction t of the move the box travels in the scene the context holds before its
+        first contact, the status bits (SWEEP_HIT, SWEEP_START_SOLID, SWEEP_INVALID), and the voxel that stops it with its material and
+        the face that was touched.  Sees every edit so far.  device=True: the sweeps are answered in device memory
+        (vrt_sweep_boxes_device, then wait) and the hits stay a torch int32 tensor (n, 8) on the GPU: .cpu().numpy().view(SWEEP_HIT_DTYPE)
+        gives the records."""
+        q = box_sweeps(lo, hi, move)
+        n = q.shape[0]
+        if device:
+            import torch
+            dev = f"cuda:{self._device_index()}"
+            sweeps = torch.from_numpy(q.view(np.int32).reshape(n, 12)).to(dev)
+            hits = torch.empty((n, 8), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(hits.device).synchronize()  # (the sweeps are written on torch's stream; the library's is another)
+            self._check(self._lib.vrt_sweep_boxes_device(self._h, sweeps.data_ptr() if n else None, n, hits.data_ptr() if n else None))
+            self.wait()
+            return hits
+        hits = np.zeros(n, dtype=SWEEP_HIT_DTYPE)
+        self._check(self._lib.vrt_sweep_boxes(self._h, q.ctypes.data, n, hits.ctypes.data))
+        return hits
 
     def region_begin(self) -> None:
         self._check(self._lib.vrt_region_begin(self._h))
