@@ -281,9 +281,67 @@ def main_ties():
         print(f"{name}: {case.width}x{case.width}, oracle(llvmpipe lowering) bit-equal: {same}")
 
 
+# ---- suns that are not overhead (tests/sun_cases.py): every fixture above renders under vrt_sun_init's sun, straight above the grid.  Four
+# frames on the 128^3 b8 terrain of the shadow_b8_* fixtures — a sun near the horizon, a soft one high on the -x -z side, one under the
+# horizon, a soft one inside the grid's box with samples and bounces — and two on the cliff scene seen from below, lit from the side and
+# from straight underneath.  A folder of their own, with ref/'s keys.
+SUN_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_sun")
+SUN_TERRAIN = W.Workload("shadow_b8_sun", 160, 90, 128, 8, 1, 0, True, 0.0)
+SUN_CLIFF = ((32, 12, 32), 4)
+
+
+def sun_cases():
+    """name -> (scene, push constants, brick dimension)"""
+    import dataclasses
+    from tests import sun_cases as S
+    out = {}
+    grid = W.build_grid(SUN_TERRAIN)
+    n = SUN_TERRAIN.voxels // SUN_TERRAIN.brick_dimension
+    terrain = oracle_scene_from_grid(grid, default_materials(256))
+    for name, view, soft, spp, bounce in (("low_x", "V2", False, 1, 0), ("high_nn", "V1", True, 1, 0), ("below", "V0", False, 1, 0),
+                                          ("inside_air", "V1", True, 2, 2)):     # (max_bounce 2: the device value is 3)
+        w = dataclasses.replace(SUN_TERRAIN, spp=spp, max_bounce=bounce)
+        pc = O.push_constants(W.camera_for(w, view).blob(), S.sun_blob(name, (n, n, n), soft=soft, scale=64.0 / n))
+        out[f"terrain_b8_{name}_{'soft' if soft else 'hard'}_{view}" + (f"_spp{spp}_b{bounce + 1}" if bounce else "")] = (terrain, pc, 8)
+    dims, b = SUN_CLIFF
+    for name in ("level", "nadir"):
+        pc = S.push_constants("cliff", S.sun_blob(name, dims), dims, width=160, height=90)
+        out[f"cliff_{'x'.join(map(str, dims))}_b{b}_{name}_hard"] = (S.scene(dims, b)[1], pc, b)
+    return out
+
+
+def main_sun():
+    os.makedirs(SUN_OUT, exist_ok=True)
+    info = GlRef().info()
+    check_implementation(info, OUT)
+    check_implementation(info, SUN_OUT)
+    largest = max(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
+    refs = {}
+    for name, (scene, pc, b) in sun_cases().items():
+        f, u = refs.setdefault(b, ReferenceShader(b)).render(scene, pc)
+        fo, uo, _ = O.render(scene, pc, lowering="llvmpipe")
+        same = bool(np.array_equal(f.view(np.uint32), fo.view(np.uint32)) and np.array_equal(u, uo))
+        path = os.path.join(SUN_OUT, name + ".npz")
+        np.savez_compressed(
+            path,
+            provenance=np.array(f"brick_raytracer.comp + rand.comp of /root/reference, OpenGL dialect edits E1-E8 of "
+                                f"oracle/ref_gl/recipe.py, {info}"),
+            brick_dimension=np.int32(b),
+            grid_state=scene.grid_state, materials=scene.materials.view(np.uint8).reshape(-1),
+            brick_status=scene.brick_status, brick_index=scene.brick_index, brick_occupancy=scene.brick_occupancy,
+            brick_start_index=scene.brick_start_index, material_index=scene.material_index,
+            push_constants=pc,
+            rgba8=u, rgb32f=np.ascontiguousarray(f[:, :, :3]),
+            float_sha256=np.array(hashlib.sha256(f.tobytes()).hexdigest()))
+        assert os.path.getsize(path) <= largest, (name, os.path.getsize(path), largest)
+        print(f"{name}: {f.shape[1]}x{f.shape[0]}, {os.path.getsize(path)} bytes, oracle(llvmpipe lowering) bit-equal: {same}")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "ties":
         main_ties()
+    elif len(sys.argv) > 1 and sys.argv[1] == "sun":
+        main_sun()
     elif len(sys.argv) > 1 and sys.argv[1] == "big":
         main_big(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "full":
@@ -293,3 +351,4 @@ if __name__ == "__main__":
         main_present()
         main_full()
         main_ties()
+        main_sun()

@@ -988,15 +988,26 @@ class VoxelRT:
     def dist_frame(self) -> None:
         self._check(self._lib.vrt_dist_frame(self._h, C.byref(self.camera.d_camera), C.byref(self.sun.device_data)))
 
-    def dist_frames(self, cameras, sun=None) -> None:
+    def dist_frames(self, cameras, sun=None, suns=None, sun_stride: int = 1) -> None:
         """vrt_dist_frames: the frames of `cameras` (96-byte Camera.Device blobs, or a ctypes array of CameraDevice) submitted by ONE
-        call across the ABI, all with this renderer's sun."""
+        call across the ABI, all with this renderer's sun (or `sun`) — or, with `suns` (32-byte Sun.Device blobs, or a ctypes array of
+        SunDevice), frame i with suns[i * sun_stride]."""
         if not isinstance(cameras, C.Array):
             arr = (L.CameraDevice * len(cameras))()
             for i, blob in enumerate(cameras):
                 C.memmove(C.byref(arr[i]), bytes(blob), 96)
             cameras = arr
-        self._check(self._lib.vrt_dist_frames(self._h, cameras, C.byref(sun if sun is not None else self.sun.device_data), len(cameras), 0))
+        if suns is None:
+            self._check(self._lib.vrt_dist_frames(self._h, cameras, C.byref(sun if sun is not None else self.sun.device_data), len(cameras), 0))
+            return
+        assert sun is None and sun_stride >= 1
+        if not isinstance(suns, C.Array):
+            arr = (L.SunDevice * len(suns))()
+            for i, blob in enumerate(suns):
+                C.memmove(C.byref(arr[i]), bytes(blob), 32)
+            suns = arr
+        assert len(cameras) == 0 or len(suns) > (len(cameras) - 1) * sun_stride, "suns[i * sun_stride] must exist for every frame"
+        self._check(self._lib.vrt_dist_frames(self._h, cameras, suns, len(cameras), sun_stride))
 
     def reserve_samples(self, max_samples_per_pixel: int) -> None:
         """vrt_reserve_samples: the persistent kernels' sample buffers made now instead of by the first dispatch that needs them."""
