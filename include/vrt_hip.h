@@ -551,8 +551,8 @@ int vrt_cast_rays_device(vrt_ctx *ctx, const vrt_ray_query *rays, uint64_t n, vr
 /* ---- First-hit buffers of a camera's image ---------------------------------------------------------------------------
  * Depth, normal, material and voxel per pixel: what a host needs to composite raster content against a traced frame (depth), to
  * guide a filter after the present pass (normal, material) and to pick under a cursor or a box selection (voxel) — without making a
- * ray per pixel and reading 48-byte records back.  The pass forms the camera rays in the kernel (vrt_ray_query_b4 / _b8 in their second
- * mode), walks them in the frames' 8x8-pixel waves and writes only the planes asked for.
+ * ray per pixel and reading 48-byte records back.  The pass forms the camera rays in the kernel (vrt_aux_query_b4 / _b8,
+ * kernels of its own), walks them in the frames' 8x8-pixel waves and writes only the planes asked for.
  *
  * CONTRACT.  For pixel (px, py) of a camera->image_width x image_height image, every plane element equals the matching bytes of the
  * vrt_ray_hit that vrt_cast_rays returns for the ray of vrt_camera_pixel_ray(camera, px, py) with flags 0 and max_t = INFINITY.  A miss
@@ -581,7 +581,7 @@ int vrt_trace_aux_device(vrt_ctx *ctx, const vrt_camera_device *camera, const vr
  * "What is at this place?" — the twin of the three writes (vrt_insert_voxels, vrt_remove_voxels, vrt_compact_bricks), in the
  * coordinates they take: x, y, z of vrt_grid_insert, y counted as insert counts it (flipped inside, Grid.zig:135); the voxel of a
  * vrt_ray_hit is in these coordinates too.  Both queries read bindings 2-6 of the scene the context holds and none of the structures
- * derived from them (vrt_ray_query_b4 / _b8 in their modes 2 and 3); each has a CPU twin on a vrt_grid, which reads only the grid's
+ * derived from them (vrt_voxel_query_b4 / _b8 and vrt_box_query_b4 / _b8); each has a CPU twin on a vrt_grid, which reads only the grid's
  * arrays and registers no delta.  A voxel is SOLID when the status bit of its cell is 1 and its occupancy bit is 1.  The status bit
  * decides first: after a removal or a compaction, brick_indices of a cell that is not loaded is stale and may name a brick that
  * belongs to another cell.
@@ -630,7 +630,7 @@ int vrt_query_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n,
 int vrt_grid_query_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, vrt_box_result *results);
 /* ---- Dense box reads: the voxels of a batch of boxes as arrays --------------------------------------------------------
  * The content of a region, for a host that meshes a chunk, builds a collider, saves a region or keeps an undo record: 32 bytes per
- * box go in (vrt_box_query), 2 bytes per voxel come out.  Mode 4 of vrt_ray_query_b4 / _b8; like the volume queries it reads
+ * box go in (vrt_box_query), 2 bytes per voxel come out.  vrt_read_query_b4 / _b8; like the volume queries it reads
  * bindings 2-6 alone, and it has a CPU twin on a vrt_grid, which reads the grid's arrays only and registers no delta.
  *
  * ARGUMENTS AND LAYOUT.  boxes is in host memory in all three forms: the host needs the boxes to size the launch, as for the shape
@@ -662,7 +662,7 @@ int vrt_read_boxes_device(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, 
 int vrt_grid_read_boxes(const vrt_grid *g, const vrt_box_query *boxes, uint64_t n, uint16_t *out, uint64_t out_elements); /* the CPU twin */
 /* ---- Box sweeps: move boxes through the scene to their first contact -----------------------------------------------------
  * "This box wants to move by this much: how far does it get, and what stops it?" — the question of a character controller or a
- * particle, answered for a batch: 48 bytes per sweep go in, 32 come out.  Mode 5 of vrt_ray_query_b4 / _b8; like the volume queries
+ * particle, answered for a batch: 48 bytes per sweep go in, 32 come out.  vrt_sweep_query_b4 / _b8; like the volume queries
  * it reads bindings 2-6 alone, and it has a CPU twin on a vrt_grid, which reads the grid's arrays only and registers no delta.
  *
  * COORDINATES.  The continuous space of vrt_grid_insert's coordinates: voxel (i, j, k) is the unit cube from (i, j, k) to

@@ -175,7 +175,7 @@ def test_a_large_sphere_far_outside_and_extreme_coordinates_are_no_ops():
 
 
 def test_the_edit_kernels_still_hold_their_pinned_set_and_budgets():
-    """The device path is two more modes of the 11 vrt_edit_* kernels: the product library still holds exactly its 60 kernels, and those
+    """The device path is two more modes of the 11 vrt_edit_* kernels: the product library still holds exactly its pinned kernels (70), and those
     11 still use no scratch, at most 64 B of LDS and at most 32 VGPRs (a spill of the new modes is caught here, without a GPU)."""
     R.test_the_product_binary_holds_exactly_the_shipped_kernels()
     R.test_edit_kernels_use_no_scratch_little_lds_and_few_registers()

@@ -4,6 +4,7 @@ The hand-scheduled kernels depend on register budgets the compiler must not sile
 7 waves per SIMD (72 VGPRs) without scratch, the path kernel at 5 (96 VGPRs).  And no kernel may own STATIC LDS: round 2 saw
 the optimiser move a whole per-lane struct (RaySetup) to LDS because of one select over its members — 12 KiB per workgroup and
 +20 % on the headline frame, with identical instruction counts.  This test is the tripwire for that class of regression."""
+import functools
 import os
 import re
 import shutil
@@ -17,8 +18,11 @@ LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 
 
 # Every kernel of the product binary, by symbol: the 28 traversal kernels, 19 others (builders of the derived structures, schedule,
-# present, assembly, self-test), the two ray-query kernels and the 11 kernels of the batched voxel inserts: 60.  A kernel that appears,
+# present, assembly, self-test), the twelve query kernels and the 11 kernels of the batched voxel inserts: 70.  A kernel that appears,
 # goes or returns (a loser of an A/B) fails the test.
+# The queries: a kernel pair (4^3 / 8^3 bricks) per kind — rays, the first-hit buffer pass, voxel look-ups, box counts, dense box reads,
+# box sweeps — so that each kind has a register allocation, a code layout and a kernel argument of its own.
+QUERY_KERNELS = frozenset(f"vrt_{kind}_query_b{b}" for kind in ("ray", "aux", "voxel", "box", "read", "sweep") for b in (4, 8))
 EDIT_KERNELS = frozenset([
     "vrt_edit_begin", "vrt_edit_scan_start", "vrt_edit_state", "vrt_edit_validate", "vrt_edit_count", "vrt_edit_scan_groups",
     "vrt_edit_rank", "vrt_edit_resolve", "vrt_edit_table", "vrt_edit_write", "vrt_edit_finish",
@@ -74,10 +78,7 @@ PRODUCT_KERNELS = frozenset([
     "_ZN3vrt24vrt_build_cell_occupancyEPKjS1_PK15HIP_vector_typeIjLj2EEPS3_mmjmmmmm",
     "_ZN3vrt25vrt_check_materials_plainEPK12vrt_materialPjj",
     "_ZN3vrt27vrt_build_status_halfblocksEPKjPjjjj",
-    # ray queries (vrt_query.hip)
-    "vrt_ray_query_b4",
-    "vrt_ray_query_b8",
-]) | EDIT_KERNELS  # batched voxel inserts (vrt_edit.hip)
+]) | QUERY_KERNELS | EDIT_KERNELS  # the queries (vrt_query.hip) and the batched voxel inserts (vrt_edit.hip)
 
 
 def code_object_notes():
@@ -113,10 +114,11 @@ def test_the_product_binary_holds_exactly_the_shipped_kernels():
     the derived structures, schedule, un-swizzle, the two present kernels, vrt_pool_resolve_kernel, vrt_check_materials_plain).  Round 5:
     + vrt_pool_kernel for 4^3 bricks, the two builders of the byte-per-cell material (vrt_build_cell_material<4>, <8>) and the present pass's
     staged kernel as its own (vrt_denoise_tile_kernel<20>, <0>; vrt_denoise_kernel<NEAR> keeps the taps from global memory).  Round 6:
-    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel).  The ray queries add vrt_ray_query_b4 / _b8,
-    the batched voxel inserts their 11 vrt_edit_* kernels (60 in all); vrt_build_status_blocks, whose words only development variants
-    read, is in the development build alone."""
-    assert len(PRODUCT_KERNELS) == 60
+    + vrt_spin_kernel (vrt_dist_selftest_slots' stand-in for a frame's trace kernel).  The queries add a kernel pair per kind
+    (QUERY_KERNELS: six kinds, twelve kernels, where one pair used to answer all six behind a mode switch), the batched voxel inserts
+    their 11 vrt_edit_* kernels (70 in all); vrt_build_status_blocks, whose words only development variants read, is in the development
+    build alone."""
+    assert len(PRODUCT_KERNELS) == 70
     ks = _kernels()
     assert set(ks) == PRODUCT_KERNELS, (sorted(set(ks) - PRODUCT_KERNELS), sorted(PRODUCT_KERNELS - set(ks)))
     traversal = [n for n in ks if "vrt_trace_kernel" in n or "vrt_path_kernel" in n or "vrt_pool_kernel" in n]
@@ -140,25 +142,30 @@ def test_one_sample_kernels_hold_7_waves_without_scratch():
         assert k["vgpr"] <= 72 and k["scratch"] == 0, (name, k)
 
 
-def _scratch_instructions(symbol_part: str) -> int:
-    """Number of scratch_* instructions in the code of the (one) kernel whose symbol contains `symbol_part`."""
+@functools.lru_cache(maxsize=None)
+def _scratch_by_symbol():
+    """(symbol line, number of scratch_* instructions behind it) for every symbol of the gfx950 code objects: one disassembly for all tests."""
+    out = []
     with tempfile.TemporaryDirectory() as d:
         shutil.copy(LIB, os.path.join(d, "lib.so"))
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=d, check=True, capture_output=True)
-        found, count = 0, 0
         for name in sorted(os.listdir(d)):
             if "gfx950" not in name:
                 continue
             dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--mcpu=gfx950", name], cwd=d, check=True, capture_output=True, text=True).stdout
-            inside = False
             for line in dis.splitlines():
                 if line.endswith(">:"):
-                    inside = symbol_part in line
-                    found += inside
-                elif inside and "scratch_" in line:
-                    count += 1
-        assert found == 1, found
-        return count
+                    out.append([line, 0])
+                elif out and "scratch_" in line:
+                    out[-1][1] += 1
+    return tuple((line, count) for line, count in out)
+
+
+def _scratch_instructions(symbol_part: str) -> int:
+    """Number of scratch_* instructions in the code of the (one) kernel whose symbol contains `symbol_part`."""
+    counts = [count for line, count in _scratch_by_symbol() if symbol_part in line]
+    assert len(counts) == 1, len(counts)
+    return counts[0]
 
 
 def test_several_samples_kernels_hold_7_waves_without_scratch():
@@ -214,10 +221,11 @@ def test_path_kernel_holds_5_waves():
         assert k["vgpr"] <= 96 and k["scratch"] <= 128, (name, k)
 
 
-def test_ray_query_kernels_hold_5_waves_without_scratch():
-    """vrt_ray_query_b4 / _b8 (five waves per SIMD): at most 96 VGPRs, no scratch, no static LDS, and no scratch instruction in their code."""
-    ks = {n: k for n, k in _kernels().items() if n.startswith("vrt_ray_query_")}
-    assert sorted(ks) == ["vrt_ray_query_b4", "vrt_ray_query_b8"], ks
+def test_query_kernels_hold_5_waves_without_scratch():
+    """The twelve query kernels, and no other of that name (five waves per SIMD, the bound the one pair had that they replace): at most
+    96 VGPRs, no scratch, no static LDS, and no scratch instruction in their code."""
+    ks = {n: k for n, k in _kernels().items() if re.fullmatch(r"vrt_\w+_query_b\d+", n)}
+    assert set(ks) == QUERY_KERNELS and len(QUERY_KERNELS) == 12, (sorted(set(ks) - QUERY_KERNELS), sorted(QUERY_KERNELS - set(ks)))
     for name, k in ks.items():
         assert k["vgpr"] <= 96 and k["scratch"] == 0 and k["lds"] == 0, (name, k)
         assert _scratch_instructions(name) == 0, name

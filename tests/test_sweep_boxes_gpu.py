@@ -1,4 +1,4 @@
-"""The box sweeps on the GPU (vrt_sweep_boxes, vrt_sweep_boxes_device; mode 5 of vrt_ray_query_b4 / _b8): every field of every record
+"""The box sweeps on the GPU (vrt_sweep_boxes, vrt_sweep_boxes_device; vrt_sweep_query_b4 / _b8): every field of every record
 bit for bit the CPU twin's on a host grid that holds the same scene (the twin is held to the numpy model in
 tests/test_brick_grid_sweep_boxes.py), through both entry points, at the batch sizes where a wave or a workgroup is partly filled, with
 the records beyond the batch untouched; one batch larger than a piece of the host form; seen behind host-staged and device edits without

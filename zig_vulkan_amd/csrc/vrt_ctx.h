@@ -5,7 +5,7 @@
 //   vrt_frame.hip    one frame: kernel choice, the bounce kernel's trials (vrt::BounceTrials), launch, timing
 //   vrt_dist.hip     the multi-GPU frame pipeline (RCCL through dlopen)
 //   vrt_post.hip     the present / denoise pass
-//   vrt_query.hip    batched ray queries, the first-hit buffer pass and the volume queries — voxel look-ups, box counts (their kernels and host side)
+//   vrt_query.hip    the six kinds of query — rays, the first-hit buffer pass, voxel look-ups, box counts, dense box reads, box sweeps — a kernel pair and an argument struct each, and their host side
 //   vrt_edit.hip     batched voxel inserts and removals, shape edits, brick compaction (their kernels and host side)
 // Replaces src/modules/voxel_rt/ComputePipeline.zig (init / dispatch / deinit) and the Pipeline.transfer* family
 // (Pipeline.zig:560-652) with its StagingRamp (render/StagingRamp.zig) for this one path.
@@ -232,10 +232,9 @@ struct vrt_ctx {
     vrt::KernelFn kernel_grid_exit = nullptr, product_grid_exit = nullptr, kernel_grid_exit_path = nullptr, product_grid_exit_path = nullptr;
     vrt::TileOwnership own{};        // weighted tile ownership (period 0: tile t belongs to rank t % shard_count)
     bool grid_uploaded = false;      // binding 1 has been uploaded (ray queries need the grid's geometry)
-    // ray queries (vrt_query.hip): the host path's device buffers
-    vrt_ray_query *d_query_rays = nullptr;
-    vrt_ray_hit *d_query_hits = nullptr;
-    uint64_t query_capacity = 0;     // rays the two buffers hold
+    // the queries' host forms (vrt_query.hip): the device buffers a piece of a batch goes in and comes out through, whatever its kind
+    uint8_t *d_query_in = nullptr, *d_query_out = nullptr;
+    uint64_t query_in_bytes = 0, query_out_bytes = 0; // bytes each holds
     // the first-hit buffer pass (vrt_trace_aux): the host path's device buffer, the wanted planes one after another
     uint8_t *d_aux_planes = nullptr;
     uint64_t aux_capacity = 0;       // bytes it holds

@@ -1,5 +1,5 @@
-// vrt_sweep.h — the part of the box sweeps that the CPU twin (host_brick_grid.cpp) and the device path (vrt_query.hip, mode 5 of
-// vrt_ray_query_b4 / _b8) share: the screening of one vrt_box_sweep, the layers a box covers, the times of the plane crossings, their
+// vrt_sweep.h — the part of the box sweeps that the CPU twin (host_brick_grid.cpp) and the device path (vrt_query.hip,
+// vrt_sweep_query_b4 / _b8) share: the screening of one vrt_box_sweep, the layers a box covers, the times of the plane crossings, their
 // order, and the walk over them (include/vrt_hip.h, the box-sweep block, is the definition).  Only the test of a slab of voxels differs
 // between the two: each side hands sweep_box its own.  Both compile this header with -ffp-contract=off and without fast-math, and the
 // device's float division is the correctly rounded one: a time is one float32 subtraction and one float32 division on either side.
