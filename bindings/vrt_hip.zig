@@ -342,6 +342,11 @@ pub const SWEEP_INVALID: u32 = 4;
 pub const SWEEP_MAX_EXTENT: f32 = 32.0;
 pub const SWEEP_MAX_MOVE: f32 = 256.0;
 pub const SWEEP_MAX_COORD: f32 = 4194304.0;
+/// The material filter of the scene queries (vrt_set_query_filter), 32 bytes: bit (m & 31) of see[m >> 5] = 1 where material
+/// entry m is seen.  While one is set every query answers as on the scene after the removal of every hidden voxel.
+pub const MaterialFilter = extern struct {
+    see: [8]u32 = .{0xFFFFFFFF} ** 8,
+};
 /// One shape of vrt_fill_shapes / vrt_clear_shapes, 32 bytes, in the coordinates vrt_grid_insert takes; clipped to the grid.
 /// Box: lo / hi are the inclusive corners.  Sphere: lo is the centre, hi[0] the radius (0..SHAPE_MAX_RADIUS), hi[1] = hi[2] = 0.
 pub const SHAPE_BOX: u32 = 0;
@@ -439,6 +444,10 @@ pub extern fn vrt_grid_read_boxes(g: ?*const Grid, boxes: [*c]const BoxQuery, n:
 pub extern fn vrt_sweep_boxes(ctx: ?*Ctx, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
 pub extern fn vrt_sweep_boxes_device(ctx: ?*Ctx, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
 pub extern fn vrt_grid_sweep_boxes(g: ?*const Grid, sweeps: [*c]const BoxSweep, n: u64, hits: [*c]SweepHit) c_int;
+pub extern fn vrt_set_query_filter(ctx: ?*Ctx, f: [*c]const MaterialFilter) c_int;
+pub extern fn vrt_get_query_filter(ctx: ?*const Ctx, out: [*c]MaterialFilter, is_set: [*c]u32) c_int;
+pub extern fn vrt_grid_set_query_filter(g: ?*Grid, f: [*c]const MaterialFilter) c_int;
+pub extern fn vrt_grid_get_query_filter(g: ?*const Grid, out: [*c]MaterialFilter, is_set: [*c]u32) c_int;
 pub extern fn vrt_insert_voxels(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials: [*c]const u8, n: u64) c_int;
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;

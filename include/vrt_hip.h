@@ -723,6 +723,37 @@ typedef struct vrt_sweep_hit {      /* 32 bytes: two dwordx4 */
 int vrt_sweep_boxes(vrt_ctx *ctx, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits);        /* host memory; blocks */
 int vrt_sweep_boxes_device(vrt_ctx *ctx, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits); /* device memory, 16-byte aligned; asynchronous (vrt_wait) */
 int vrt_grid_sweep_boxes(const vrt_grid *g, const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits); /* the CPU twin */
+/* ---- Material filters: scene queries that see through chosen voxels --------------------------------------------------------
+ * Scenes keep water, glass or fog as solid voxels, and game logic wants to ask "where is the sea bed", "is this volume free of
+ * rock", "how far does the diver get".  A filter names the material entries (the value vrt_get_voxels gives, 0..255) the queries
+ * SEE; every other solid voxel is hidden from them.
+ *
+ * DEFINITION.  While a filter is set, every scene query — vrt_cast_rays, vrt_trace_aux, vrt_get_voxels, vrt_query_boxes,
+ * vrt_read_boxes, vrt_sweep_boxes, their _device forms and, for a grid's filter, the four CPU twins — answers exactly as the same
+ * query would, with no filter, on the scene after vrt_remove_voxels of every solid voxel whose material entry is hidden.  Byte for
+ * byte: a ray walks on through a hidden voxel as it walks through one its ray ignores (comp:427) and max_t filters the first SEEN
+ * hit; a hidden voxel reads VRT_VOXEL_EMPTY; counts and tight bounds are taken over the seen voxels (only hidden ones: the all-zero
+ * record); for a sweep "solid" means seen in START_SOLID, in the slab test and in the choice of the contact voxel.  The first-hit
+ * planes equal vrt_cast_rays' bytes under any filter.  Everything that is not a query is untouched: frames, edits (paint's `only`
+ * included), derived structures, vrt_read_buffer.  An undo record, vrt_write_boxes(boxes, vrt_read_boxes(boxes)), must therefore be
+ * READ with no filter set: read under a filter it would empty the hidden voxels when written back.
+ *
+ * STATE.  Host state of the context (or grid) alone: the setter touches no device and is legal on any context; the queries keep their
+ * own VRT_E_STATE rules.  The filter is copied into the kernel arguments of each launch, so an asynchronous _device query issued
+ * before vrt_set_query_filter runs under the filter that was set when it was issued.  NULL: everything is seen, the state after
+ * vrt_create / vrt_grid_create, and a query then runs the code it ran before filters existed.  An all-zero filter is legal: the
+ * scene looks empty.  vrt_get_query_filter: *out = the filter (all bits set while none is set), *is_set (may be NULL) = 1 while one
+ * is set.  VRT_E_INVALID_ARG for a NULL ctx, grid or out.
+ *
+ * SCENES UPLOADED BY HAND.  brick_start_indices need not be multiples of 16: the filtered counts and sweeps then read a byte per
+ * voxel instead of 16 at a time, with the same answers.  A solid voxel whose material entry lies at or beyond the end of binding 6
+ * (no scene an insert or an edit makes) has no entry a filter could hide it by: look-ups and reads give VRT_VOXEL_EMPTY for it as
+ * they do without a filter, and counts and sweeps keep it, as they do without one. */
+typedef struct vrt_material_filter { uint32_t see[8]; } vrt_material_filter; /* bit (m & 31) of see[m >> 5] = 1: material entry m is seen */
+int vrt_set_query_filter(vrt_ctx *ctx, const vrt_material_filter *f);  /* NULL: everything is seen (the state after vrt_create) */
+int vrt_get_query_filter(const vrt_ctx *ctx, vrt_material_filter *out, uint32_t *is_set);
+int vrt_grid_set_query_filter(vrt_grid *g, const vrt_material_filter *f); /* for the four CPU twins */
+int vrt_grid_get_query_filter(const vrt_grid *g, vrt_material_filter *out, uint32_t *is_set);
 /* ---- Batched voxel inserts into the uploaded scene --------------------------------------------------------------
  * BrickGrid.insert (Grid.zig:129-194) for n voxels at once, on the GPU, on the scene buffers the context holds: after
  * vrt_insert_voxels(ctx, xyz, m, n) on a context whose bindings 2-6 equal a vrt_grid's arrays, bindings 2-6 equal that grid's

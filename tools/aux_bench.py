@@ -9,7 +9,7 @@ Timing and warm-up as tools/ray_query_bench.py: device events around K launches 
 context's stream), repeated R times per subject, the subjects taking turns; reported are the median, the minimum and the maximum of the
 R per-launch means.  Before timing, the planes of the full-size pass are compared with the hits of the yardstick, byte for byte.
 
-    python tools/aux_bench.py [--steps K] [--warmup W] [--reps R] [--view V1]
+    python tools/aux_bench.py [--steps K] [--warmup W] [--reps R] [--view V1] [--hide M[,M...]]
 Prints one JSON line per subject and a last one with the ratios."""
 import argparse
 import ctypes as C
@@ -30,7 +30,9 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--view", default="V1")
+    ap.add_argument("--hide", default="", help="M[,M...]: the material entries a query filter hides from every batch (vrt_set_query_filter); none by default")
     args = ap.parse_args()
+    hide = [int(m) for m in args.hide.split(",") if m.strip()]
 
     import torch
     from zig_vulkan_amd import _lib as L
@@ -41,6 +43,8 @@ def main() -> int:
     grid = W.build_grid(w)
     rt = W.make_renderer(w, grid)
     W.set_view(rt, args.view)
+    if hide:
+        rt.set_query_filter(hide=hide)
     cam = rt.camera.d_camera
     width, height = int(cam.image_width), int(cam.image_height)
     n = width * height
@@ -90,7 +94,7 @@ def main() -> int:
         print(json.dumps({"subject": name, "pixels": n, "ms_median": round(med[name], 4), "ms_min": round(min(times), 4), "ms_max": round(max(times), 4),
                           "gpixels_per_s": round(n / (med[name] * 1e-3) / 1e9, 2), "bytes_per_pixel": bytes_per_pixel[name],
                           "hit_fraction": round(float(hit.mean()), 4), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
-                          "view": args.view, "parity_with_cast_rays": "byte-equal"}), flush=True)
+                          "view": args.view, "parity_with_cast_rays": "byte-equal", **({"hide": hide} if hide else {})}), flush=True)
     print(json.dumps({"aux_all_planes_over_cast_rays": round(med["aux_all_planes"] / med["cast_rays_pixels"], 3),
                       "aux_depth_only_over_cast_rays": round(med["aux_depth_only"] / med["cast_rays_pixels"], 3)}), flush=True)
     rt.deinit()

@@ -22,7 +22,7 @@ STRUCTS = {"vrt_ctx": "Ctx", "vrt_grid": "Grid", "vrt_vox": "Vox", "vrt_benchmar
            "vrt_sun_config": "SunConfig", "vrt_denoise_config": "DenoiseConfig", "vrt_vox_xyzi": "VoxXyzi", "vrt_vox_rgba": "VoxRgba", "vrt_dist_options": "DistOptions",
            "vrt_ray_query": "RayQuery", "vrt_ray_hit": "RayHit", "vrt_aux_planes": "AuxPlanes",
            "vrt_box_query": "BoxQuery", "vrt_box_result": "BoxResult", "vrt_shape": "Shape",
-           "vrt_box_sweep": "BoxSweep", "vrt_sweep_hit": "SweepHit"}
+           "vrt_box_sweep": "BoxSweep", "vrt_sweep_hit": "SweepHit", "vrt_material_filter": "MaterialFilter"}
 OPAQUE = {"Ctx", "Grid", "Vox", "Benchmark"}
 SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64", "uint8_t": "u8", "uint16_t": "u16", "float": "f32",
            "double": "f64", "void": "void", "vrt_buffer_id": "BufferId", "vrt_derived_id": "DerivedId"}

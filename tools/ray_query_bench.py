@@ -7,7 +7,7 @@ the synthetic terrain, view V1.  Three batches, rays and hits in device memory:
 Times are device events around K batches after W warm-up batches (vrt_region_begin / _end on the context's stream).  Beside each number: the
 algorithmic I/O bound, 80 bytes per ray (a 32-byte query read, a 48-byte hit written) at the HBM peak of 8 TB/s.
 
-    python tools/ray_query_bench.py [--steps K] [--warmup W] [--view V1]
+    python tools/ray_query_bench.py [--steps K] [--warmup W] [--view V1] [--hide M[,M...]]
 Prints one JSON line per batch."""
 import argparse
 import json
@@ -45,7 +45,9 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--view", default="V1")
+    ap.add_argument("--hide", default="", help="M[,M...]: the material entries a query filter hides from every batch (vrt_set_query_filter); none by default")
     args = ap.parse_args()
+    hide = [int(m) for m in args.hide.split(",") if m.strip()]
 
     import torch
     from zig_vulkan_amd import _lib as L
@@ -56,6 +58,8 @@ def main() -> int:
     grid = W.build_grid(w)
     rt = W.make_renderer(w, grid)
     W.set_view(rt, args.view)
+    if hide:
+        rt.set_query_filter(hide=hide)
     o, d = camera_rays(rt.camera)
     rng = np.random.default_rng(2024)
     perm = rng.permutation(len(o))
@@ -89,7 +93,7 @@ def main() -> int:
         print(json.dumps({"batch": name, "rays": n, "ms": round(ms, 4), "grays_per_s": round(n / (ms * 1e-3) / 1e9, 2),
                           "hit_fraction": round(float(hits.mean()), 4), "io_bound_ms": round(bound_ms, 4),
                           "io_bound_grays_per_s": round(HBM_PEAK / BYTES_PER_RAY / 1e9, 1), "of_io_bound": round(bound_ms / ms, 3),
-                          "steps": args.steps, "warmup": args.warmup, "view": args.view}), flush=True)
+                          "steps": args.steps, "warmup": args.warmup, "view": args.view, **({"hide": hide} if hide else {})}), flush=True)
     rt.deinit()
     return 0
 

@@ -12,7 +12,7 @@ for a read 2 bytes per element written, 36 bytes per box of tables, and of the s
 the occupancy record of each loaded one and a byte per solid voxel read; for the baseline 14 bytes per voxel (12 read, 2 written).
 Before timing every batch is compared with the CPU twin on the host grid, and the two sides with each other.
 
-    python tools/read_boxes_bench.py [--steps K] [--warmup W] [--reps R] [--baseline-lib PATH]
+    python tools/read_boxes_bench.py [--steps K] [--warmup W] [--reps R] [--baseline-lib PATH] [--hide M[,M...]]
 Prints one JSON line per batch."""
 import argparse
 import ctypes as C
@@ -71,7 +71,11 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--baseline-lib", default=None, help="another build of libvrt_hip.so for the baseline (the parent commit's)")
+    ap.add_argument("--hide", default="", help="M[,M...]: the material entries a query filter hides from every batch (vrt_set_query_filter); none by default")
     args = ap.parse_args()
+    hide = [int(m) for m in args.hide.split(",") if m.strip()]
+    if hide and args.baseline_lib:
+        ap.error("--hide sets the filter on one context: the baseline must be this build's")
 
     import torch
     from volume_query_bench import surface_voxels
@@ -101,6 +105,9 @@ def main() -> int:
              ("b_4096_boxes_34_cubed_in_the_sky", lo_b, lo_b + SIDE - 1),
              ("c_one_box_512x64x512", np.array([[0, y0, 0]]), np.array([[shape[0] - 1, y0 + 63, shape[2] - 1]]))]
 
+    if hide:   # the same batches, answered under the filter by the reads, by the look-ups beside them and by the twin
+        rt.set_query_filter(hide=hide)
+        grid.set_query_filter(hide=hide)
     for name, lo, hi in cases:
         lo, hi = lo.astype(np.int32), hi.astype(np.int32)
         q = box_queries(lo, hi)
@@ -154,7 +161,8 @@ def main() -> int:
                           "baseline_ms_median": round(base_ms, 5), "baseline_ms_min": round(min(t_base), 5), "baseline_ms_max": round(max(t_base), 5),
                           "baseline_io_bytes": io_base, "baseline_io_bound_ms": round(io_base / HBM_PEAK * 1e3, 6),
                           "baseline_of_io_bound": round(io_base / HBM_PEAK * 1e3 / base_ms, 4), "baseline_over_read": round(base_ms / ms, 3),
-                          "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "equal_to_cpu_twin": True, "equal_to_baseline": True}), flush=True)
+                          "steps": args.steps, "warmup": args.warmup, "reps": args.reps, "equal_to_cpu_twin": True, "equal_to_baseline": True,
+                          **({"hide": hide} if hide else {})}), flush=True)
         del out, xyz, base_out
     if base_rt is not rt:
         base_rt.deinit()

@@ -11,7 +11,7 @@ offered for the same question before it had sweeps: vrt_read_boxes of the swept 
 call) plus the CPU twin of the sweep on the host grid, which stands in for a host that sweeps in what it read.
 Before timing every batch is compared with the CPU twin on the host grid.
 
-    python tools/sweep_bench.py [--steps K] [--warmup W] [--reps R]
+    python tools/sweep_bench.py [--steps K] [--warmup W] [--reps R] [--hide M[,M...]]
 Prints one JSON line per batch."""
 import argparse
 import json
@@ -36,7 +36,9 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--hide", default="", help="M[,M...]: the material entries a query filter hides from every batch (vrt_set_query_filter); none by default")
     args = ap.parse_args()
+    hide = [int(m) for m in args.hide.split(",") if m.strip()]
 
     import torch
     from zig_vulkan_amd import BOX_SWEEP_DTYPE, SWEEP_HIT, SWEEP_HIT_DTYPE, SWEEP_START_SOLID, box_sweeps
@@ -90,6 +92,9 @@ def main() -> int:
         return (t1 - t0) * 1e3, (t2 - t1) * 1e3
 
     batches = [("a_characters_6x14x6", characters(1 << 16), True), ("b_particles_quarter", particles(1 << 20), False), ("c_limits_32_cubed_move_256", limits(1 << 12), False)]
+    if hide:   # the same batches, answered under the filter by the device and by the twin it is checked against
+        rt.set_query_filter(hide=hide)
+        grid.set_query_filter(hide=hide)
     for name, q, with_parent_route in batches:
         assert q.dtype == BOX_SWEEP_DTYPE
         n = len(q)
@@ -117,7 +122,7 @@ def main() -> int:
                "msweeps_per_s": round(n / (ms * 1e-3) / 1e6, 3), "hit_fraction": round(float(np.mean((want["status"] & SWEEP_HIT) != 0)), 4),
                "start_solid_fraction": round(float(np.mean((want["status"] & SWEEP_START_SOLID) != 0)), 4), "io_bytes": n * SWEEP_BYTES,
                "io_bound_ms": round(bound_ms, 6), "of_io_bound": round(bound_ms / ms, 5), "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
-               "equal_to_cpu_twin": True}
+               "equal_to_cpu_twin": True, **({"hide": hide} if hide else {})}
         if with_parent_route:
             read_ms, cpu_ms = hull_read_plus_cpu_sweep(q)
             row.update({"read_hulls_host_ms": round(read_ms, 3), "cpu_sweep_ms": round(cpu_ms, 3), "read_plus_cpu_over_sweep": round((read_ms + cpu_ms) / ms, 1)})

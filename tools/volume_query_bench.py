@@ -12,7 +12,7 @@ Beside each number: the algorithmic I/O bound at the HBM peak of 8 TB/s — 14 b
 plus, for (d) and (e), one pass over the occupancy words of the loaded cells the boxes cover (8 bytes per word, counted on the host).
 Before timing every batch is compared with the CPU twin on the host grid.
 
-    python tools/volume_query_bench.py [--steps K] [--warmup W] [--reps R]
+    python tools/volume_query_bench.py [--steps K] [--warmup W] [--reps R] [--hide M[,M...]]
 Prints one JSON line per batch."""
 import argparse
 import json
@@ -63,7 +63,9 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--hide", default="", help="M[,M...]: the material entries a query filter hides from every batch (vrt_set_query_filter); none by default")
     args = ap.parse_args()
+    hide = [int(m) for m in args.hide.split(",") if m.strip()]
 
     import torch
     from zig_vulkan_amd import BOX_RESULT_DTYPE, VOXEL_EMPTY, box_queries
@@ -88,6 +90,9 @@ def main() -> int:
 
     small, large = boxes(1 << 18, (2, 4, 2)), boxes(1 << 12, (64, 64, 64))
     whole = (np.zeros((1, 3), np.int32), (shape - 1).astype(np.int32)[None, :])
+    if hide:   # the same batches, answered under the filter by the device and by the twin it is checked against
+        rt.set_query_filter(hide=hide)
+        grid.set_query_filter(hide=hide)
 
     def voxel_batch(name, xyz):
         dx = torch.from_numpy(xyz.view(np.int32)).cuda()
@@ -113,6 +118,29 @@ def main() -> int:
         box_batch("e_box_whole_grid", *whole, loaded_words(grid, *whole) * 8),
     ]
     torch.cuda.synchronize()
+
+    def host_filter_route(lo, hi):
+        """What a host did for filtered counts before the queries took a filter, on the wall clock: vrt_get_voxels of every voxel of the
+        boxes (host form, no filter), the filter and the sums on the host.  Beside it the filtered vrt_query_boxes, host form too.
+        (milliseconds for the look-ups and the host's part, milliseconds for the filtered query; the counts are compared)"""
+        import time
+        side = hi[0] - lo[0] + 1
+        off = np.stack(np.meshgrid(*(np.arange(s) for s in side), indexing="ij"), axis=-1).reshape(-1, 3)
+        xyz = np.ascontiguousarray((lo[:, None, :] + off[None, :, :]).reshape(-1, 3), dtype=np.uint32)
+        rt.query_boxes(lo, hi)                     # (warm: the context's device buffers are grown)
+        t0 = time.perf_counter()
+        filtered = rt.query_boxes(lo, hi)
+        t1 = time.perf_counter()
+        rt.set_query_filter()
+        rt.get_voxels(xyz[:1 << 20])               # (warm)
+        t2 = time.perf_counter()
+        m = rt.get_voxels(xyz)
+        count = ((m != VOXEL_EMPTY) & ~np.isin(m, hide)).reshape(len(lo), -1).sum(axis=1)
+        t3 = time.perf_counter()
+        rt.set_query_filter(hide=hide)
+        assert np.array_equal(count, filtered["count"].astype(np.int64))
+        return (t3 - t2) * 1e3, (t1 - t0) * 1e3
+
     for name, n, launch, check, io_bytes, _keep in batches:
         launch()
         rt.wait()
@@ -129,10 +157,15 @@ def main() -> int:
             times.append(rt.region_end() / args.steps)
         ms = float(np.median(times))
         bound_ms = io_bytes / HBM_PEAK * 1e3
-        print(json.dumps({"batch": name, "items": n, "ms_median": round(ms, 5), "ms_min": round(min(times), 5), "ms_max": round(max(times), 5),
-                          "gitems_per_s": round(n / (ms * 1e-3) / 1e9, 4), "nonempty_fraction": round(nonempty, 4), "io_bytes": io_bytes,
-                          "io_bound_ms": round(bound_ms, 6), "of_io_bound": round(bound_ms / ms, 4), "steps": args.steps, "warmup": args.warmup,
-                          "reps": args.reps, "equal_to_cpu_twin": True}), flush=True)
+        row = {"batch": name, "items": n, "ms_median": round(ms, 5), "ms_min": round(min(times), 5), "ms_max": round(max(times), 5),
+               "gitems_per_s": round(n / (ms * 1e-3) / 1e9, 4), "nonempty_fraction": round(nonempty, 4), "io_bytes": io_bytes,
+               "io_bound_ms": round(bound_ms, 6), "of_io_bound": round(bound_ms / ms, 4), "steps": args.steps, "warmup": args.warmup,
+               "reps": args.reps, "equal_to_cpu_twin": True, **({"hide": hide} if hide else {})}
+        if hide and name == "c_boxes_2x4x2":
+            route_ms, host_form_ms = host_filter_route(*small)
+            row.update({"lookups_plus_host_filter_wall_ms": round(route_ms, 3), "filtered_query_host_form_wall_ms": round(host_form_ms, 3),
+                        "host_route_over_filtered_query": round(route_ms / host_form_ms, 1)})
+        print(json.dumps(row), flush=True)
     rt.deinit()
     return 0
 

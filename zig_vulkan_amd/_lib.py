@@ -192,6 +192,10 @@ class SweepHit(C.Structure):  # vrt_sweep_hit (32 bytes)
                 ("voxel", C.c_int32 * 3), ("_reserved", C.c_uint32)]
 
 
+class MaterialFilter(C.Structure):  # vrt_material_filter (32 bytes): bit (m & 31) of see[m >> 5] = 1: material entry m is seen
+    _fields_ = [("see", C.c_uint32 * 8)]
+
+
 SHAPE_BOX, SHAPE_SPHERE = 0, 1  # VRT_SHAPE_BOX, VRT_SHAPE_SPHERE
 SHAPE_MAX_RADIUS = 16384        # VRT_SHAPE_MAX_RADIUS
 SHAPES_MAX = 4096               # VRT_SHAPES_MAX
@@ -209,7 +213,7 @@ SWEEP_MAX_COORD = 4194304.0   # VRT_SWEEP_MAX_COORD
 assert C.sizeof(GridState) == 64 and C.sizeof(Material) == 20
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(AuxPlanes) == 32
 assert C.sizeof(BoxQuery) == 32 and C.sizeof(BoxResult) == 32 and C.sizeof(Shape) == 32
-assert C.sizeof(BoxSweep) == 48 and C.sizeof(SweepHit) == 32
+assert C.sizeof(BoxSweep) == 48 and C.sizeof(SweepHit) == 32 and C.sizeof(MaterialFilter) == 32
 assert C.sizeof(CameraDevice) == 96 and C.sizeof(SunDevice) == 32
 
 _P = C.POINTER
@@ -304,6 +308,10 @@ SIGNATURES = {
     "vrt_sweep_boxes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_sweep_boxes_device": (C.c_int, [_ctx, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vrt_grid_sweep_boxes": (C.c_int, [_grid, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vrt_set_query_filter": (C.c_int, [_ctx, _P(MaterialFilter)]),
+    "vrt_get_query_filter": (C.c_int, [_ctx, _P(MaterialFilter), _P(C.c_uint32)]),
+    "vrt_grid_set_query_filter": (C.c_int, [_grid, _P(MaterialFilter)]),
+    "vrt_grid_get_query_filter": (C.c_int, [_grid, _P(MaterialFilter), _P(C.c_uint32)]),
     "vrt_insert_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_insert_voxels_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint64]),
     "vrt_remove_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

@@ -251,7 +251,8 @@ void BrickGrid::getVoxels(const uint32_t *xyz, uint64_t n, uint16_t *out) const 
         const uint32_t brick_index = brick_indices[grid_index];
         const uint32_t nth_bit = (x % b) + b * ((z % b) + b * (flipped_y % b)); // voxelAt
         if (!((brick_occupancy[(size_t)brick_index * brick_bytes_ + nth_bit / 8] >> (nth_bit % 8)) & 1u)) continue;
-        out[i] = material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu) + nth_bit]; // comp:422-425
+        const uint8_t material = material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu) + nth_bit]; // comp:422-425
+        if (sees(material)) out[i] = material; // a voxel the queries' filter hides reads as empty
     }
 }
 
@@ -283,13 +284,14 @@ void BrickGrid::queryBoxes(const vrt_box_query *boxes, uint64_t n, vrt_box_resul
                 for (int64_t cx = lo[0] / b; cx <= hi[0] / b; cx++) {
                     const size_t grid_index = (size_t)cx + (size_t)d.dim_x * ((size_t)cz + (size_t)d.dim_z * (size_t)cy); // gridAt
                     if (!((brick_statuses[grid_index / 32] >> (grid_index % 32)) & 1u)) continue;
-                    const uint8_t *occ = &brick_occupancy[(size_t)brick_indices[grid_index] * brick_bytes_];
+                    const uint32_t brick_index = brick_indices[grid_index];
+                    const uint8_t *occ = &brick_occupancy[(size_t)brick_index * brick_bytes_];
                     const int64_t x0 = std::max(lo[0], cx * b), x1 = std::min(hi[0], cx * b + b - 1);
                     const uint32_t row_mask = ((1u << (x1 - x0 + 1)) - 1u) << (x0 - cx * b);
                     for (int64_t y = std::max(lo[1], cy * b); y <= std::min(hi[1], cy * b + b - 1); y++)
                         for (int64_t z = std::max(lo[2], cz * b); z <= std::min(hi[2], cz * b + b - 1); z++) {
                             const uint32_t row_bit = (uint32_t)(b * ((z - cz * b) + b * (y - cy * b))); // voxelAt of the row's x = 0
-                            const uint32_t row = (occ[row_bit / 8] >> (row_bit % 8)) & row_mask;
+                            const uint32_t row = seenRow(brick_index, row_bit, (occ[row_bit / 8] >> (row_bit % 8)) & row_mask);
                             if (!row) continue;
                             count += (uint64_t)__builtin_popcount(row);
                             mn[0] = std::min<int64_t>(mn[0], cx * b + __builtin_ctz(row));
@@ -350,7 +352,7 @@ int BrickGrid::readBoxes(const vrt_box_query *boxes, uint64_t n, uint16_t *out, 
                     for (int64_t fy = std::max(lo[1], cy * b); fy <= std::min(hi[1], cy * b + b - 1); fy++)
                         for (int64_t z = std::max(lo[2], cz * b); z <= std::min(hi[2], cz * b + b - 1); z++) {
                             const uint32_t row_bit = (uint32_t)(b * ((z - cz * b) + b * (fy - cy * b))); // voxelAt of the row's x = 0
-                            const uint32_t row = (occ[row_bit / 8] >> (row_bit % 8)) & row_mask;
+                            const uint32_t row = seenRow(brick_index, row_bit, (occ[row_bit / 8] >> (row_bit % 8)) & row_mask);
                             if (!row) continue;
                             const int64_t y = dim[1] - 1 - fy;
                             uint16_t *dst = box + (uint64_t)(x0 - q.lo[0]) + s.side[0] * ((uint64_t)(z - q.lo[2]) + s.side[2] * (uint64_t)(y - q.lo[1])); // voxel x0
@@ -375,7 +377,8 @@ int BrickGrid::sweepBoxes(const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit
     const vrt_grid_state &d = device_state_;
     const int64_t b = brick_dimension_;
     const int64_t dim[3] = {d.voxel_dim_x, d.voxel_dim_y, d.voxel_dim_z};
-    // the slab clipped to the grid, its voxels in the order y, z, x of the caller's count: the first solid one is the contact
+    // the slab clipped to the grid, its voxels in the order y, z, x of the caller's count: the first solid one (under the queries'
+    // filter: the first seen one) is the contact
     const auto solid = [&](const SweepSlabRange &s, SweepContact &c) {
         const int32_t lo[3] = {s.x0, s.y0, s.z0}, hi[3] = {s.x1, s.y1, s.z1};
         int64_t l[3], h[3];
@@ -402,7 +405,7 @@ int BrickGrid::sweepBoxes(const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit
                     const int64_t x0 = std::max(l[0], cx * b), x1 = std::min(h[0], cx * b + b - 1);
                     const uint32_t row_mask = ((1u << (x1 - x0 + 1)) - 1u) << (x0 - cx * b);
                     const uint32_t row_bit = (uint32_t)(b * (z % b + b * (fy % b))); // voxelAt of the row's x = 0
-                    const uint32_t row = (brick_occupancy[(size_t)brick_index * brick_bytes_ + row_bit / 8] >> (row_bit % 8)) & row_mask;
+                    const uint32_t row = seenRow(brick_index, row_bit, (brick_occupancy[(size_t)brick_index * brick_bytes_ + row_bit / 8] >> (row_bit % 8)) & row_mask);
                     if (!row) continue;
                     const uint32_t x = (uint32_t)__builtin_ctz(row);
                     c.x = (int32_t)(cx * b + x), c.y = (int32_t)y, c.z = (int32_t)z;

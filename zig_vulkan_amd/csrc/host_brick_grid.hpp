@@ -89,6 +89,17 @@ public:
     // per sweep: how far the box gets along its move and the voxel that stops it (include/vrt_hip.h, the box-sweep block; the walk is
     // vrt_sweep.h's).  A batch that holds a non-zero flags / _reserved / _reserved2 is refused and writes nothing; *why (may be null) names the item.
     int sweepBoxes(const vrt_box_sweep *sweeps, uint64_t n, vrt_sweep_hit *hits, std::string *why = nullptr) const;
+    // The material filter of the four queries above (include/vrt_hip.h, the material-filter block): while one is set they answer as on
+    // the grid after the removal of every solid voxel whose material entry it hides.  nullptr: none, everything is seen.  No array and
+    // no delta is touched.
+    void setQueryFilter(const vrt_material_filter *f) {
+        query_filter_set_ = f != nullptr;
+        if (f) query_filter_ = *f;
+    }
+    bool queryFilter(vrt_material_filter *out) const {
+        for (int k = 0; k < 8; k++) out->see[k] = query_filter_set_ ? query_filter_.see[k] : ~0u;
+        return query_filter_set_;
+    }
 
     // Shape edits (the reference has none: include/vrt_hip.h defines them).  The arrays and the deltas that insertUnlocked /
     // removeManyUnlocked give on the shapes' voxels (shapes in array order, within a shape the cells that hold a voxel of it in
@@ -145,6 +156,18 @@ private:
     // an element that is none of the three kinds
     bool writeRows(const WriteBox &w, const uint16_t *data, uint32_t cx, uint32_t cy, uint32_t cz, uint8_t set[64], uint8_t clear[64], bool *has_set,
                    bool *has_clear) const;
+    // does the queries' filter see material entry m (true while none is set) ...
+    bool sees(uint8_t m) const { return !query_filter_set_ || ((query_filter_.see[m >> 5] >> (m & 31u)) & 1u); }
+    // ... and the bits of `row` — B voxels along x from bit row_bit of a brick — whose voxels it sees
+    uint32_t seenRow(uint32_t brick_index, uint32_t row_bit, uint32_t row) const {
+        if (!query_filter_set_) return row;
+        const uint8_t *materials = &material_indices[(size_t)(brick_start_indices[brick_index] & 0x7FFFFFFFu) + row_bit]; // comp:422-425
+        for (uint32_t rest = row; rest; rest &= rest - 1u)
+            if (!sees(materials[__builtin_ctz(rest)])) row &= ~(1u << __builtin_ctz(rest));
+        return row;
+    }
+    vrt_material_filter query_filter_{};
+    bool query_filter_set_ = false;
 
     uint32_t brick_dimension_ = 4, brick_bits_ = 64, brick_bytes_ = 8;
     uint64_t brick_alloc_ = 0;

@@ -288,6 +288,19 @@ int vrt_grid_sweep_boxes(const vrt_grid *g, const vrt_box_sweep *sweeps, uint64_
     return rc == VRT_OK ? rc : vrt_impl::fail(nullptr, rc, why); // (a grid keeps no error text: vrt_last_error(NULL) has it)
 }
 
+int vrt_grid_set_query_filter(vrt_grid *g, const vrt_material_filter *f) {
+    if (!g) return VRT_E_INVALID_ARG;
+    reinterpret_cast<vrt::BrickGrid *>(g)->setQueryFilter(f);
+    return VRT_OK;
+}
+
+int vrt_grid_get_query_filter(const vrt_grid *g, vrt_material_filter *out, uint32_t *is_set) {
+    if (!g || !out) return VRT_E_INVALID_ARG;
+    const bool set = reinterpret_cast<const vrt::BrickGrid *>(g)->queryFilter(out);
+    if (is_set) *is_set = set ? 1u : 0u;
+    return VRT_OK;
+}
+
 int vrt_grid_fill_shapes(vrt_grid *g, const vrt_shape *shapes, uint64_t n) {
     if (!g) return VRT_E_INVALID_ARG;
     return reinterpret_cast<vrt::BrickGrid *>(g)->fillShapes(shapes, n);

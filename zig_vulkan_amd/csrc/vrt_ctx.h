@@ -235,6 +235,9 @@ struct vrt_ctx {
     // the queries' host forms (vrt_query.hip): the device buffers a piece of a batch goes in and comes out through, whatever its kind
     uint8_t *d_query_in = nullptr, *d_query_out = nullptr;
     uint64_t query_in_bytes = 0, query_out_bytes = 0; // bytes each holds
+    // the material filter of the scene queries (vrt_set_query_filter): host state, copied into the arguments of every query launch
+    vrt_material_filter query_filter{};
+    bool query_filter_set = false;
     // the first-hit buffer pass (vrt_trace_aux): the host path's device buffer, the wanted planes one after another
     uint8_t *d_aux_planes = nullptr;
     uint64_t aux_capacity = 0;       // bytes it holds

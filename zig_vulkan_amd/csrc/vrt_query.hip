@@ -42,30 +42,51 @@ struct QueryScene {
     uint32_t brick_alloc; // a loaded cell that names a brick beyond it (no scene an edit or a host grid made) reads as empty
 };
 
+// The material filter of a launch (vrt_set_query_filter), the last member of every kind's arguments.  on == 0: none is set; every
+// kernel branches on it uniformly, and a launch without a filter executes no vector load and no per-lane test it did not before.
+struct QueryFilter {
+    uint32_t on;
+    uint32_t see[8]; // bit (m & 31) of see[m >> 5]: material entry m is seen
+};
+VRT_DI bool filter_sees(const QueryFilter &f, uint32_t material) { return (f.see[material >> 5] >> (material & 31u)) & 1u; }
+// The same from the eight words in scalar registers, picked by three selects: no lane's value indexes the kernel's arguments.  (Where an
+// argument struct is indexed by a lane the compiler stops merging the scalar loads of its other members, and a look-up's chain of
+// dependent loads gets a round trip to the scalar cache in front of each.)
+VRT_DI bool filter_sees_select(const QueryFilter &f, uint32_t material) {
+    const uint32_t w01 = (material & 32u) ? f.see[1] : f.see[0], w23 = (material & 32u) ? f.see[3] : f.see[2];
+    const uint32_t w45 = (material & 32u) ? f.see[5] : f.see[4], w67 = (material & 32u) ? f.see[7] : f.see[6];
+    const uint32_t w03 = (material & 64u) ? w23 : w01, w47 = (material & 64u) ? w67 : w45;
+    return (((material & 128u) ? w47 : w03) >> (material & 31u)) & 1u;
+}
+
 // The kernel arguments, one struct per kind.  The four batched kinds share their shape: the scene, and one launch's share of the batch.
 struct RayArgs {
     TraceParams scene;
     const u32x4 *in; // vrt_ray_query as two dwordx4 (16-byte aligned, like the hits)
     u32x4 *out;      // vrt_ray_hit as three dwordx4
     uint64_t n;      // rays of this launch, one per lane
+    QueryFilter filter;
 };
 struct VoxelArgs {
     QueryScene scene;
     const uint32_t *in; // x, y, z per voxel, y as vrt_grid_insert takes it
     uint16_t *out;      // the material entry, or VRT_VOXEL_EMPTY
     uint64_t n;         // voxels, one per lane
+    QueryFilter filter;
 };
 struct BoxArgs {
     QueryScene scene;
     const u32x4 *in; // vrt_box_query as two dwordx4 (16-byte aligned, like the results)
     u32x4 *out;      // vrt_box_result as two dwordx4
     uint64_t n;      // boxes, one per wave
+    QueryFilter filter;
 };
 struct SweepArgs {
     QueryScene scene;
     const u32x4 *in; // vrt_box_sweep as three dwordx4 (16-byte aligned, like the hits)
     u32x4 *out;      // vrt_sweep_hit as two dwordx4
     uint64_t n;      // sweeps, one per lane
+    QueryFilter filter;
 };
 // The first-hit buffer pass: a workgroup is a 16x16-pixel tile of the camera's image, blockIdx.x / .y the tile's column / row
 struct AuxArgs {
@@ -77,6 +98,7 @@ struct AuxArgs {
     u32x4 *point_t;         // dwords 0..3 of vrt_ray_hit (16-byte aligned, like the next two)
     u32x4 *normal_material; // dwords 4..7
     u32x4 *voxel_hit;       // dwords 8..11
+    QueryFilter filter;
 };
 // The dense box reads: n items, one per lane
 struct ReadArgs {
@@ -88,6 +110,7 @@ struct ReadArgs {
     uint32_t first_item;    // the first item of this launch
     uint32_t first_element; // the element `out` points at (the first element of the launch's first item, or 0)
     uint32_t n;             // items of this launch
+    QueryFilter filter;
 };
 
 constexpr uint32_t kQueryBlock = 256u;             // threads per workgroup: four waves, one ray per lane
@@ -124,10 +147,15 @@ VRT_DI HitRecord pack_hit(bool found, const Hit hit, const int voxel[3], uint32_
 }
 
 // The frames' choice of status copy: the byte per cell where the context keeps one (grids up to 2^18 cells), the shader's words
-// otherwise.  Both walks give the same hits; the branch is uniform over the launch.
+// otherwise.  Both walks give the same hits; the branch is uniform over the launch.  So is the one on the filter: with one set the walk
+// is grid_hit<SEE>, whose lanes walk on through a solid voxel the filter hides as through one their ray ignores (comp:427).
 template <int B>
-VRT_DI bool query_walk(const TraceParams &p, const Ray &r, Hit &hit, int *voxel) {
+VRT_DI bool query_walk(const TraceParams &p, const QueryFilter &f, const Ray &r, Hit &hit, int *voxel) {
     Cnt<false> c;
+    if (f.on) {
+        if (p.status_bytes) return grid_hit<B, false, kStatusBytes, false, false, true, false, false, false, true>(p, nullptr, r, hit, c, voxel, nullptr, false, f.see);
+        return grid_hit<B, false, kStatusLinearAlways, false, false, true, false, false, false, true>(p, nullptr, r, hit, c, voxel, nullptr, false, f.see);
+    }
     if (p.status_bytes) return grid_hit<B, false, kStatusBytes, false, false, true>(p, nullptr, r, hit, c, voxel);
     return grid_hit<B, false, kStatusLinearAlways, false, false, true>(p, nullptr, r, hit, c, voxel);
 }
@@ -153,7 +181,7 @@ VRT_DI void aux_query(const AuxArgs &a) {
     Hit hit;
     int voxel[3] = {0, 0, 0};
     bool found = false;
-    if (ray_walkable(origin, direction)) found = query_walk<B>(a.scene, create_ray(origin, direction), hit, voxel) && hit.t <= __builtin_inff();
+    if (ray_walkable(origin, direction)) found = query_walk<B>(a.scene, a.filter, create_ray(origin, direction), hit, voxel) && hit.t <= __builtin_inff();
     const HitRecord r = pack_hit(found, hit, voxel, a.scene.grid.voxel_dim_y);
     const uint32_t pixel = py * a.width + px; // (at most 2^24 pixels)
     if (a.depth) a.depth[pixel] = found ? hit.t : __builtin_inff();
@@ -179,7 +207,7 @@ VRT_DI void ray_query(const RayArgs &a) {
     if (ray_walkable(origin, direction) && max_t >= 0.0f && (flags & ~VRT_RAY_RAW_DIRECTION) == 0u) { // (NaN max_t fails `>= 0`)
         // CreateRay (comp:180-184), or the ray as given
         const Ray r = (flags & VRT_RAY_RAW_DIRECTION) ? Ray{origin, direction, 1.0f, MAT_NONE} : create_ray(origin, direction);
-        found = query_walk<B>(a.scene, r, hit, voxel) && hit.t <= max_t; // max_t filters the first hit
+        found = query_walk<B>(a.scene, a.filter, r, hit, voxel) && hit.t <= max_t; // max_t filters the first hit (under a filter: the first seen one)
     }
     const HitRecord r = pack_hit(found, hit, voxel, a.scene.grid.voxel_dim_y);
     u32x4 *dst = a.out + 3u * i;
@@ -227,12 +255,60 @@ VRT_DI uint64_t cell_box_mask(uint32_t xl, uint32_t xh, uint32_t zl, uint32_t zh
     else return group_bits(xl, xh, 0x1111111111111111ull) & (0x0001000100010001ull * (group_range(zl, zh, 4u) & 0xFFFFull)) & group_range(yl, yh, 16u);
 }
 
+// Under a filter: the bits of m — a masked occupancy word, word `word` of an 8^3 brick or a whole 4^3 brick — whose voxels the filter
+// sees.  The word's voxels are 64 contiguous bytes of binding 6: where the brick's entries start on a 16-byte boundary (every brick an
+// insert or an edit made) they come as dwordx4, and only the quarters of the word that hold a bit of m are loaded; the table look-up of
+// a byte reads the launch's own arguments.  Otherwise a byte per set bit.  A voxel whose entry lies beyond binding 6 has no material to
+// hide it by: its bit stays, as in a count without a filter.
+template <int B>
+VRT_DI uint64_t seen_bits(const QueryScene &s, const QueryFilter &f, uint32_t brick, uint32_t word, uint64_t m) {
+    const uint32_t entry = brick_entry(s, brick, word * 64u), limit = entry_limit<B>(s);
+    uint64_t seen = 0ull;
+    if ((entry & 15u) == 0u && entry + 64u <= limit) {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(s.material_index + entry);
+#pragma unroll
+        for (uint32_t quarter = 0; quarter < 4u; quarter++) {
+            const uint32_t part = (uint32_t)(m >> (16u * quarter)) & 0xFFFFu;
+            if (part == 0u) continue;
+            const u32x4 v = src[quarter];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w}; // (indexed by constants after unrolling)
+            uint32_t bits = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < 16u; k++) bits |= (uint32_t)filter_sees(f, (w[k >> 2] >> (8u * (k & 3u))) & 0xFFu) << k;
+            seen |= (uint64_t)(bits & part) << (16u * quarter);
+        }
+    } else {
+        for (uint64_t rest = m; rest; rest &= rest - 1ull) {
+            const uint32_t bit = (uint32_t)__builtin_ctzll(rest);
+            if (entry + bit >= limit || filter_sees(f, s.material_index[entry + bit])) seen |= 1ull << bit;
+        }
+    }
+    return seen;
+}
+// The sweeps' form.  A sweep wants the first seen voxel of a word only, and its kernel has no register to spare: the sixteen look-ups
+// seen_bits keeps in flight would cost every sweep, filtered or not, a wave per SIMD.  m (bit 0 = the voxel of `entry`) without its
+// lowest bits up to the first voxel the filter sees, 0 where it sees none: a byte per hidden voxel passed, none behind the first seen.
+template <int B>
+VRT_DI uint64_t from_first_seen(const QueryScene &s, const QueryFilter &f, uint32_t entry, uint64_t m) {
+    const uint32_t limit = entry_limit<B>(s);
+    while (m) {
+        const uint32_t e = entry + (uint32_t)__builtin_ctzll(m);
+        if (e >= limit || filter_sees(f, s.material_index[e])) break;
+        m &= m - 1ull;
+    }
+    return m;
+}
+
 // Voxel look-ups: one voxel per lane; a wave reads 768 contiguous bytes of xyz and stores 128 of materials.
 template <int B>
 VRT_DI void voxel_query(const VoxelArgs &a) {
     constexpr uint32_t kBits = (uint32_t)(B * B * B);
     const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
+    // "a filter is set", requested with n and held in a scalar register from here on: requested where it is used, behind the look-up,
+    // it is one more round trip to the scalar cache at the end of every wave (the empty asm pins it)
+    const uint32_t filtered = a.filter.on;
     if (i >= a.n) return;
+    asm volatile("" ::"s"(filtered));
     const uint32_t *src = a.in + 3u * i;
     const uint32_t x = src[0], y = src[1], z = src[2];
     const QueryScene &s = a.scene;
@@ -246,15 +322,17 @@ VRT_DI void voxel_query(const VoxelArgs &a) {
             if ((s.brick_occupancy[brick * (kBits / 8u) + (nth_bit >> 3)] >> (nth_bit & 7u)) & 1u) material = brick_material<B>(s, brick, nth_bit);
         }
     }
+    if (filtered && material != VRT_VOXEL_EMPTY && !filter_sees_select(a.filter, material)) material = VRT_VOXEL_EMPTY; // a hidden voxel reads as empty
     a.out[i] = (uint16_t)material;
 }
 
 // Box counts: one wave per box.  The wave clips the box and turns it into a range of cells; its lanes stride over the occupancy words of
 // those cells (cell-major, the eight layers of a cell on adjacent lanes), skip the cells whose status bit is 0 before any other load,
 // and count word & mask, the mask being box intersected with cell.  The bounds come from the first and last set bit of the rows' OR (x),
-// of the word (z, and y of a 4^3 brick) and from the layer (y of an 8^3 brick).
-template <int B>
-VRT_DI void box_query(const BoxArgs &a) {
+// of the word (z, and y of a 4^3 brick) and from the layer (y of an 8^3 brick).  Without a filter no material is read; under one a
+// lane with a non-zero masked word drops the bits of hidden voxels first (seen_bits).
+template <int B, bool SEE>
+VRT_DI void box_query_walk(const BoxArgs &a) {
     constexpr uint32_t kWords = B == 8 ? 8u : 1u;    // 64-bit occupancy words per brick
     constexpr uint32_t kStride = 64u / kWords;       // cells a wave covers per trip
     const uint32_t lane = threadIdx.x & 63u;
@@ -289,7 +367,10 @@ VRT_DI void box_query(const BoxArgs &a) {
                 const uint32_t yl = y0 > by ? y0 - by : 0u, yh = std::min(y1 - by, (uint32_t)B - 1u); // (read for 4^3 bricks only)
                 const bool layer = B != 8 || (by + word >= y0 && by + word <= y1); // an 8^3 brick's word is one layer
                 const uint64_t mask = layer ? cell_box_mask<B>(xl, xh, zl, zh, yl, yh) : 0ull;
-                const uint64_t m = (brick < s.brick_alloc && mask) ? occupancy[(uint64_t)brick * kWords + word] & mask : 0ull;
+                uint64_t m = (brick < s.brick_alloc && mask) ? occupancy[(uint64_t)brick * kWords + word] & mask : 0ull;
+                if constexpr (SEE) {
+                    if (m) m = seen_bits<B>(s, a.filter, brick, word, m); // count and bounds over the seen voxels
+                }
                 if (m) {
                     count += (uint64_t)__builtin_popcountll(m);
                     const uint32_t first = (uint32_t)__builtin_ctzll(m), last = 63u - (uint32_t)__builtin_clzll(m);
@@ -342,6 +423,11 @@ VRT_DI void box_query(const BoxArgs &a) {
     }
     a.out[2u * box] = r0;
     a.out[2u * box + 1u] = r1;
+}
+template <int B>
+VRT_DI void box_query(const BoxArgs &a) {
+    if (!a.filter.on) box_query_walk<B, false>(a);
+    else box_query_walk<B, true>(a);
 }
 
 // Dense box reads: one cell row of one box per lane. An item is (box k, row (y, z) of the box, cell column c), c from floor(lo.x / B) to
@@ -402,10 +488,15 @@ VRT_DI void read_query(const ReadArgs &a) {
                     for (uint32_t x = 0; x < (uint32_t)B; x++)
                         if (((bits >> x) & 1u) && entry + x < limit) bytes |= (uint64_t)s.material_index[entry + x] << (8u * x);
                 }
+                uint32_t hidden = 0u; // under a filter: the voxels of the row whose material byte, in hand, the filter hides
+                if (a.filter.on) { // (uniform over the launch)
+#pragma unroll
+                    for (uint32_t x = 0; x < (uint32_t)B; x++) hidden |= (uint32_t)!filter_sees_select(a.filter, (uint32_t)(bytes >> (8u * x)) & 0xFFu) << x;
+                }
                 uint64_t w[2] = {0ull, 0ull};
 #pragma unroll
                 for (uint32_t x = 0; x < (uint32_t)B; x++) { // (x is a constant after unrolling)
-                    const bool solid = ((bits >> x) & 1u) && entry + x < limit; // an entry at or beyond the end reads as empty, as a voxel look-up reads it
+                    const bool solid = (((bits & ~hidden) >> x) & 1u) && entry + x < limit; // an entry at or beyond the end reads as empty, as a voxel look-up reads it
                     const uint64_t value = solid ? (bytes >> (8u * x)) & 0xFFull : (uint64_t)VRT_VOXEL_EMPTY;
                     w[x >> 2] |= value << (16u * (x & 3u));
                 }
@@ -459,9 +550,11 @@ VRT_DI void read_query(const ReadArgs &a) {
 // intersected with cell (cell_box_mask).  With y flipped the first voxel of a cell by (y, z, x) is the lowest set bit of its
 // highest layer that has one; a cell's candidate is packed, relative to the slab's corner, into one key (a slab has fewer than 64 layers
 // on every axis), the smallest key wins, and a row of cells that gave one ends the search.  Only the winner's material is loaded.
-template <int B>
+// SEE: under a filter "solid" means seen — a masked word loses its bits up to the first seen voxel (from_first_seen) before that is taken.
+template <int B, bool SEE = false>
 struct SweepSlab {
     const QueryScene &scene;
+    const QueryFilter *filter = nullptr; // (SEE)
     VRT_DI bool operator()(const SweepSlabRange &s, SweepContact &c) const {
         constexpr uint32_t kShift = B == 8 ? 3u : 2u, kMask = (uint32_t)B - 1u;
         const vrt_grid_state &g = scene.grid;
@@ -494,14 +587,20 @@ struct SweepSlab {
                     bool found = false;
                     if constexpr (B == 8) {
                         for (uint32_t l = yh + 1u; l-- > yl;) {
-                            const uint64_t m = occupancy[(uint64_t)brick * 8u + l] & mask;
+                            uint64_t m = occupancy[(uint64_t)brick * 8u + l] & mask;
+                            if constexpr (SEE) m = from_first_seen<B>(scene, *filter, brick_entry(scene, brick, 64u * l), m);
                             if (m) {
                                 layer = l, bit = (uint32_t)__builtin_ctzll(m), found = true;
                                 break;
                             }
                         }
                     } else {
-                        const uint64_t m = occupancy[brick] & mask;
+                        uint64_t m = occupancy[brick] & mask;
+                        if constexpr (SEE) { // layer by layer from the top: the first seen voxel of the highest layer that has one
+                            const uint64_t all = m;
+                            m = 0ull;
+                            for (uint32_t l = 4u; l-- > 0u && !m;) m = from_first_seen<B>(scene, *filter, brick_entry(scene, brick, 16u * l), (all >> (16u * l)) & 0xFFFFull) << (16u * l);
+                        }
                         if (m) {
                             layer = (63u - (uint32_t)__builtin_clzll(m)) >> 4;
                             bit = (uint32_t)__builtin_ctz((uint32_t)(m >> (16u * layer)) & 0xFFFFu), found = true;
@@ -529,7 +628,7 @@ VRT_DI void sweep_query(const SweepArgs &a) {
     // Sixteen no-ops, run once per wave, that move the kernel's code by 64 bytes.  The batches that are one wave per SIMD follow where
     // the slab loops fall in the instruction stream: without them the same instructions are 6 % (characters) and 2 % (the limit boxes)
     // behind the sweeps as they were inside the six-mode kernel, with them level (profiles/query_split/regression_ab.md).
-    asm volatile("s_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\n");
+    asm volatile(".rept %0\ns_nop 0\n.endr\n" ::"i"(16));
     const uint64_t i = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
     if (i >= a.n) return;
     const u32x4 *src = a.in + 3u * i;
@@ -537,7 +636,8 @@ VRT_DI void sweep_query(const SweepArgs &a) {
     const float lo[3] = {as_f32(q0.x), as_f32(q0.y), as_f32(q0.z)}, hi[3] = {as_f32(q1.x), as_f32(q1.y), as_f32(q1.z)};
     const float move[3] = {as_f32(q2.x), as_f32(q2.y), as_f32(q2.z)};
     vrt_sweep_hit h;
-    sweep_box(lo, hi, move, q0.w | q1.w | q2.w, SweepSlab<B>{a.scene}, &h);
+    if (!a.filter.on) sweep_box(lo, hi, move, q0.w | q1.w | q2.w, SweepSlab<B>{a.scene}, &h); // (uniform over the launch)
+    else sweep_box(lo, hi, move, q0.w | q1.w | q2.w, SweepSlab<B, true>{a.scene, &a.filter}, &h);
     u32x4 *dst = a.out + 2u * i;
     dst[0] = u32x4{as_u32(h.t), h.status, h.material, (uint32_t)h.normal};
     dst[1] = u32x4{(uint32_t)h.voxel[0], (uint32_t)h.voxel[1], (uint32_t)h.voxel[2], 0u};
@@ -545,16 +645,17 @@ VRT_DI void sweep_query(const SweepArgs &a) {
 
 } // namespace vrt
 
-// A kernel pair per kind, vrt_<kind>_b4 / _b8, each at five waves per SIMD (<= 96 VGPRs)
-#define VRT_QUERY_KERNELS(kind, Args)                                                                                          \
-    extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, 5) void vrt_##kind##_b4(const vrt::Args a) { vrt::kind<4>(a); } \
-    extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, 5) void vrt_##kind##_b8(const vrt::Args a) { vrt::kind<8>(a); }
-VRT_QUERY_KERNELS(ray_query, RayArgs)
-VRT_QUERY_KERNELS(aux_query, AuxArgs)
-VRT_QUERY_KERNELS(voxel_query, VoxelArgs)
-VRT_QUERY_KERNELS(box_query, BoxArgs)
-VRT_QUERY_KERNELS(read_query, ReadArgs)
-VRT_QUERY_KERNELS(sweep_query, SweepArgs)
+// A kernel pair per kind, vrt_<kind>_b4 / _b8, each at five waves per SIMD (<= 96 VGPRs).  The sweeps ask for the six they always ran at
+// (<= 80 VGPRs): their filtered walk shares the kernel with the plain one, and at one register more every sweep would lose a wave.
+#define VRT_QUERY_KERNELS(kind, Args, waves)                                                                                       \
+    extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, waves) void vrt_##kind##_b4(const vrt::Args a) { vrt::kind<4>(a); } \
+    extern "C" __global__ __launch_bounds__(vrt::kQueryBlock, waves) void vrt_##kind##_b8(const vrt::Args a) { vrt::kind<8>(a); }
+VRT_QUERY_KERNELS(ray_query, RayArgs, 5)
+VRT_QUERY_KERNELS(aux_query, AuxArgs, 5)
+VRT_QUERY_KERNELS(voxel_query, VoxelArgs, 5)
+VRT_QUERY_KERNELS(box_query, BoxArgs, 5)
+VRT_QUERY_KERNELS(read_query, ReadArgs, 5)
+VRT_QUERY_KERNELS(sweep_query, SweepArgs, 6)
 #undef VRT_QUERY_KERNELS
 
 using namespace vrt_impl;
@@ -573,6 +674,12 @@ void bind_scene(const vrt_ctx *ctx, vrt::TraceParams &scene) { scene = ctx->para
 void bind_scene(const vrt_ctx *ctx, vrt::QueryScene &scene) {
     const vrt::TraceParams &p = ctx->params;
     scene = {p.grid, p.brick_status, p.brick_index, p.brick_occupancy, p.brick_start_index, p.material_index, (uint32_t)ctx->cfg.brick_alloc}; // (brick_alloc * B^3 <= 2^31)
+}
+
+// The filter of a launch: the context's, as it is set now
+void bind_filter(const vrt_ctx *ctx, vrt::QueryFilter &f) {
+    f.on = ctx->query_filter_set ? 1u : 0u;
+    for (int k = 0; k < 8; k++) f.see[k] = ctx->query_filter_set ? ctx->query_filter.see[k] : 0u;
 }
 
 // What the ray queries and the first-hit buffer pass check and do before their first launch: the scene is there, and the derived
@@ -599,6 +706,7 @@ template <class Args, void (*K4)(const Args), void (*K8)(const Args)>
 hipError_t launch_kind(vrt_ctx *ctx, const void *in, uint64_t n, void *out, dim3 groups) {
     Args a{};
     bind_scene(ctx, a.scene);
+    bind_filter(ctx, a.filter);
     a.in = static_cast<decltype(a.in)>(in), a.out = static_cast<decltype(a.out)>(out), a.n = n;
     return launch_pair(K4, K8, a, ctx, groups);
 }
@@ -735,6 +843,7 @@ int read_boxes_run(vrt_ctx *ctx, const vrt_box_query *boxes, uint64_t n, uint64_
 
     vrt::ReadArgs a{};
     bind_scene(ctx, a.scene);
+    bind_filter(ctx, a.filter);
     a.boxes = reinterpret_cast<const vrt::u32x4 *>(d_tables);
     a.prefix = reinterpret_cast<const uint32_t *>(d_tables + n * sizeof(vrt_box_query));
     a.box_count = (uint32_t)n;
@@ -805,6 +914,7 @@ int aux_begin(vrt_ctx *ctx) {
 int launch_aux(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_planes &planes) {
     vrt::AuxArgs a{};
     bind_scene(ctx, a.scene);
+    bind_filter(ctx, a.filter);
     a.width = camera->image_width;
     a.height = camera->image_height;
     for (int k = 0; k < 3; k++) {
@@ -866,6 +976,20 @@ int vrt_trace_aux(vrt_ctx *ctx, const vrt_camera_device *camera, const vrt_aux_p
     for (int k = 0; k < 4; k++)
         if (host[k]) VRT_HIP(ctx, hipMemcpyAsync(host[k], dev[k], pixels * (k < 3 ? 16u : 4u), hipMemcpyDeviceToHost, ctx->stream));
     VRT_HIP(ctx, wait_stream(ctx->stream));
+    return VRT_OK;
+}
+
+int vrt_set_query_filter(vrt_ctx *ctx, const vrt_material_filter *f) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    ctx->query_filter_set = f != nullptr;
+    if (f) ctx->query_filter = *f;
+    return VRT_OK;
+}
+
+int vrt_get_query_filter(const vrt_ctx *ctx, vrt_material_filter *out, uint32_t *is_set) {
+    if (!ctx || !out) return VRT_E_INVALID_ARG;
+    for (int k = 0; k < 8; k++) out->see[k] = ctx->query_filter_set ? ctx->query_filter.see[k] : ~0u;
+    if (is_set) *is_set = ctx->query_filter_set ? 1u : 0u;
     return VRT_OK;
 }
 

@@ -1210,13 +1210,17 @@ VRT_DI int steps_left_fresh(int step, int pos, int dim, int zero_budget) {
 // caller looks the material up once the walk is over (grid_hit).  kPlainAnyHit: the caller only asks whether there is a hit (a shadow
 // ray); `hit` and hit_axis are not outputs.  Where the bit is clear — a scene with a MAT_NONE record, a context made without the
 // flag — the round is the one every other kernel runs, and hit.index is the material.
+// SEE (the filtered scene queries, vrt_query.hip's query_walk; off everywhere else): `see` is a material filter's 256 bits, and a lane
+// walks on through a solid voxel whose material entry the filter hides exactly as through one its ray ignores.
 constexpr int kPlainOff = 0, kPlainHit = 1, kPlainAnyHit = 2;
-template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false, bool CONSTS = false, int PLAIN = kPlainOff>
+template <int B, bool EAGER = true, bool BY_CELL = false, bool VOXEL = false, bool REJECT = false, bool CONSTS = false, int PLAIN = kPlainOff, bool SEE = false>
 VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const Ray &r, const RaySetup &s, float g_scale, uint32_t brick_index, f3 brick_min,
-                              Hit &hit, int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u) {
+                              Hit &hit, int axis_in, int &hit_axis, uint32_t cell = 0u, uint32_t *hit_voxel = nullptr, uint32_t box = 0u,
+                              [[maybe_unused]] const uint32_t *see = nullptr) {
     constexpr bool kConsts = CONSTS;
     static_assert(!(CONSTS && BY_CELL), "the by-cell copy is the bounce kernel's");
     static_assert(PLAIN == kPlainOff || CONSTS, "the flags word is BrickConsts'");
+    static_assert(!SEE || PLAIN == kPlainOff, "a filter tests the material entry, which a plain round does not look up");
     const float brick_voxel_scale = 1.0f / (float)B; // spec const 5, Pipeline.zig:313
     const float voxel_scale = g_scale * brick_voxel_scale;
     const bool pow2 = kConsts ? opaque_uniform(bc.scale_pow2) != 0u : p.scale_pow2 != 0u;
@@ -1295,6 +1299,7 @@ VRT_DI bool brick_walk_gfx950(const TraceParams &p, const BrickConsts &bc, const
                 const uint32_t mtype = m->type;
                 const float mdata = m->type_data;
                 ignore_brick = (mtype == r.ignore_type_material) && (r.internal_reflection == mdata); // comp:427
+                if constexpr (SEE) ignore_brick = ignore_brick || !((see[mi >> 5] >> (mi & 31u)) & 1u);
             }
             if (!ignore_brick) {
                 if constexpr (PLAIN != kPlainAnyHit) {
@@ -1596,9 +1601,13 @@ VRT_DI f3 opaque_uniform3(const float (&v)[3]) { return mk3(opaque_uniform(v[0])
 // it (brick_walk_gfx950<..., PLAIN>): a hit's material is then requested HERE, once, behind the walk — the caller reads it behind
 // its next walk, and the round trip runs under that walk's set-up.  ANY_HIT (with KARGS: the shadow ray): only the answer counts; `hit`
 // is not an output, and on such a scene no round asks for a material at all.
-template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false, bool ANY_HIT = false>
+// SEE (with VOXEL: the scene queries under a material filter, whose 256 bits are `see`): the brick rounds pass over the solid voxels
+// the filter hides (brick_walk_gfx950<..., SEE>).  No other instantiation reads `see`.
+template <int B, bool COUNT, int MODE, bool BATCH = false, bool SCALAR_ENTRY = false, bool VOXEL = false, bool REJECT = false, bool KARGS = false, bool ANY_HIT = false,
+          bool SEE = false>
 VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray &r, Hit &hit, Cnt<COUNT> &c, int *voxel = nullptr,
-                     const DerivedWords *early = nullptr, bool sits_out = false) {
+                     const DerivedWords *early = nullptr, bool sits_out = false, [[maybe_unused]] const uint32_t *see = nullptr) {
+    static_assert(!SEE || (VOXEL && !KARGS), "material filters belong to the scene queries' walks");
     static_assert(!VOXEL || ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT && !BATCH),
                   "voxel coordinates come from the hand-written walk without batching");
     constexpr bool kHandWalk = (MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT;
@@ -1767,7 +1776,7 @@ VRT_DI bool grid_hit(const TraceParams &p, const uint32_t *lds_filter, const Ray
         bool found;
         if constexpr ((MODE == kStatusLinearAlways || MODE == kStatusLinearLds || MODE == kStatusBytes) && !COUNT) {
             [[maybe_unused]] uint32_t voxel_in_brick = 0u;
-            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT, KARGS, kPlain>(p, bc, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box);
+            found = brick_walk_gfx950<B, true, BATCH, VOXEL, REJECT, KARGS, kPlain, SEE>(p, bc, r, s, g_scale, brick_index, brick_min, hit, brick_axis, hit_axis, cell, &voxel_in_brick, box, see);
             if constexpr (VOXEL) {
                 if (found) { // voxel index x + B (z + B y) in the brick (comp:412)
                     voxel[0] = cx * B + (int)(voxel_in_brick % (uint32_t)B);

@@ -12,6 +12,7 @@ this module only marshals arguments.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, field
 from typing import Optional, Sequence, Tuple
@@ -155,6 +156,20 @@ class BrickGrid:
         if rc != L.VRT_OK:
             raise L.VrtError(rc, (lib.vrt_last_error(None) or b"").decode())
         return out
+
+    def set_query_filter(self, see=None, hide=None) -> None:
+        """vrt_grid_set_query_filter: the material entries get_voxels, query_boxes, read_boxes and sweep_boxes see (`see`) or do not
+        (`hide`), as material_filter takes them; the four then answer as on the grid after remove_many of every hidden voxel.  None,
+        None clears the filter.  Nothing else changes: the arrays, the deltas and every edit are as without one."""
+        f = material_filter(see, hide)
+        check(lib.vrt_grid_set_query_filter(self._h, C.byref(f) if f is not None else None))
+
+    @property
+    def query_filter(self) -> Optional[np.ndarray]:
+        """The filter that is set as a 256-element bool array ([m]: material entry m is seen), or None while none is set."""
+        f, is_set = L.MaterialFilter(), C.c_uint32(0)
+        check(lib.vrt_grid_get_query_filter(self._h, C.byref(f), C.byref(is_set)))
+        return filter_seen(f) if is_set.value else None
 
     @property
     def device_state(self) -> L.GridState:
@@ -415,6 +430,36 @@ def shape_records(shapes) -> np.ndarray:
         return np.ascontiguousarray(shapes).reshape(-1)
     shapes = list(shapes)
     return np.ascontiguousarray(np.concatenate([shape_records(s) for s in shapes])) if shapes else np.zeros(0, dtype=SHAPE_DTYPE)
+
+
+def material_filter(see=None, hide=None) -> Optional[L.MaterialFilter]:
+    """A vrt_material_filter from the material entries the queries see, or from those they do not: an iterable of entries (0..255) or
+    a 256-element bool array to either argument, never to both.  None, None: no filter (None)."""
+    if see is not None and hide is not None:
+        raise ValueError("give the entries to see or the entries to hide, not both")
+    if see is None and hide is None:
+        return None
+    given = see if see is not None else hide
+    a = np.asarray(given if isinstance(given, np.ndarray) else list(given))
+    if a.dtype == np.bool_:
+        if a.shape != (256,):
+            raise ValueError("a bool array names all 256 material entries")
+        named = a.copy()
+    else:
+        entries = a.astype(np.int64).reshape(-1)
+        if entries.size and (entries.min() < 0 or entries.max() > 255 or not np.array_equal(entries, a.reshape(-1))):
+            raise ValueError("material entries are integers 0..255")
+        named = np.zeros(256, dtype=bool)
+        named[entries] = True
+    seen = named if see is not None else ~named
+    f = L.MaterialFilter()
+    f.see[:] = np.packbits(seen, bitorder="little").view("<u4").tolist()
+    return f
+
+
+def filter_seen(f: L.MaterialFilter) -> np.ndarray:
+    """The 256 bits of a vrt_material_filter as a bool array: [m] is True where material entry m is seen."""
+    return np.unpackbits(np.array(list(f.see), dtype="<u4").view(np.uint8), bitorder="little").astype(bool)
 
 
 def ray_queries(origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
@@ -704,6 +749,33 @@ class VoxelRT:
 
     def wait(self) -> None:
         self._check(self._lib.vrt_wait(self._h))
+
+    # -- the material filter of the scene queries -----------------------------------
+    def set_query_filter(self, see=None, hide=None) -> None:
+        """vrt_set_query_filter: the material entries the scene queries see (`see`) or do not (`hide`), as material_filter takes them:
+        an iterable of entries or a 256-element bool array to either, never to both; None, None clears the filter.  While one is set
+        cast_rays, trace_aux, get_voxels, query_boxes, read_boxes and sweep_boxes answer as on the scene after remove_voxels of every
+        hidden voxel; frames, edits and read_buffer are untouched.  Host state: a device query already issued keeps the filter it
+        was issued under.  An undo record for write_boxes must be read with no filter set."""
+        f = material_filter(see, hide)
+        self._check(self._lib.vrt_set_query_filter(self._h, C.byref(f) if f is not None else None))
+
+    @property
+    def query_filter(self) -> Optional[np.ndarray]:
+        """The filter that is set as a 256-element bool array ([m]: material entry m is seen), or None while none is set."""
+        f, is_set = L.MaterialFilter(), C.c_uint32(0)
+        self._check(self._lib.vrt_get_query_filter(self._h, C.byref(f), C.byref(is_set)))
+        return filter_seen(f) if is_set.value else None
+
+    @contextlib.contextmanager
+    def filtered(self, hide=None, see=None):
+        """`with rt.filtered(hide=[0]):` — the queries inside run under that filter; the one set before is restored on exit."""
+        before = self.query_filter
+        self.set_query_filter(see=see, hide=hide)
+        try:
+            yield self
+        finally:
+            self.set_query_filter(see=before)
 
     # -- ray queries ----------------------------------------------------------
     def cast_rays(self, origins, directions, max_t=None, raw: bool = False) -> np.ndarray:
