@@ -122,6 +122,7 @@ typedef struct {
     const oracle_scene *s;
     const oracle_push *pc;
     oracle_counters *c;
+    int32_t *voxel; /* optional: the voxel of the hit in the walk's voxel coordinates (cell * brick_dimensions + position in the brick) */
 } Env;
 
 /* ------------------------------------------------------------------ lowering of the GLSL built-ins
@@ -360,6 +361,7 @@ static int BrickHit(const Env *e, const Ray *r, float t_min, float t_max, v3 ray
                 hit->t += t_value - t_offset;
                 hit->point = vadd(RayAt(r, hit->t), vscale(hit->normal, t_offset));
                 *brick_position = vadd(vmul(V3((float)lx, (float)ly, (float)lz), voxel_scale), *brick_position);
+                if (e->voxel) { e->voxel[0] = lx; e->voxel[1] = ly; e->voxel[2] = lz; }
                 return 1;
             }
         }
@@ -439,6 +441,7 @@ static int GridHit(const Env *e, const Ray *r, float t_min, float t_max, v3 *hit
             if (e->c) e->c->bricks_entered++;
             if (BrickHit(e, r, t_min, grid_t_max, ray_delta, ray_step, g_scale, brick_index, &brick_min, hit)) {
                 *hit_min = brick_min;
+                if (e->voxel) { e->voxel[0] += lx * s->brick_dimensions; e->voxel[1] += ly * s->brick_dimensions; e->voxel[2] += lz * s->brick_dimensions; }
                 return 1;
             }
         }
@@ -603,7 +606,7 @@ static void shade_pixel(const Env *e, int px, int py, float out_f[4], uint8_t ou
  */
 void oracle_render_rows(const oracle_scene *scene, const oracle_push *pc, int y0, int y1,
                         float *rgba32f, uint8_t *rgba8, oracle_counters *counters) {
-    Env e = {scene, pc, counters};
+    Env e = {scene, pc, counters, 0};
     const int W = (int)pc->image_width;
     for (int y = y0; y < y1; y++) {
         for (int x = 0; x < W; x++) {
@@ -616,7 +619,7 @@ void oracle_render_rows(const oracle_scene *scene, const oracle_push *pc, int y0
 /* Render an arbitrary list of pixels (x,y pairs); outputs are packed per pixel. */
 void oracle_render_pixels(const oracle_scene *scene, const oracle_push *pc, const int32_t *xy, uint64_t n,
                           float *rgba32f, uint8_t *rgba8, oracle_counters *counters) {
-    Env e = {scene, pc, counters};
+    Env e = {scene, pc, counters, 0};
     for (uint64_t i = 0; i < n; i++)
         shade_pixel(&e, xy[2 * i], xy[2 * i + 1], rgba32f ? rgba32f + 4 * i : 0, rgba8 ? rgba8 + 4 * i : 0);
 }
@@ -624,7 +627,7 @@ void oracle_render_pixels(const oracle_scene *scene, const oracle_push *pc, cons
 /* Single-ray probe for known-answer tests: returns hit flag, fills the record. */
 int oracle_grid_hit(const oracle_scene *scene, const oracle_push *pc, const float origin[3], const float dir[3],
                     float out_point[3], float out_normal[3], float *out_t, uint32_t *out_index, oracle_counters *counters) {
-    Env e = {scene, pc, counters};
+    Env e = {scene, pc, counters, 0};
     Ray r = CreateRay(V3(origin[0], origin[1], origin[2]), V3(dir[0], dir[1], dir[2]));
     HitRecord hit; memset(&hit, 0, sizeof hit);
     v3 hmin = V3(0, 0, 0);
@@ -641,12 +644,35 @@ int oracle_grid_hit(const oracle_scene *scene, const oracle_push *pc, const floa
 int oracle_grid_hit_raw(const oracle_scene *scene, const oracle_push *pc, const float origin[3], const float dir[3],
                         uint32_t ignore_type_material, float internal_reflection, float out_point[3], float out_normal[3],
                         float *out_t, uint32_t *out_index, oracle_counters *counters) {
-    Env e = {scene, pc, counters};
+    Env e = {scene, pc, counters, 0};
     Ray r;
     r.origin = V3(origin[0], origin[1], origin[2]);
     r.direction = V3(dir[0], dir[1], dir[2]);
     r.internal_reflection = internal_reflection;
     r.ignore_type_material = ignore_type_material;
+    HitRecord hit; memset(&hit, 0, sizeof hit);
+    v3 hmin = V3(0, 0, 0);
+    const int ok = GridHit(&e, &r, 0.00001f, INFINITY, &hmin, &hit);
+    out_point[0] = hit.point.x; out_point[1] = hit.point.y; out_point[2] = hit.point.z;
+    out_normal[0] = hit.normal.x; out_normal[1] = hit.normal.y; out_normal[2] = hit.normal.z;
+    *out_t = hit.t; *out_index = hit.index;
+    return ok;
+}
+
+/* Both probes in one, with the voxel of the hit: raw == 0 is oracle_grid_hit, otherwise oracle_grid_hit_raw(..., MAT_NONE, 1.0).
+ * out_voxel: the walk's voxel coordinates (y as the shader counts it), untouched for a miss. */
+int oracle_grid_hit_voxel(const oracle_scene *scene, const oracle_push *pc, const float origin[3], const float dir[3], int raw,
+                          float out_point[3], float out_normal[3], float *out_t, uint32_t *out_index, int32_t out_voxel[3]) {
+    Env e = {scene, pc, 0, out_voxel};
+    Ray r;
+    if (raw) {
+        r.origin = V3(origin[0], origin[1], origin[2]);
+        r.direction = V3(dir[0], dir[1], dir[2]);
+        r.internal_reflection = 1.0f;
+        r.ignore_type_material = MAT_NONE;
+    } else {
+        r = CreateRay(V3(origin[0], origin[1], origin[2]), V3(dir[0], dir[1], dir[2]));
+    }
     HitRecord hit; memset(&hit, 0, sizeof hit);
     v3 hmin = V3(0, 0, 0);
     const int ok = GridHit(&e, &r, 0.00001f, INFINITY, &hmin, &hit);
