@@ -420,6 +420,7 @@ pub extern fn vrt_grid_insert_many(g: ?*Grid, xyz: [*c]const u32, materials: [*c
 pub extern fn vrt_grid_remove_many(g: ?*Grid, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_grid_remove(g: ?*Grid, x: u64, y: u64, z: u64) c_int;
 pub extern fn vrt_grid_compact(g: ?*Grid, out: *[2]u32) c_int;
+pub extern fn vrt_grid_scroll(g: ?*Grid, cx: i32, cy: i32, cz: i32, out: *[2]u32) c_int;
 pub extern fn vrt_grid_device_state(g: ?*const Grid) [*c]const GridState;
 pub extern fn vrt_grid_data(g: ?*const Grid, id: BufferId, nbytes: [*c]u64) ?*const anyopaque;
 pub extern fn vrt_grid_active_bricks(g: ?*const Grid) u32;
@@ -453,6 +454,7 @@ pub extern fn vrt_insert_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, materials
 pub extern fn vrt_remove_voxels(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_remove_voxels_device(ctx: ?*Ctx, xyz: [*c]const u32, n: u64) c_int;
 pub extern fn vrt_compact_bricks(ctx: ?*Ctx, out: *[2]u32) c_int;
+pub extern fn vrt_scroll_scene(ctx: ?*Ctx, cx: i32, cy: i32, cz: i32, out: *[2]u32) c_int;
 pub extern fn vrt_grid_fill_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_grid_clear_shapes(g: ?*Grid, shapes: [*c]const Shape, n: u64) c_int;
 pub extern fn vrt_fill_shapes(ctx: ?*Ctx, shapes: [*c]const Shape, n: u64) c_int;

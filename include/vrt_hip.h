@@ -490,6 +490,23 @@ int vrt_grid_remove(vrt_grid *g, uint64_t x, uint64_t y, uint64_t z);
  * or a loaded cell names a brick >= A.  out (may be NULL) = {A, L}, on success.  Deltas: per array, the first to the last element
  * whose value changed; inactive where none did. */
 int vrt_grid_compact(vrt_grid *g, uint32_t out[2]);
+/* Scrolling: the scene moves by whole cells (bricks) inside the grid (the reference has none).  cx, cy, cz are cells in the
+ * coordinates vrt_grid_insert takes: the content of voxel (x, y, z) is afterwards at (x + cx B, y + cy B, z + cz B); with the y flip
+ * of Grid.zig:135 the stored cell row moves by -cy.  No brick moves: the shift permutes the two per-cell arrays.  With stored cell
+ * coordinates c, the shift s in those coordinates and src = c - s:
+ *   src inside the grid on every axis   brick_statuses bit and brick_indices entry of c = those of src.  A PURE SHIFT: the stale
+ *                                       brick_indices entry of a cell that is not loaded moves with it, no status bit decides anything;
+ *   src outside the grid                status bit 0 and brick_indices 0, a fresh grid's values.
+ * The bits of the last status word beyond the grid's last cell keep their value.  brick_occupancy, brick_start_indices,
+ * material_indices, active_bricks and the material cursor are NOT touched (brick_start_indices need not be allocation-shaped: a scene
+ * built by the reference's own builder scrolls too): the bricks of the loaded cells that left the grid are dead as vrt_grid_compact
+ * defines it, and a compaction gives their slots back; the slab that entered is empty, for vrt_grid_write_boxes / _fill_shapes /
+ * _insert_many to fill.  A zero shift writes nothing; |shift| >= the grid's cells on an axis empties the grid, a legal call; the
+ * shifts are worked in 64-bit signed arithmetic (INT32_MIN is safe).  out (may be NULL) = {loaded cells that left the grid, loaded
+ * cells afterwards}.  Deltas of brick_statuses and brick_indices: the first to the last element whose value changed; inactive where
+ * none did.  The world stays in place when the host moves min_point / max_point of the grid state it uploads by minus the shift times
+ * the scale. */
+int vrt_grid_scroll(vrt_grid *g, int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]);
 const vrt_grid_state *vrt_grid_device_state(const vrt_grid *g);
 /* Borrowed pointer + byte size of host array `id` (GRID_STATE..MATERIAL_INDEX;
  * MATERIALS is not part of the grid => NULL). */
@@ -805,6 +822,18 @@ int vrt_remove_voxels_device(vrt_ctx *ctx, const uint32_t *xyz, uint64_t n);
  * grid state and for one of the multi-GPU pipeline.  out (may be NULL) = {A, L}, on success.  The derived structures are refreshed for
  * the written ranges (the renamed cells, the filled holes, the cleared tail) before the next frame or query. */
 int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]);
+/* ---- Scene scrolling on the uploaded scene ------------------------------------------------------------------------------
+ * vrt_grid_scroll on the GPU, for a host that follows a player through a world larger than its grid: on a context whose bindings
+ * 2-6 equal a vrt_grid's arrays, after vrt_scroll_scene(ctx, cx, cy, cz, out) they equal that grid's arrays after
+ * vrt_grid_scroll(g, cx, cy, cz, out), byte for byte.  Only bindings 2 and 3 are read and written (one bit and one u32 per cell: an
+ * eighth mode of the vrt_edit_* kernels copies them and writes them back shifted); binding 5 need not be allocation-shaped.  Errors and
+ * ordering as for vrt_compact_bricks: one scene write on the context's stream, a refused call changes no scene byte, one small
+ * status read-back ends the call; VRT_E_STATE for a context without a grid state and for one of the multi-GPU pipeline.  out (may be
+ * NULL) = {loaded cells that left, loaded cells afterwards}, on success.  The derived structures are refreshed for the range of
+ * cells whose status bit or index changed, before the next frame, query or edit: those see the scrolled scene without a vrt_wait.
+ * THE STREAMING STEP is vrt_scroll_scene, vrt_compact_bricks (the bricks of the cells that left are dead), then vrt_write_boxes /
+ * vrt_fill_shapes of the slab that entered. */
+int vrt_scroll_scene(vrt_ctx *ctx, int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]);
 /* ---- Shape edits on the uploaded scene: fill and clear boxes and spheres ---------------------------------------------------
  * The write-side twin of vrt_query_boxes: a host that edits with a brush (dig a sphere, place a box) sends 32 bytes per shape and
  * not 13 bytes per voxel, and the device works per 32-bit occupancy word, not per voxel (two more modes of the vrt_edit_* kernels).

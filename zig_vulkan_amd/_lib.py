@@ -281,6 +281,7 @@ SIGNATURES = {
     "vrt_grid_remove": (C.c_int, [_grid, C.c_uint64, C.c_uint64, C.c_uint64]),
     "vrt_grid_remove_many": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
     "vrt_grid_compact": (C.c_int, [_grid, _P(C.c_uint32 * 2)]),
+    "vrt_grid_scroll": (C.c_int, [_grid, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint32 * 2)]),
     "vrt_grid_device_state": (_P(GridState), [_grid]),
     "vrt_grid_data": (C.c_void_p, [_grid, C.c_int, _P(C.c_uint64)]),
     "vrt_grid_active_bricks": (C.c_uint32, [_grid]),
@@ -324,6 +325,7 @@ SIGNATURES = {
     "vrt_read_schedule": (C.c_int, [_ctx, C.c_uint32, C.c_void_p, C.c_uint64]),
     "vrt_schedule_sort": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vrt_compact_bricks": (C.c_int, [_ctx, _P(C.c_uint32 * 2)]),
+    "vrt_scroll_scene": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint32 * 2)]),
     "vrt_grid_fill_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
     "vrt_grid_clear_shapes": (C.c_int, [_grid, C.c_void_p, C.c_uint64]),
     "vrt_fill_shapes": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),

@@ -238,6 +238,46 @@ int BrickGrid::compact(uint32_t out[2]) {
     return VRT_OK;
 }
 
+int BrickGrid::scroll(int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]) {
+    const vrt_grid_state &d = device_state_;
+    const int64_t dim[3] = {d.dim_x, d.dim_y, d.dim_z}; // x, the stored (flipped) y, z
+    int64_t s[3] = {cx, -(int64_t)cy, cz};              // Grid.zig:135: a step up in y is a step down in the stored rows
+    for (int k = 0; k < 3; k++) s[k] = std::max(-dim[k], std::min(dim[k], s[k])); // (at +-dim every source lies outside: the grid empties)
+    const uint64_t cells = brick_indices.size();
+    const size_t words = brick_statuses.size();
+    const uint32_t tail = cells % 32u ? ~0u << (cells % 32u) : 0u; // the bits of the last word beyond the last cell
+    uint64_t before = 0, after = 0;
+    for (size_t w = 0; w < words; w++) before += (uint64_t)__builtin_popcount(brick_statuses[w] & (w + 1 == words ? ~tail : ~0u));
+    if (out) out[0] = 0, out[1] = (uint32_t)before;
+    if (!s[0] && !s[1] && !s[2]) return VRT_OK;
+
+    std::vector<uint32_t> status(words, 0u), index((size_t)cells, 0u); // a fresh grid's values where no source lies inside
+    status[words - 1] = brick_statuses[words - 1] & tail;
+    const int64_t shift = s[0] + dim[0] * (s[2] + dim[2] * s[1]); // of the linear index, for the cells whose source lies inside on every axis
+    for (int64_t y = std::max<int64_t>(0, s[1]); y < std::min(dim[1], dim[1] + s[1]); y++)
+        for (int64_t z = std::max<int64_t>(0, s[2]); z < std::min(dim[2], dim[2] + s[2]); z++)
+            for (int64_t x = std::max<int64_t>(0, s[0]); x < std::min(dim[0], dim[0] + s[0]); x++) {
+                const uint64_t c = (uint64_t)(x + dim[0] * (z + dim[2] * y)), src = c - (uint64_t)shift;
+                index[c] = brick_indices[src];
+                if ((brick_statuses[src / 32] >> (src % 32)) & 1u) status[c / 32] |= 1u << (c % 32), after++;
+            }
+    if (out) out[0] = (uint32_t)(before - after), out[1] = (uint32_t)after;
+
+    // the new values into the old arrays (which stay where they are: vrt_grid_data's pointers hold); the delta of each runs from its
+    // first to its last element that changed
+    auto replace = [](std::vector<uint32_t> &old, const std::vector<uint32_t> &now, DeviceDataDelta &dd) {
+        size_t first = 0, last = old.size();
+        while (first < last && old[first] == now[first]) first++;
+        while (last > first && old[last - 1] == now[last - 1]) last--;
+        if (first == last) return;
+        std::copy(now.begin() + first, now.begin() + last, old.begin() + first);
+        dd.registerDeltaRange(first, last - 1);
+    };
+    replace(brick_statuses, status, brick_statuses_delta);
+    replace(brick_indices, index, brick_indices_delta);
+    return VRT_OK;
+}
+
 void BrickGrid::getVoxels(const uint32_t *xyz, uint64_t n, uint16_t *out) const {
     const vrt_grid_state &d = device_state_;
     const uint32_t b = brick_dimension_;

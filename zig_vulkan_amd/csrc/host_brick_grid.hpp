@@ -75,6 +75,16 @@ public:
     // out (may be null) = {A, L}.  Deltas: per array, the first to the last element whose value changed.  Single-threaded.
     int compact(uint32_t out[2]);
 
+    // Scrolling (the reference has none: include/vrt_hip.h defines it).  The scene moves by whole cells, (cx, cy, cz) in the coordinates
+    // insert takes: the content of voxel (x, y, z) is afterwards at (x + cx B, y + cy B, z + cz B), so with the y flip the stored cell
+    // row moves by -cy.  A pure shift of brick_statuses and brick_indices with zero fill: cell c takes both entries of cell c - s (the
+    // stale index of a cell that is not loaded moves with it), or status 0 and index 0 where c - s lies outside the grid; the bits of
+    // the last status word beyond the last cell keep their value.  The three other arrays, active_bricks and the material cursor stay:
+    // the bricks of the loaded cells that left are dead as compact() defines it.  out (may be null) = {loaded cells that left, loaded
+    // cells afterwards}.  A zero shift writes nothing; |shift| >= dim on an axis empties the grid; the shifts are worked in 64 bits.
+    // Deltas: per array, the first to the last element whose value changed.  Single-threaded.
+    int scroll(int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]);
+
     // Volume queries (the reference has none: include/vrt_hip.h defines them).  Coordinates as insert takes them.  They read the five
     // arrays only and register no delta.  A voxel is solid when its cell's status bit and its occupancy bit are 1; the status bit is
     // tested first (brick_indices of a cell that is not loaded is stale).

@@ -264,6 +264,11 @@ int vrt_grid_compact(vrt_grid *g, uint32_t out[2]) {
     return reinterpret_cast<vrt::BrickGrid *>(g)->compact(out);
 }
 
+int vrt_grid_scroll(vrt_grid *g, int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]) {
+    if (!g) return VRT_E_INVALID_ARG;
+    return reinterpret_cast<vrt::BrickGrid *>(g)->scroll(cx, cy, cz, out);
+}
+
 int vrt_grid_get_voxels(const vrt_grid *g, const uint32_t *xyz, uint64_t n, uint16_t *out) {
     if (!g || (n && (!xyz || !out))) return VRT_E_INVALID_ARG;
     reinterpret_cast<const vrt::BrickGrid *>(g)->getVoxels(xyz, n, out);

@@ -1,7 +1,8 @@
 // vrt_edit.hip — the edits of the uploaded scene behind the C ABI: batched voxel inserts and removals (vrt_insert_voxels,
 // vrt_remove_voxels and their _device forms), brick compaction (vrt_compact_bricks), the shape, paint and dense box edits
-// (vrt_fill_shapes, vrt_clear_shapes, vrt_paint_shapes, vrt_write_boxes, vrt_write_boxes_device), the allocation state the inserts
-// continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels vrt_edit_* and their host side.
+// (vrt_fill_shapes, vrt_clear_shapes, vrt_paint_shapes, vrt_write_boxes, vrt_write_boxes_device), scene scrolling (vrt_scroll_scene),
+// the allocation state the inserts continue (vrt_scene_bricks) and the read-back of a scene buffer (vrt_read_buffer): their kernels
+// vrt_edit_* and their host side.
 // BrickGrid.insert (Grid.zig:129-194) for a whole batch, on the context's scene buffers, with the bytes a vrt_grid gives after
 // vrt_grid_insert_many; a failed batch writes nothing.  The kernels are integer work only, so every flavour compiles them to the same
 // instructions.  "Binding k" below is buffer id k of vrt_buffer_id (binding 5 = VRT_BUF_BRICK_START_INDEX), as in include/vrt_hip.h's
@@ -31,6 +32,7 @@
 //   clear     4   x                                         last   phases 0, 1 x        cell
 //   paint     5   x                                                x           x        cell
 //   write     6   x         x     x           x    x        last   phases 0, 1 x        cell, oom, value
+//   scroll    7                                                        phases 0, 1 x        none ("not allocation-shaped" neither)
 // ("last": vrt_edit_table runs behind the phase that reads the scratch words; only an insert needs its last writers.)  Beyond the table:
 //   remove (vrt_grid_remove_many; §12)  a voxel of a cell that is not loaded is a no-op; validation elects one voxel per touched loaded
 //     cell.  Phase 0 clears the occupancy bits (atomicAnd); phase 1, a kernel boundary after every clear, has the elected voxel read its
@@ -57,6 +59,13 @@
 //     any other element is an error.  It is a fill of `set` with a material per voxel (read again from the elements in phase 0: a whole
 //     row as one 8-byte store, a whole nibble as a dword, the rest as bytes, never an entry the item does not set) and a clear of `clear`
 //     in one chain; the boxes are disjoint, so no voxel has two writers.
+//   scroll (vrt_grid_scroll; §23)  has no batch and validates nothing: it reads and writes bindings 2 and 3 alone, over the cells of the
+//     grid in at most kEditCopyGroups workgroups, and its scratch words are the per-voxel words of a batch of `cells` voxels.  write
+//     phase 0: binding 3 copied into vcell and binding 2's words into vinfo, in 16-byte pieces.  Phase 1 (a kernel boundary after every
+//     copy: it overwrites what phase 0 read): cell c takes the copies' bit and entry of c - S, S = sx + dim_x (sz + dim_z sy), where
+//     c - s lies inside the grid on each axis (a linear index in range is not enough: rows wrap), else 0 and 0; a wave's 64 new bits are
+//     one __ballot, stored as two whole status words by two lanes (lanes beyond the last cell put the old bit back); only values that
+//     changed are stored.  The range of changed cells and the loaded cells before and afterwards go to EditStatus, one atomic per wave.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstddef>
@@ -74,8 +83,8 @@ constexpr uint32_t kEditBlock = 256;      // threads per workgroup of the per-vo
 constexpr uint32_t kEditScanBlock = 1024; // the one workgroup that scans the per-workgroup counts
 constexpr uint32_t kEditNone = 0xFFFFFFFFu;
 constexpr uint32_t kEditOpInsert = 0, kEditOpRemove = 1, kEditOpCompact = 2, kEditOpFill = 3, kEditOpClear = 4, kEditOpPaint = 5,
-                   kEditOpWrite = 6; // EditArgs::op
-constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's grid-stride passes (copy, zero), at most
+                   kEditOpWrite = 6, kEditOpScroll = 7; // EditArgs::op
+constexpr uint32_t kEditCopyGroups = 1024; // workgroups of compaction's and scrolling's grid-stride passes (copy, zero, shift), at most
 
 // The fields of EditArgs::vinfo[i], voxel or item i as vrt_edit_validate recorded it.  (Compaction keeps its live flags in these words.)
 constexpr uint32_t kInfoNewCell = 0x80000000u; // bit 31: its cell was not loaded when the batch began
@@ -111,10 +120,11 @@ struct EditStatus {
     uint32_t ok;            // the state's shape flag
     uint64_t cursor;        // next material entry after the batch
     uint32_t cell_lo, cell_hi;  // cells that became loaded (binding 2: their status words, binding 3: their entries); removal: unloaded;
-                                // compaction: renamed (binding 3 only)
+                                // compaction: renamed (binding 3 only); scrolling: whose status bit or entry of binding 3 changed
     uint32_t occ_lo, occ_hi;    // bytes of binding 4 that gained a bit; removal: that lost one; compaction: first hole to the end of brick A - 1
     uint32_t mat_lo, mat_hi;    // bytes of binding 6 written
     uint64_t painted;           // paint: the voxels painted
+    uint32_t was_loaded, loaded; // scrolling: the loaded cells before and afterwards
 };
 
 // One shape of a fill or clear batch as the kernels read it (64 bytes): ClippedShape (y flipped; index 0 = x, 1 = flipped y, 2 = z),
@@ -148,7 +158,8 @@ struct EditArgs {
     uint32_t rescan;         // 1: vrt_edit_begin also clears the accumulators of the scan of binding 5
     uint32_t op;             // kEditOpInsert / ... / kEditOpPaint / kEditOpWrite (uniform: every kernel of a chain sees the same)
     uint32_t phase;          // removal, vrt_edit_write: 0 clears occupancy bits, 1 clears the status bits of emptied bricks;
-                             // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells
+                             // compaction: 0 copies the records of the bricks that move, 1 clears the tail and renames the cells;
+                             // scrolling: 0 copies bindings 2 and 3 into the scratch words, 1 writes them back shifted
     // scratch (the context's, grown on demand)
     uint32_t *cell_first;    // [cells] lowest batch index of a voxel in a cell that is not loaded (removal: that is loaded); kEditNone between batches
     uint32_t *vcell;         // [n] the voxel's cell (kEditNone: not written)
@@ -167,9 +178,10 @@ struct EditArgs {
     uint32_t brick_alloc;
     uint32_t start_words;           // entries of binding 5 scanned by vrt_edit_scan_start (= brick_alloc)
     uint64_t material_entries;      // bytes of binding 6 (brick_alloc * B^3)
-    uint32_t cells;                 // compaction: cells of the grid (n = max(cells, brick_alloc): the threads of its per-cell kernels)
+    uint32_t cells;                 // compaction: cells of the grid (n = max(cells, brick_alloc): the threads of its per-cell kernels); scrolling: idem
     uint32_t only;                  // paint: the material an entry must hold to be painted (VRT_PAINT_ANY: whatever it holds)
     const uint16_t *data;           // write: the boxes' elements (2-byte aligned; behind every older member, whose offsets stay)
+    int32_t shift[3];               // scrolling: the shift in stored cells along x, the flipped y and z, each within [-dim, dim]
 };
 
 } // namespace vrt
@@ -477,6 +489,7 @@ __global__ void __launch_bounds__(64) vrt_edit_begin(EditArgs a) {
     s.occ_lo = kEditNone, s.occ_hi = 0;
     s.mat_lo = kEditNone, s.mat_hi = 0;
     s.painted = 0;
+    s.was_loaded = 0, s.loaded = 0;
     *a.out = s;
     if (a.rescan) {
         a.state->first_unset = kEditNone;
@@ -800,6 +813,59 @@ __device__ inline void compact_write(const EditArgs &a) {
     wave_range(&a.out->cell_lo, lo, hi);
 }
 
+// n words from src to dst: lanes on consecutive 16-byte pieces where both are so aligned, the (up to three) words behind the pieces singly
+__device__ inline void copy_words(uint32_t *dst, const uint32_t *src, uint32_t n, uint32_t i, uint32_t stride) {
+    const bool aligned = !((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u);
+    const uint32_t pieces = aligned ? n >> 2 : 0u; // (below 2^30, and stride <= 2^18: t does not wrap)
+    for (uint32_t t = i; t < pieces; t += stride) reinterpret_cast<uint4 *>(dst)[t] = reinterpret_cast<const uint4 *>(src)[t];
+    for (uint64_t t = ((uint64_t)pieces << 2) + i; t < n; t += stride) dst[t] = src[t];
+}
+
+// scrolling's two passes over the cells (every lane of the wave gets to phase 1's ballots and reductions)
+__device__ inline void scroll_write(const EditArgs &a) {
+    const uint32_t cells = a.cells, words = (cells >> 5) + ((cells & 31u) ? 1u : 0u);
+    const uint32_t stride = gridDim.x * kEditBlock;
+    if (a.phase == 0) {
+        const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
+        copy_words(a.vcell, a.index, cells, i, stride);
+        copy_words(a.vinfo, a.status, words, i, stride);
+        return;
+    }
+    const uint32_t dim_x = a.dim_x, dim_z = a.dim_z, dim_y = a.voxel_dim_y / a.b;
+    const uint32_t sx = (uint32_t)a.shift[0], sy = (uint32_t)a.shift[1], sz = (uint32_t)a.shift[2];
+    const uint32_t shift = sx + dim_x * (sz + dim_z * sy); // S modulo 2^32: c - S is exact for a source inside the grid
+    uint32_t lo = kEditNone, hi = 0, was_loaded = 0, loaded = 0;
+    // a wave's 64 cells begin at a multiple of 64: two whole status words (uniform trips per wave; 64-bit: cells reach 2^32 - 1)
+    for (uint64_t base = blockIdx.x * kEditBlock; base < cells; base += stride) {
+        const uint64_t at = base + threadIdx.x;
+        const uint32_t c = (uint32_t)at;
+        const bool in = at < cells, held = (at >> 5) < words; // held: the cell's status word exists (beyond the last cell: its bit stays)
+        const uint32_t old_word = held ? a.vinfo[c >> 5] : 0u;
+        uint32_t bit = (old_word >> (c & 31u)) & 1u, was = 0;
+        if (in) {
+            const uint32_t old_index = a.vcell[c];
+            const uint32_t x = c % dim_x, t = c / dim_x, z = t % dim_z, y = t / dim_z;
+            uint32_t index = 0;
+            was = bit, bit = 0;
+            if (x - sx < dim_x && z - sz < dim_z && y - sy < dim_y) { // (unsigned: a source below 0 wraps beyond every dim)
+                const uint32_t src = c - shift;
+                bit = (a.vinfo[src >> 5] >> (src & 31u)) & 1u;
+                index = a.vcell[src];
+            }
+            if (index != old_index) a.index[c] = index;
+            if (index != old_index || bit != was) lo = min(lo, c), hi = max(hi, c);
+        }
+        const uint64_t now = __ballot(bit != 0u);
+        const uint32_t word = lane_id() < 32u ? (uint32_t)now : (uint32_t)(now >> 32);
+        if (!(lane_id() & 31u) && held && word != old_word) a.status[c >> 5] = word;
+        was_loaded += (uint32_t)__popcll(__ballot(was != 0u));
+        loaded += (uint32_t)__popcll(__ballot(in && bit != 0u));
+    }
+    wave_range(&a.out->cell_lo, lo, hi);
+    if (lane_id() == 0 && was_loaded) atomicAdd(&a.out->was_loaded, was_loaded);
+    if (lane_id() == 0 && loaded) atomicAdd(&a.out->loaded, loaded);
+}
+
 // `material` into the entries of binding 6 that `keep` names, bit k = entries[k], entries = binding 6 + slot (slot + 31 lies within the
 // brick's B^3 entries): a whole run of 32 on a 16-byte aligned slot as two 16-byte stores, otherwise nibble by nibble (store_nibble)
 __device__ inline void store_materials(uint8_t *entries, uint32_t slot, uint32_t keep, uint32_t material) {
@@ -937,6 +1003,10 @@ __global__ void __launch_bounds__(kEditBlock) vrt_edit_write(EditArgs a) {
         compact_write(a);
         return;
     }
+    if (a.op == kEditOpScroll) {
+        scroll_write(a);
+        return;
+    }
     const uint32_t i = blockIdx.x * kEditBlock + threadIdx.x;
     uint32_t cell_lo = kEditNone, cell_hi = 0, occ_lo = kEditNone, occ_hi = 0, mat_lo = kEditNone, mat_hi = 0;
     const uint32_t cell = i < a.n ? a.vcell[i] : kEditNone;
@@ -1050,8 +1120,10 @@ constexpr EditOp kEditOps[] = {
     // write: a fill's ranking, a clear's two phases, and the scratch words cleared behind the phase that reads them
     {{kValidate, kCount, kScanGroups, kRank, kResolve, kWrite, kWritePhase1, kTable}, kEditErrShape | kEditErrCell | kEditErrOom | kEditErrValue,
      kB2 | kB3 | kB4 | kB5 | kB6, "; nothing was written", "dense box writes are", false, true},
+    // scroll: the two grid-stride passes, 2.  Nothing is validated (no error of its own, and whatever binding 5 holds will do); no cell's scratch word is touched
+    {{over(kWrite, 2), over(kWritePhase1, 2)}, 0u, kB2 | kB3, "; nothing was scrolled", "scene scrolling is", false, false},
 };
-static_assert(sizeof(kEditOps) / sizeof(kEditOps[0]) == kEditOpWrite + 1, "one row per op");
+static_assert(sizeof(kEditOps) / sizeof(kEditOps[0]) == kEditOpScroll + 1, "one row per op");
 
 // what every entry point checks before it touches the device: the scene is there and this context may edit it ...
 int edit_allowed(vrt_ctx *ctx, uint32_t op) {
@@ -1081,9 +1153,9 @@ int not_shaped(vrt_ctx *ctx) {
 // scratch for a batch of n voxels: the per-cell words (once, all 0xFFFFFFFF; every batch leaves them so), the per-voxel words, the
 // per-workgroup counts and, for the ops that need it, the last-writer table (a power of two of at least 2n entries, zeroed).  No kernel
 // of an earlier batch is in flight: every batch ends with a wait for its status.  Nothing to launch where the state is known not to be
-// allocation-shaped.
+// allocation-shaped (to an op that reports it).
 int edit_scratch(vrt_ctx *ctx, uint64_t n, uint32_t op) {
-    if (ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
+    if ((kEditOps[op].errs & vrt::kEditErrShape) && ctx->edit_state_valid && !ctx->edit_ok) return not_shaped(ctx);
     if (!ctx->d_edit_cell_first) {
         const uint64_t cells = (uint64_t)ctx->cfg.dim_x * ctx->cfg.dim_y * ctx->cfg.dim_z;
         VRT_HIP(ctx, ctx->res.device(&ctx->d_edit_cell_first, cells * sizeof(uint32_t)));
@@ -1284,6 +1356,28 @@ int compact(vrt_ctx *ctx, uint32_t out[2]) {
     return VRT_OK;
 }
 
+// the scene shifted by whole cells: the two passes over the cells, as one scene write.  A zero shift without `out` has nothing to do;
+// with it, the chain counts the loaded cells and stores nothing (it stores only values that change).
+int scroll(vrt_ctx *ctx, int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]) {
+    const int64_t dim[3] = {ctx->cfg.dim_x, ctx->cfg.dim_y, ctx->cfg.dim_z};
+    int64_t shift[3] = {cx, -(int64_t)cy, cz}; // Grid.zig:135: the stored cell row moves by -cy
+    for (int k = 0; k < 3; k++) shift[k] = std::max(-dim[k], std::min(dim[k], shift[k])); // (at +-dim every source lies outside: the grid empties)
+    if (!out && !shift[0] && !shift[1] && !shift[2]) return VRT_OK;
+    const uint64_t cells = (uint64_t)dim[0] * dim[1] * dim[2];
+    int rc = edit_scratch(ctx, cells, vrt::kEditOpScroll); // its scratch: the per-voxel words of a batch of `cells` voxels
+    if (rc != VRT_OK) return rc;
+    vrt::EditArgs a = edit_args(ctx, vrt::kEditOpScroll, nullptr, nullptr, 0);
+    a.cells = (uint32_t)cells;
+    for (int k = 0; k < 3; k++) a.shift[k] = (int32_t)shift[k];
+    const uint64_t groups = (cells + vrt::kEditBlock - 1u) / vrt::kEditBlock;
+    vrt::EditStatus s;
+    rc = run_edit(ctx, a, &s, 0, (uint32_t)std::min<uint64_t>(groups, vrt::kEditCopyGroups));
+    if (rc != VRT_OK) return rc;
+    if (out) out[0] = s.was_loaded - s.loaded, out[1] = s.loaded;
+    mark_written(ctx, s, kEditOps[vrt::kEditOpScroll].writes, 0); // the cells whose bit or entry changed; none: nothing was written
+    return VRT_OK;
+}
+
 // What the records of the item modes have in common: the shape's clipped range, and where its items lie, behind the *items of the
 // shapes before it.  false: the batch's items reach 2^31 (the sum is tested before it can wrap: *items < 2^31 on entry).
 bool place_items(const vrt::ClippedShape &c, uint32_t b, uint64_t *items, vrt::ShapeRec *r) {
@@ -1420,6 +1514,14 @@ int vrt_compact_bricks(vrt_ctx *ctx, uint32_t out[2]) {
     const int rc = edit_prepare(ctx, vrt::kEditOpCompact);
     if (rc != VRT_OK) return rc;
     return compact(ctx, out);
+}
+
+int vrt_scroll_scene(vrt_ctx *ctx, int32_t cx, int32_t cy, int32_t cz, uint32_t out[2]) {
+    if (!ctx) return VRT_E_INVALID_ARG;
+    DeviceGuard dg(ctx->device);
+    const int rc = edit_prepare(ctx, vrt::kEditOpScroll);
+    if (rc != VRT_OK) return rc;
+    return scroll(ctx, cx, cy, cz, out);
 }
 
 int vrt_scene_bricks(vrt_ctx *ctx, uint32_t out[2]) {

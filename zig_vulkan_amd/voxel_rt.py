@@ -90,6 +90,15 @@ class BrickGrid:
         check(lib.vrt_grid_compact(self._h, C.byref(out)))
         return int(out[0]), int(out[1])
 
+    def scroll(self, cx: int, cy: int, cz: int) -> Tuple[int, int]:
+        """vrt_grid_scroll: the scene moves by (cx, cy, cz) whole cells, in insert's coordinates: the content of voxel (x, y, z) is
+        afterwards at (x + cx B, y + cy B, z + cz B); what leaves the grid is gone (its bricks are dead: compact() gives them back) and
+        the slab that enters is empty.  Only brick_statuses and brick_indices change.  Returns (loaded cells that left the grid, loaded
+        cells afterwards)."""
+        out = (C.c_uint32 * 2)()
+        check(lib.vrt_grid_scroll(self._h, cx, cy, cz, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     def fill_shapes(self, shapes) -> None:
         """vrt_grid_fill_shapes: the shapes (box(...) / sphere(...) records, or a SHAPE_DTYPE array) filled with their materials, as
         insert_many of their voxels, shapes in array order; all or nothing."""
@@ -668,6 +677,15 @@ class VoxelRT:
         after compact(), and insert_voxels continues from the bricks that are left.  Returns (allocated bricks before, after)."""
         out = (C.c_uint32 * 2)()
         self._check(self._lib.vrt_compact_bricks(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
+    def scroll_scene(self, cx: int, cy: int, cz: int) -> Tuple[int, int]:
+        """BrickGrid.scroll on the scene the context holds (vrt_scroll_scene): the scene moves by (cx, cy, cz) cells, bindings 2-6
+        afterwards equal the host grid's arrays after scroll(cx, cy, cz).  Frames, queries and edits issued after it see the scrolled
+        scene.  The streaming step: scroll_scene, compact_bricks, write_boxes of the slab that entered.  Returns (loaded cells that
+        left the grid, loaded cells afterwards)."""
+        out = (C.c_uint32 * 2)()
+        self._check(self._lib.vrt_scroll_scene(self._h, cx, cy, cz, C.byref(out)))
         return int(out[0]), int(out[1])
 
     def read_buffer(self, buf_id: int) -> np.ndarray:
